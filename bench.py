@@ -17,6 +17,10 @@ flight by default (--inflight); the strictly serial figures are measured in the 
 
 Scaling is weak: every rank owns S scenarios (different seeds); no collective inside the solve.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the steps and prints the line.  Everything measured beside the line -- the strictly
+serial steps (per-launch roofline), the planner-semantics steps, the configs[1] latency figure and the CPU baseline --
+runs only with --full.  --dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -70,6 +74,37 @@ def host_cores():
     return n
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, outputs):
+    """The last timed step's results as a caller receives them, DIR/<name>.npy in float64: per-candidate success flag, cost,
+    gate verdict and total duration, the per-scenario records (dist.RECORD_WIDTH columns) and the winners' trajectories
+    packed as getTrajs returns them.  Above DUMP_LIMIT_BYTES in all, every array keeps a fixed, seeded sample of its rows
+    (the row indices in <name>_rows.npy).  A candidate whose solve failed can have no cost (NaN): such entries are
+    written as 0, and cost_defined / total_duration_defined hold 1 where the value is a number, 0 where it is not.  A
+    scenario without an accepted candidate has no cost and duration in its record (NaN in dist.scenario_records): written
+    as 0, its status column (0) says so.  Nothing else is altered."""
+    ok, cost, feas, dur, recs, trajs = outputs
+    arrays = {"success": ok, "cost": cost, "cost_defined": np.isfinite(cost), "feasible": feas, "total_duration": dur,
+              "total_duration_defined": np.isfinite(dur), "scenario_records": recs,
+              "winner_piece_off": trajs["piece_off"], "winner_durations": trajs["durations"],
+              "winner_coeffs": trajs["coeffs"], "winner_knots_xy": trajs["knots_xy"]}
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    for k in ("cost", "total_duration", "scenario_records"):
+        arrays[k] = np.where(np.isfinite(arrays[k]), arrays[k], 0.0)
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES and len(a) > 1:
+            # (a row is at least as large as its index: half the budget for the rows, half for their indices)
+            keep = max(1, int(len(a) * DUMP_LIMIT_BYTES * 0.45 / total))
+            rows = np.sort(np.random.default_rng(12345).choice(len(a), size=keep, replace=False))
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     # stdout carries the one JSON line and nothing else: whatever libraries print there meanwhile (RCCL's version banner
     # when the first communicator is created) goes to stderr
@@ -100,8 +135,17 @@ def main():
     ap.add_argument("--hires-size", type=float, default=50.0)
     ap.add_argument("--inflight", type=int, default=None,
                     help="batches (contexts) in flight per GPU (default 3): step i+1 is issued while step i is still solving and its waves "
-                         "take the SIMDs step i's tail leaves idle; 1 = strictly serial steps (also measured and reported beside the line)")
+                         "take the SIMDs step i's tail leaves idle; 1 = strictly serial steps (also measured and reported beside the line "
+                         "with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is reported beside the line: strictly serial steps, planner semantics, the configs[1] "
+                         "latency and the CPU baseline (each can still be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (per-candidate flags, costs and durations, the per-scenario "
+                         "records, the winners' trajectories) as DIR/<name>.npy in float64")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_serial = args.no_planner = args.no_config1 = True
 
     import torch
 
@@ -261,6 +305,7 @@ def main():
                                             return_winners=True)
         winners["last"] = o_.getTrajs(best, n_pieces)
         winners["n"] = len(best)
+        winners["outputs"] = (ok, o_.traj_cost, feas, dur, recs, winners["last"])   # what this step returns to its caller
         tb_ = time.perf_counter()
         if distributed:                  # the one exchange of the path: per-scenario result records over RCCL
             tc = time.perf_counter()
@@ -300,6 +345,8 @@ def main():
     if distributed:
         dist.barrier()
     elapsed = time.perf_counter() - t_start
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, winners["outputs"])
     ok = res[-1][0]
     kernel_ms = [r[1] for r in res]
     # per-candidate figures of the line (evaluation counts, device times, gate verdicts) come from the last TIMED step, read
@@ -422,7 +469,8 @@ def main():
         kms, kdef = serial["kernel_ms"], ("mean HIP-event span of the batch's concurrent launches over the strictly serial steps run after the timed "
                                           "region (serial_steps); the timed region overlaps three batches -- see `sustained`")
     else:
-        kms, kdef = kms_wall, "NO serial steps in this run (--no-serial): wall time of the timed region / steps, i.e. the sustained figure"
+        kms, kdef = kms_wall, ("NO serial steps in this run (they run with --full, unless --no-serial): wall time of the timed region / "
+                               "steps, i.e. the sustained figure")
     achieved = abytes / (kms * 1e-3) / 1e9
     # the same with the measured cost of a partly filled pass instead of a whole pass for every pass (PASS_COST_FIXED)
     tail_ = 13.0 * np_ - 64.0 * (np.ceil(13.0 * np_ / 64.0) - 1.0)

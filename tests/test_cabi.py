@@ -171,14 +171,14 @@ planner_node:
     from conftest import EMU_LIB
     pc, ignored_c = api.params_from_yaml_c(text, lib=api.load(EMU_LIB))
     assert bytes(pc) == bytes(p) and sorted(ignored_c) == sorted(ignored)
-    ref = "/root/reference/src/planner/params/optimizer.yaml"
-    if os.path.exists(ref):      # build container only: the reference's own file gives exactly the built-in defaults
-        q, ign = api.params_from_yaml(ref)
-        assert bytes(q) == bytes(d)
-        qc, ign_c = api.params_from_yaml_c(ref, lib=api.load(EMU_LIB))
-        assert bytes(qc) == bytes(d) and sorted(ign_c) == sorted(ign)
-        assert sorted(ign) == ["first_stage/mean_time_weight", "mean_time_lowb", "mean_time_uppb", "second_stage/alm_data/epsilon_con",
-                               "second_stage/alm_data/max_iter"]
+    # the reference's own parameter file (its settings, tests/golden/optimizer.yaml) gives exactly the built-in defaults
+    ref = os.path.join(ROOT, "tests", "golden", "optimizer.yaml")
+    q, ign = api.params_from_yaml(ref)
+    assert bytes(q) == bytes(d)
+    qc, ign_c = api.params_from_yaml_c(ref, lib=api.load(EMU_LIB))
+    assert bytes(qc) == bytes(d) and sorted(ign_c) == sorted(ign)
+    assert sorted(ign) == ["first_stage/mean_time_weight", "mean_time_lowb", "mean_time_uppb", "second_stage/alm_data/epsilon_con",
+                           "second_stage/alm_data/max_iter"]
 
 
 def test_isa_lint_recognises_the_defect_pattern(tmp_path):

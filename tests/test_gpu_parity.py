@@ -735,7 +735,7 @@ def test_rccl_record_gather_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, TOPAY_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", "29517", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--scenarios", "64",
+           "--master-port", "29517", os.path.join(root, "bench.py"), "--full", "--gpus", "1", "--steps", "3", "--warmup", "1", "--scenarios", "64",
            "--no-cpu-baseline", "--no-config1", "--no-serial"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]

@@ -11,7 +11,7 @@ except Exception as ex:
     print(sys.argv[1], "failed", ex)
 PY
 }
-A="--steps 12 --warmup 3 --no-cpu-baseline --no-config1"
+A="--full --steps 12 --warmup 3 --no-cpu-baseline --no-config1"
 L=$PWD/tools/libs/libtopay_skip.so
 run all env TOPAY_LIB=$L python3 bench.py $A
 run le42 env TOPAY_LIB=$L TOPAY_EXPERIMENT_SKIP_ABOVE=42 python3 bench.py $A

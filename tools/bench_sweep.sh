@@ -1,5 +1,6 @@
 #!/bin/bash
 # usage: tools/bench_sweep.sh "<tag>" "<bench args>" ...   (pairs)  -- runs bench.py with a hard kill timeout and prints value / ms per step
+#   (the serial figure of the digest needs --full among the bench args)
 while [ $# -ge 2 ]; do
   tag=$1; args=$2; shift 2
   s=$(date +%s)

@@ -19,10 +19,13 @@ merged the body of the `if` into it) -- that writes vector registers or memory l
 `s_or_b64 exec, exec, ...`.  `--build` compiles topay_amd/csrc/topay_hip.hip with the product flags first.  Exit status
 1 when anything is found (the build refuses such a library: __graft_entry__.build()).
 """
+import atexit
 import os
 import re
+import shutil
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LANEWISE = re.compile(r"^(v_(?!readlane|readfirstlane|writelane)|ds_|scratch_|global_|flat_|buffer_)")
@@ -71,7 +74,10 @@ def lint(path):
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     if "--build" in sys.argv:
-        out = "/tmp/topay_isa_lint.s"
+        # a directory of this process's own: a fixed name in the shared temporary directory fails for the next user
+        tmp = tempfile.mkdtemp(prefix="topay_isa_lint_")
+        atexit.register(shutil.rmtree, tmp, True)
+        out = os.path.join(tmp, "topay_hip.s")
         src = os.path.join(ROOT, "topay_amd", "csrc", "topay_hip.hip")
         extra = [a[len("--flag="):] for a in sys.argv if a.startswith("--flag=")]
         subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S",

@@ -8,7 +8,7 @@ OUT=$ROOT/gpurun_out/pmc_sq_${1:-r02}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 -L > $OUT/counters.txt 2>&1
-ARGS="--gpus 1 --steps 1 --warmup 1 --no-cpu-baseline --no-config1 --inflight 1 --scenarios 256"
+ARGS="--full --gpus 1 --steps 1 --warmup 1 --no-cpu-baseline --no-config1 --inflight 1 --scenarios 256"
 timeout -s KILL 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_BUSY_CYCLES -d $OUT/p1 -o pmc -- python3 $ROOT/bench.py $ARGS > $OUT/b1.json 2> $OUT/p1.log
 timeout -s KILL 300 rocprofv3 --pmc SQ_IFETCH SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_INSTS_SMEM -d $OUT/p2 -o pmc -- python3 $ROOT/bench.py $ARGS > $OUT/b2.json 2> $OUT/p2.log
 timeout -s KILL 300 rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQ_WAIT_INST_LDS SQ_INST_CYCLES_VMEM_RD SQ_IFETCH_LEVEL -d $OUT/p3 -o pmc -- python3 $ROOT/bench.py $ARGS > $OUT/b3.json 2> $OUT/p3.log
