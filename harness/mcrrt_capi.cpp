@@ -3,6 +3,7 @@
 // on the host would differ from the device (built with contraction off) in the last bit.
 #include "mcrrt.hpp"
 #include "jps.hpp"
+#include "topo_prm.hpp"
 
 using namespace topay_wl;
 
@@ -71,5 +72,79 @@ int wl_plan2d_jps(void* world, const double* start, const double* end, double th
 
 double wl_mcrrt_u01(unsigned long long seed, unsigned long long inst, unsigned long long iter, unsigned long long slot) {
   return mcrrt_u01(seed, inst, iter, slot);
+}
+
+// TopologyPRM::findTopoPaths restated (harness/topo_prm.hpp) on `world` with the two front-end fields given by the caller
+// (wl_edt_front_end_fields).  Returns a handle that keeps every intermediate result; stats[8] as topay_topo_paths,
+// counters[2] = connector moves (topo_prm.cpp:254), collision-point pushes (543-549).
+void* wl_topo_run(void* world, const double* inflate, const double* critical, const double* start_xy, const double* end_xy,
+                  const TopoParams* prm, unsigned long long inst, int use_critical, int track_slack, int* stats, int* counters,
+                  double* min_slack) {
+  const World& w = *(const World*)world;
+  TopologyPRM* t = new TopologyPRM(w.gm, inflate, critical, *prm, inst);
+  t->track_slack = track_slack != 0;
+  const int st = t->findTopoPaths({start_xy[0], start_xy[1], 0.0}, {end_xy[0], end_xy[1], 0.0}, use_critical != 0);
+  for (int i = 0; i < 8; i++) stats[i] = 0;
+  stats[0] = st;
+  if (st >= 0) {
+    stats[1] = t->samples_drawn; stats[2] = t->samples_passed; stats[3] = t->nodes_before; stats[4] = t->nodes_after;
+    stats[5] = t->raw_found; stats[6] = t->n_filtered; stats[7] = (int)t->select_paths.size();
+  }
+  counters[0] = t->n_moves; counters[1] = t->n_pushes;
+  *min_slack = t->min_slack;
+  return t;
+}
+void wl_topo_free(void* h) { delete (TopologyPRM*)h; }
+int wl_topo_graph_size(void* h) { return (int)((TopologyPRM*)h)->graph_.size(); }
+// graph in list order: id, type, position, neighbour ids (WL_TOPO_MAX_NB per node)
+void wl_topo_graph(void* h, int* id, int* type, double* pos_xy, int* n_nb, int* nb) {
+  int k = 0;
+  for (auto& n : ((TopologyPRM*)h)->graph_) {
+    id[k] = n->id_; type[k] = n->type_; pos_xy[2 * k] = n->pos_[0]; pos_xy[2 * k + 1] = n->pos_[1];
+    n_nb[k] = (int)n->neighbors_.size();
+    for (int j = 0; j < n_nb[k] && j < WL_TOPO_MAX_NB; j++) nb[k * WL_TOPO_MAX_NB + j] = n->neighbors_[j]->id_;
+    k++;
+  }
+}
+// which: 0 raw paths kept by searchPaths, 1 their shortcut versions, 2 the selected paths.  lens == NULL: returns the
+// number of paths; else fills lens and, when xy != NULL, the points back to back.
+int wl_topo_get_paths(void* h, int which, int* lens, double* xy) {
+  TopologyPRM* t = (TopologyPRM*)h;
+  const std::vector<TopologyPRM::Path>& ps = which == 0 ? t->raw_paths_ : (which == 1 ? t->short_paths_first_ : t->select_paths);
+  if (!lens) return (int)ps.size();
+  size_t o = 0;
+  for (size_t i = 0; i < ps.size(); i++) {
+    lens[i] = (int)ps[i].size();
+    if (xy) for (auto& p : ps[i]) { xy[o++] = p[0]; xy[o++] = p[1]; }
+  }
+  return (int)ps.size();
+}
+// the cells lineVisib tests for the ray p1 -> p2 (before boundIndex2d): returns their number, writes at most cap
+int wl_topo_ray_cells(void* world, const double* inflate, const double* p1, const double* p2, int cap, int* cells) {
+  const World& w = *(const World*)world;
+  TopoParams prm{};
+  TopologyPRM t(w.gm, inflate, inflate, prm, 0);
+  t.record_cells = true;
+  V3 pc;
+  t.lineVisib({p1[0], p1[1], 0.0}, {p2[0], p2[1], 0.0}, -1.0e300, pc);
+  for (size_t i = 0; i < t.visited_cells.size() && (int)i < cap; i++) { cells[2 * i] = t.visited_cells[i][0]; cells[2 * i + 1] = t.visited_cells[i][1]; }
+  return (int)t.visited_cells.size();
+}
+// samples createGraph draws in `seconds` of accumulated loop time (the reference's max_sample_time rule, for the budget measurement)
+int wl_topo_samples_in(void* world, const double* inflate, const double* critical, const double* start_xy, const double* end_xy,
+                       const TopoParams* prm, unsigned long long inst, double seconds) {
+  const World& w = *(const World*)world;
+  // doubling search on the count: the loop body is deterministic, so the time of the first k samples is measured directly
+  int lo = 64;
+  for (;;) {
+    TopoParams q = *prm;
+    q.max_sample_num = lo;
+    TopologyPRM t(w.gm, inflate, critical, q, inst);
+    const auto t0 = std::chrono::steady_clock::now();
+    try { t.use_critical = false; t.createGraph({start_xy[0], start_xy[1], 0.0}, {end_xy[0], end_xy[1], 0.0}); } catch (const TopoAbort&) { return lo; }
+    const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (dt >= seconds || lo >= (1 << 20)) return (int)((double)lo * std::min(1.0, seconds / dt));
+    lo *= 2;
+  }
 }
 }

@@ -366,3 +366,106 @@ def rs_interpolate(from_pose, to_pose, t, rho=1.0e-2):
     out = np.zeros(3)
     L.wl_rs_interpolate(rho, _dp(a), _dp(b), float(t), _dp(out))
     return out
+
+
+# ---- topological roadmap (TopologyPRM::findTopoPaths) restatement: harness/topo_prm.hpp ---------------------------------
+TOPO_MAX_NB = 32
+
+
+class TopoParams(C.Structure):
+    """== topay_topo_params_t (include/topay.h), == topay_wl::TopoParams (harness/topo_prm.hpp)"""
+    _fields_ = [("sample_inflate_x", C.c_double), ("sample_inflate_y", C.c_double), ("clearance", C.c_double),
+                ("ratio_to_short", C.c_double), ("max_sample_num", C.c_int), ("max_raw_path", C.c_int), ("max_raw_path2", C.c_int),
+                ("reserve_num", C.c_int), ("node_cap", C.c_int), ("reserved", C.c_int), ("seed", C.c_uint64)]
+
+    def __init__(self, **kw):
+        super().__init__(1.5, 4.0, 0.1, 2.0, TOPO_DEFAULT_SAMPLES, 300, 25, 6, 512, 0, 42)
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+TOPO_DEFAULT_SAMPLES = 2368   # == topay_topo_default_params (docs/EXPERIMENTS.md, "Sampling budget of the roadmap")
+
+
+def world_front_end_fields(world, chassis_radius=0.4):
+    """(inflate, critical) of a World, built once with the CPU construction and kept on the object."""
+    f = getattr(world, "_front_end_fields", None)
+    if f is None:
+        f = front_end_fields(world.occ2d, world.occ3d, world.dims, world.res, chassis_radius)
+        world._front_end_fields = f
+    return f
+
+
+def _topo_lib():
+    L = mlib()
+    if not getattr(L, "_topo_ready", False):
+        L.wl_topo_run.restype = C.c_void_p
+        L.wl_topo_run.argtypes = [C.c_void_p, c_dp, c_dp, c_dp, c_dp, C.POINTER(TopoParams), C.c_uint64, C.c_int, C.c_int, c_ip, c_ip, c_dp]
+        L.wl_topo_free.argtypes = [C.c_void_p]
+        L.wl_topo_free.restype = None
+        L.wl_topo_graph_size.argtypes = [C.c_void_p]
+        L.wl_topo_graph.argtypes = [C.c_void_p, c_ip, c_ip, c_dp, c_ip, c_ip]
+        L.wl_topo_graph.restype = None
+        L.wl_topo_get_paths.argtypes = [C.c_void_p, C.c_int, c_ip, c_dp]
+        L.wl_topo_ray_cells.argtypes = [C.c_void_p, c_dp, c_dp, c_dp, C.c_int, c_ip]
+        L.wl_topo_samples_in.argtypes = [C.c_void_p, c_dp, c_dp, c_dp, c_dp, C.POINTER(TopoParams), C.c_uint64, C.c_double]
+        L._topo_ready = True
+    return L
+
+
+def topo_paths(world, start, goal, params=None, inst=0, critical=False, track_slack=True, fields=None):
+    """CPU restatement of TopologyPRM::findTopoPaths on `world` (fields = (inflate, critical) arrays; default: the CPU
+    construction for a 0.4 m chassis).  Returns a dict: status, paths (select_paths: list of [m, 2]), stats (8 ints as
+    topay_topo_paths), graph (id, type, pos, n_nb, nb in list order), raw_paths, short_paths, min_slack, moves, pushes."""
+    L = _topo_lib()
+    prm = params or TopoParams()
+    inf, cr = fields if fields is not None else world_front_end_fields(world)
+    inf = np.ascontiguousarray(inf, dtype=np.float64)
+    cr = np.ascontiguousarray(cr, dtype=np.float64)
+    a = np.ascontiguousarray(np.asarray(start, dtype=np.float64)[:2])
+    b = np.ascontiguousarray(np.asarray(goal, dtype=np.float64)[:2])
+    stats, cnt, slack = np.zeros(8, dtype=np.int32), np.zeros(2, dtype=np.int32), C.c_double(0)
+    h = C.c_void_p(L.wl_topo_run(world.h, _dp(inf), _dp(cr), _dp(a), _dp(b), C.byref(prm), int(inst), int(bool(critical)), int(bool(track_slack)),
+                                 stats.ctypes.data_as(c_ip), cnt.ctypes.data_as(c_ip), C.byref(slack)))
+    try:
+        n = L.wl_topo_graph_size(h)
+        g = dict(id=np.zeros(n, dtype=np.int32), type=np.zeros(n, dtype=np.int32), pos=np.zeros((n, 2)), n_nb=np.zeros(n, dtype=np.int32),
+                 nb=np.zeros((n, TOPO_MAX_NB), dtype=np.int32))
+        L.wl_topo_graph(h, g["id"].ctypes.data_as(c_ip), g["type"].ctypes.data_as(c_ip), _dp(g["pos"]), g["n_nb"].ctypes.data_as(c_ip),
+                        g["nb"].ctypes.data_as(c_ip))
+
+        def paths(which):
+            m = L.wl_topo_get_paths(h, which, None, None)
+            lens = np.zeros(max(m, 1), dtype=np.int32)
+            L.wl_topo_get_paths(h, which, lens.ctypes.data_as(c_ip), None)
+            xy = np.zeros((max(int(lens[:m].sum()), 1), 2))
+            L.wl_topo_get_paths(h, which, lens.ctypes.data_as(c_ip), _dp(xy))
+            o = np.concatenate([[0], np.cumsum(lens[:m])])
+            return [xy[o[i]:o[i + 1]].copy() for i in range(m)]
+
+        ok = stats[0] >= 0
+        return dict(status=int(stats[0]), paths=paths(2), stats=stats, graph=g, raw_paths=paths(0) if ok else [], short_paths=paths(1) if ok else [],
+                    min_slack=slack.value, moves=int(cnt[0]), pushes=int(cnt[1]))
+    finally:
+        L.wl_topo_free(h)
+
+
+def topo_ray_cells(world, p1, p2, cap=4096):
+    """The cells TopologyPRM::lineVisib tests for the ray p1 -> p2, in order (before boundIndex2d clamps them)."""
+    L = _topo_lib()
+    inf = np.ascontiguousarray(world_front_end_fields(world)[0])
+    a = np.ascontiguousarray(p1, dtype=np.float64)
+    b = np.ascontiguousarray(p2, dtype=np.float64)
+    cells = np.zeros((cap, 2), dtype=np.int32)
+    n = L.wl_topo_ray_cells(world.h, _dp(inf), _dp(a), _dp(b), cap, cells.ctypes.data_as(c_ip))
+    return cells[:min(n, cap)].copy()
+
+
+def topo_samples_in(world, start, goal, seconds=0.01, params=None, inst=0):
+    """Samples createGraph draws in `seconds` of loop time on this host, one thread (the reference's max_sample_time rule)."""
+    L = _topo_lib()
+    inf, cr = world_front_end_fields(world)
+    prm = params or TopoParams()
+    a = np.ascontiguousarray(np.asarray(start, dtype=np.float64)[:2])
+    b = np.ascontiguousarray(np.asarray(goal, dtype=np.float64)[:2])
+    return int(L.wl_topo_samples_in(world.h, _dp(np.ascontiguousarray(inf)), _dp(np.ascontiguousarray(cr)), _dp(a), _dp(b), C.byref(prm), int(inst), float(seconds)))

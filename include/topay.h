@@ -338,6 +338,68 @@ topay_status topay_mcrrt_plan(topay_ctx* ctx, int n, const int* map_ids /* n, NU
  * (robo_state.first), state (MCRRTNode::NodeState: 1 EXPANDED, 2 IN_TREE, 3 IN_ANTI_TREE), parent (index, -1 none),
  * cost, q (7 per node).  Up to cap rows; any pointer may be NULL. */
 topay_status topay_mcrrt_nodes(topay_ctx* ctx, int instance, int cap, int* layer, int* state, int* parent, double* cost, double* q);
+/* == TopologyPRM::findTopoPaths (src/planner/src/topo_prm.cpp:60-122 with createGraph 124-212, findVisibGuard 214-233,
+ * needConnection 235-263, getSample 265-276, lineVisib 278-315, pruneGraph 317-344, pruneEquivalent 346-382, selectShortPaths
+ * 384-422, sameTopoPath 424-448, discretizePath 472-506, 599-616, shortcutPath(s) 512-582, discretizeLine 584-597, searchPaths /
+ * depthFirstSearch 656-734; RayCaster::setInput / step, src/planner/src/utils/raycast.cpp:31-48, 253-346; parameters
+ * src/planner/params/topo_prm.yaml): the topological roadmap that gives a planning call its up to reserve_num candidate
+ * chassis paths (planner.cpp:813), for n (start, goal) queries, one wavefront each.  The roadmap reads the two front-end
+ * fields of the query's map slot (getDistCoarse2d / 2i: esdf_buffer_2d_inflate, or esdf_buffer_2d_critical where
+ * critical[p] != 0 -- the planner's second try, planner.cpp:961-963) and, for the push of a collision point, the plain 2-D
+ * field (the critical one when critical): the slot must have been filled by topay_build_esdf* (TOPAY_ERR_NO_MAP after
+ * topay_set_map, which has no front-end fields).
+ *   n_paths[p], path_len, path_xy   select_paths of query p in the reference's order (shortest first): path k has
+ *                             path_len[p * cap_paths + k] points at path_xy + (p * cap_paths + k) * cap_points * 2, first = start,
+ *                             last = goal: the raw path topay_dense_path takes.  Counts beyond cap_points are reported, not
+ *                             written.  cap_paths >= reserve_num.
+ *   stats (n x 8, optional)   status (1 at least one path, 0 none, -1 a pool of the query is full: node_cap nodes,
+ *                             TOPAY_TOPO_MAX_NB neighbours of a node, or the points of a discretised path -- twice the map's
+ *                             diagonal in cells + 512; -2 undefined in the reference: a raw path of 100 nodes or more
+ *                             (path_list(100), line 666), discretizePath without an interval or on an interval of zero length
+ *                             (lines 491-500), a depth-first search past 2 000 000 nodes), samples drawn, samples that passed the
+ *                             clearance test, graph nodes before / after pruneGraph, raw paths the search found, paths after the
+ *                             first pruneEquivalent, selected paths.  With a negative status the other seven are 0.
+ * Device memory: the graphs, raw paths and point buffers of the call stay in the context for topay_topo_graph /
+ * topay_topo_raw_paths until the next call or topay_destroy -- per query node_cap x 156 bytes, max_raw_path x 200 bytes and
+ * (2 max_raw_path2 + 2 reserve_num) point buffers of 16 bytes x the point cap of the largest map of the call: 1.1 MB per
+ * query with the defaults on a 200 x 200 map, i.e. 1.1 GB for 1024 queries.  Split a larger sweep into several calls.  The
+ * point cap of a query (status -1) is that of its own map.
+ * Where the reference is not reproducible the library is deterministic: every draw of rand_pos_(eng_)
+ * (default_random_engine(rd_()), topo_prm.cpp:36-37, 268-269) is a pure function of (seed, first_instance + p, sample index,
+ * axis) -- the generator of topay_mcrrt_plan, mapped to [-1, 1) -- and the 0.01 s of accumulated wall time (max_sample_time) is
+ * part of the count max_sample_num: default 2368 = the median number of samples the CPU restatement draws in 10 ms on one
+ * host core over 64 tables scenarios (2340, docs/EXPERIMENTS.md "Sampling budget of the roadmap"), rounded up to whole
+ * waves of 64; the reference's other bound, 5000, does not bind there.  A ray that has not reached its end cell after
+ * |dx| + |dy| steps (the reference would not terminate) counts as visible.  sample_inflate_z is read by the reference and
+ * never used (z = 0); short_cut_num likewise (parallel_shortcut: true runs one iteration per raw path, selectShortPaths five). */
+#define TOPAY_TOPO_MAX_NB 32   /* neighbours per graph node */
+typedef struct {
+  double sample_inflate_x, sample_inflate_y;  /* topo_prm/sample_inflate_x, _y (1.5, 4.0) */
+  double clearance;                           /* topo_prm/clearance (0.1) */
+  double ratio_to_short;                      /* topo_prm/ratio_to_short (2.0) */
+  int max_sample_num;                         /* samples per query (2368, see above; topo_prm.yaml: 5000 and 0.01 s) */
+  int max_raw_path, max_raw_path2;            /* 300, 25 (at most 4096, 64) */
+  int reserve_num;                            /* 6 (at most 16) */
+  int node_cap;                               /* graph nodes per query (512); status -1 when it needs more */
+  int reserved;
+  unsigned long long seed;
+} topay_topo_params_t;
+void topay_topo_default_params(topay_topo_params_t* p);
+topay_status topay_topo_paths(topay_ctx* ctx, int n, const int* map_ids /* n, NULL = slot 0 */, const double* start_xy /* n x 2 */,
+                              const double* end_xy /* n x 2 */, const int* critical /* n, NULL = all 0 */,
+                              const topay_topo_params_t* params /* NULL = defaults */, unsigned long long first_instance,
+                              int cap_paths, int cap_points, int* n_paths /* n */, int* path_len /* n x cap_paths */,
+                              double* path_xy /* n x cap_paths x cap_points x 2 */, int* stats /* n x 8, optional */);
+/* The graph of query `instance` of the last topay_topo_paths after pruneGraph, in list order (diagnostics, parity tests):
+ * id, type (1 guard, 2 connector), position, number of neighbours and their ids (TOPAY_TOPO_MAX_NB per node).  Up to cap
+ * nodes are written, *n_nodes is their number in the graph; any output pointer may be NULL. */
+topay_status topay_topo_graph(topay_ctx* ctx, int instance, int cap, int* id, int* type, double* pos_xy, int* n_neighbors,
+                              int* neighbors /* cap x TOPAY_TOPO_MAX_NB */, int* n_nodes);
+/* Parity tooling: the <= max_raw_path2 raw paths searchPaths kept for `instance` (which = 0) or their versions after
+ * shortcutPaths (which = 1), laid out as topay_topo_paths lays out one query. */
+topay_status topay_topo_raw_paths(topay_ctx* ctx, int instance, int which, int cap_paths, int cap_points, int* n_paths,
+                                  int* path_len /* cap_paths */, double* path_xy /* cap_paths x cap_points x 2 */);
+
 /* ompl::base::ReedsSheppStateSpace(rho) for n pose pairs (x, y, theta): distance[i] = distance(from_i, to_i), word[i] /
  * lengths[i][5] = the shortest path's segment word (0..17, OMPL's reedsSheppPathType numbering) and signed segment lengths
  * in units of rho, pose[i] = interpolate(from_i, to_i, t[i]) when t is given.  Output pointers may be NULL. */

@@ -69,6 +69,16 @@ class McrrtParams(C.Structure):
                 ("seed", C.c_ulonglong)]
 
 
+class TopoParams(C.Structure):
+    """topay_topo_params_t (include/topay.h): the roadmap's parameters, deterministic caps and seed."""
+    _fields_ = [("sample_inflate_x", C.c_double), ("sample_inflate_y", C.c_double), ("clearance", C.c_double),
+                ("ratio_to_short", C.c_double), ("max_sample_num", C.c_int), ("max_raw_path", C.c_int), ("max_raw_path2", C.c_int),
+                ("reserve_num", C.c_int), ("node_cap", C.c_int), ("reserved", C.c_int), ("seed", C.c_ulonglong)]
+
+
+TOPO_MAX_NB = 32   # TOPAY_TOPO_MAX_NB
+
+
 class Record(C.Structure):
     """topay_record_t: the 32-byte per-scenario record of the multi-GPU exchange."""
     _fields_ = [("scenario_id", C.c_int), ("best_candidate", C.c_int), ("status", C.c_int), ("n_pieces", C.c_int),
@@ -121,6 +131,12 @@ def load(path=None):
     L.topay_mcrrt_plan.argtypes = [C.c_void_p, C.c_int, c_ip, c_ip, c_dp, c_dp, c_dp, C.POINTER(McrrtParams), C.c_ulonglong, C.c_int, c_ip, c_dp,
                                    c_ip, c_dp]
     L.topay_mcrrt_nodes.argtypes = [C.c_void_p, C.c_int, C.c_int, c_ip, c_ip, c_ip, c_dp, c_dp]
+    L.topay_topo_default_params.argtypes = [C.POINTER(TopoParams)]
+    L.topay_topo_default_params.restype = None
+    L.topay_topo_paths.argtypes = [C.c_void_p, C.c_int, c_ip, c_dp, c_dp, c_ip, C.POINTER(TopoParams), C.c_ulonglong, C.c_int, C.c_int, c_ip, c_ip,
+                                   c_dp, c_ip]
+    L.topay_topo_graph.argtypes = [C.c_void_p, C.c_int, C.c_int, c_ip, c_ip, c_dp, c_ip, c_ip, c_ip]
+    L.topay_topo_raw_paths.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_ip, c_ip, c_dp]
     L.topay_reeds_shepp.argtypes = [C.c_void_p, C.c_int, c_dp, c_dp, c_dp, C.c_double, c_dp, c_ip, c_dp, c_dp]
     L.topay_dense_path.argtypes = [C.c_void_p, C.c_int, c_ip, c_dp, C.c_double, c_dp, c_dp, C.c_double, C.c_double, C.c_int, c_ip, c_dp]
     L.topay_connect_check_num.argtypes = [C.c_int, c_dp, c_dp, c_dp, C.c_double, c_ip]
@@ -587,6 +603,73 @@ class MomaTrajOptBatch:
         _chk(self.L, self.L.topay_plan2d_jps(self.h, n, None if mid is None else _ip(mid), _dp(a), _dp(b), float(threshold), int(cap), _ip(ln), _dp(out),
                                              _ip(st)))
         return [out[p, :min(ln[p], cap)].copy() for p in range(n)], st, ln
+
+    def topo_params(self, **kw):
+        p = TopoParams()
+        self.L.topay_topo_default_params(C.byref(p))
+        for k, v in kw.items():
+            setattr(p, k, v)
+        return p
+
+    def topo_paths(self, start_xy, end_xy, prm=None, map_ids=None, critical=None, first_instance=0, cap_paths=None, cap_points=256):
+        """TopologyPRM::findTopoPaths for a batch of (start, goal) pairs on maps built with build_esdf* -> (list per query of
+        lists of [m, 2] paths, shortest first; stats [n, 8]: status, samples, samples past the clearance test, nodes before /
+        after pruning, raw paths, paths after the first prune, selected paths)."""
+        a = np.ascontiguousarray(start_xy, dtype=np.float64).reshape(-1, 2)
+        b = np.ascontiguousarray(end_xy, dtype=np.float64).reshape(-1, 2)
+        n = len(a)
+        prm = prm if prm is not None else self.topo_params()
+        cap_paths = int(cap_paths or prm.reserve_num)
+        mid = None if map_ids is None else np.ascontiguousarray(map_ids, dtype=np.int32)
+        cr = None if critical is None else np.ascontiguousarray(np.broadcast_to(np.asarray(critical), (n,)), dtype=np.int32)
+        while True:
+            npth, ln = np.zeros(n, dtype=np.int32), np.zeros((n, cap_paths), dtype=np.int32)
+            out, st = np.zeros((n, cap_paths, cap_points, 2)), np.zeros((n, 8), dtype=np.int32)
+            _chk(self.L, self.L.topay_topo_paths(self.h, n, _ip(mid), _dp(a), _dp(b), _ip(cr), C.byref(prm), int(first_instance), cap_paths,
+                                                 int(cap_points), _ip(npth), _ip(ln), _dp(out), _ip(st)))
+            if n == 0 or ln.max() <= cap_points:
+                break
+            cap_points = int(ln.max())   # (a path longer than the buffer: its length was reported, ask again with room for it)
+        return [[out[p, k, :ln[p, k]].copy() for k in range(npth[p])] for p in range(n)], st
+
+    def topo_graph(self, k, cap=None):
+        """Graph of query k of the last topo_paths after pruneGraph, in list order: dict of id, type, pos, n_nb, nb."""
+        cap = int(cap or 65535)
+        n = C.c_int(0)
+        _chk(self.L, self.L.topay_topo_graph(self.h, int(k), 0, None, None, None, None, None, C.byref(n)))
+        m = min(n.value, cap)
+        g = dict(id=np.zeros(m, dtype=np.int32), type=np.zeros(m, dtype=np.int32), pos=np.zeros((m, 2)), n_nb=np.zeros(m, dtype=np.int32),
+                 nb=np.zeros((m, TOPO_MAX_NB), dtype=np.int32))
+        _chk(self.L, self.L.topay_topo_graph(self.h, int(k), m, _ip(g["id"]), _ip(g["type"]), _dp(g["pos"]), _ip(g["n_nb"]), _ip(g["nb"]), C.byref(n)))
+        return g
+
+    def topo_raw_paths(self, k, which=0, cap_paths=64, cap_points=None):
+        """The raw paths searchPaths kept for query k of the last topo_paths (which = 0) or their shortcut versions (1)."""
+        cap_points = int(cap_points or (100 if which == 0 else 1024))
+        while True:
+            n, ln, out = C.c_int(0), np.zeros(cap_paths, dtype=np.int32), np.zeros((cap_paths, cap_points, 2))
+            _chk(self.L, self.L.topay_topo_raw_paths(self.h, int(k), int(which), cap_paths, cap_points, C.byref(n), _ip(ln), _dp(out)))
+            if ln.max() <= cap_points:
+                break
+            cap_points = int(ln.max())
+        return [out[i, :ln[i]].copy() for i in range(min(n.value, cap_paths))]
+
+    def candidate_paths(self, start_xy, end_xy, map_ids=None, critical=False, prm=None, first_instance=0):
+        """The candidates of a planning call (planner.cpp:813-829): the roadmap's paths, plus -- when not critical and not empty --
+        the plan2d_jps path (threshold chassis_colli_radius + 0.1); at most 8 per query (ValueError above: the reference throws
+        "Too many paths to optimize").  Returns a list per query of [m, 2] raw paths, the layout dense_path takes."""
+        a = np.ascontiguousarray(start_xy, dtype=np.float64).reshape(-1, 2)
+        b = np.ascontiguousarray(end_xy, dtype=np.float64).reshape(-1, 2)
+        paths, _ = self.topo_paths(a, b, prm, map_ids=map_ids, critical=1 if critical else None, first_instance=first_instance)
+        if not critical:
+            jps, _, _ = self.plan2d_jps(a, b, float(self.opt_param.chassis_colli_radius) + 0.1, map_ids=map_ids)
+            for p in range(len(a)):
+                if len(jps[p]):
+                    paths[p].append(jps[p])
+        for p in range(len(a)):
+            if len(paths[p]) > 8:
+                raise ValueError(f"query {p}: {len(paths[p])} candidate paths (at most 8: too many paths to optimize)")
+        return paths
 
     def mcrrt_params(self, **kw):
         p = McrrtParams()

@@ -23,6 +23,7 @@
 #include "topay_front.h"
 #include "topay_mcrrt.h"
 #include "topay_jps.h"
+#include "topay_topo.h"
 #include "topay_yaml.h"
 
 #include "topay_kernels.h"
@@ -264,6 +265,9 @@ struct topay_ctx {
   DevBuf qnext;
   DevBuf mc_i, mc_d, mc_k, mc_rs, mc_in;   // node tables, Reeds-Shepp words and inputs of the last topay_mcrrt_plan
   int mc_n = 0, mc_node_cap = 0;
+  DevBuf tp_i, tp_d, tp_raw, tp_pts, tp_io;   // graphs, raw paths and point buffers of the last topay_topo_paths (topay_topo_graph / _raw_paths)
+  int tp_n = 0, tp_pt_cap = 0, tp_nbuf = 0;
+  topay_topo_params_t tp_P;
   DevBuf paths, path_off, path_len, bvel, bacc, scratch;
   DevBuf N, s1_past, map_id, head, tail, start_xy, goal_xy, init_xy, x0;
   DevBuf x, work, hist_s, hist_y, hist_ys, hist_alpha, lu;
@@ -586,7 +590,7 @@ void topay_destroy(topay_ctx* c) {
                     &c->map_id, &c->head, &c->tail, &c->start_xy, &c->goal_xy, &c->init_xy, &c->x0, &c->x, &c->work,
                     &c->hist_s, &c->hist_y, &c->hist_ys, &c->hist_alpha, &c->lu, &c->poff, &c->noff, &c->group_id, &c->group_tau, &c->interrupted, &c->success, &c->cost, &c->stats,
                     &c->xyerr, &c->coef, &c->T, &c->knots, &c->alm, &c->fout, &c->order, &c->trace, &c->elapsed, &c->startus, &c->hwid, &c->sbuf, &c->mstash, &c->feas_cseq, &c->feas_tk, &c->feas_report, &c->feas_flags, &c->edt_occ, &c->edt_tmp1,
-                    &c->edt_tmp2, &c->edt_v, &c->edt_z, &c->edt_out2, &c->edt_out3, &c->pb_io, &c->qnext, &c->mc_i, &c->mc_d, &c->mc_k, &c->mc_rs, &c->mc_in};
+                    &c->edt_tmp2, &c->edt_v, &c->edt_z, &c->edt_out2, &c->edt_out3, &c->pb_io, &c->qnext, &c->mc_i, &c->mc_d, &c->mc_k, &c->mc_rs, &c->mc_in, &c->tp_i, &c->tp_d, &c->tp_raw, &c->tp_pts, &c->tp_io};
   for (DevBuf* b : bufs) b->release();
   for (int i = 0; i < TOPAY_MAX_MAPS; i++) { c->map2d[i].release(); c->map3d[i].release(); c->map2d_inf[i].release(); c->map2d_crit[i].release(); }
   for (auto& a : c->map_arenas) a.buf.release();
@@ -1857,6 +1861,213 @@ topay_status topay_plan2d_jps(topay_ctx* c, int n, const int* map_ids, const dou
   HIPCHK(hipStreamSynchronize(c->stream));
   ws.release();
   io.release();
+  return TOPAY_OK;
+}
+
+void topay_topo_default_params(topay_topo_params_t* p) {
+  if (!p) return;
+  p->sample_inflate_x = 1.5;     // planner/params/topo_prm.yaml
+  p->sample_inflate_y = 4.0;
+  p->clearance = 0.1;
+  p->ratio_to_short = 2.0;
+  p->max_sample_num = 2368;      // the reference's 0.01 s of sampling as a count (include/topay.h; docs/EXPERIMENTS.md)
+  p->max_raw_path = 300;
+  p->max_raw_path2 = 25;
+  p->reserve_num = 6;
+  p->node_cap = 512;
+  p->reserved = 0;
+  p->seed = 42;
+}
+
+// Points a discretised / shortened path may have: one point per cell along twice the map's diagonal, and 512 for the
+// extra point of every segment.  (A raw path zigzags inside the sampling region, whose length is at most the diagonal
+// + 2 sample_inflate_x; a path that needs more gives status -1.)  The cap of a query is that of its own map (the kernel
+// forms it again from the map's dimensions); the buffers of a call are strided by the largest.  harness/topo_prm.hpp: topo_pt_cap.
+static int topo_pt_cap(int nx, int ny) { return 2 * (int)std::ceil(std::sqrt((double)nx * nx + (double)ny * ny)) + 512; }
+
+// Layout of the integer scratch of a topay_topo_paths call (topay_ctx::tp_i), in ints from its start: per node type,
+// neighbour count, guard list, neighbour ids; per query raw-path lengths, kept raw paths, point-buffer lengths, meta.
+struct TopoLayout {
+  size_t type, nnb, guards, nb, raw_len, keep, pts_len, meta, total;
+  TopoLayout(size_t N, const topay_topo_params_t& P, int nbuf) {
+    const size_t nn = N * (size_t)P.node_cap;
+    type = 0; nnb = nn; guards = 2 * nn; nb = 3 * nn;
+    raw_len = nb + nn * TOPAY_TOPO_MAX_NB;
+    keep = raw_len + N * (size_t)P.max_raw_path;
+    pts_len = keep + N * (size_t)P.max_raw_path2;
+    meta = pts_len + N * (size_t)nbuf;
+    total = meta + N * 8;
+  }
+};
+
+topay_status topay_topo_paths(topay_ctx* c, int n, const int* map_ids, const double* start_xy, const double* end_xy, const int* critical,
+                              const topay_topo_params_t* prm, unsigned long long first_instance, int cap_paths, int cap_points, int* n_paths,
+                              int* path_len, double* path_xy, int* stats) {
+  if (!c || n <= 0 || !start_xy || !end_xy || !n_paths || !path_len || !path_xy || cap_points < 2) return TOPAY_ERR_INVALID_ARG;
+  topay_topo_params_t P;
+  if (prm) P = *prm;
+  else topay_topo_default_params(&P);
+  if (P.max_sample_num < 0 || P.max_raw_path < 1 || P.max_raw_path > 4096 || P.max_raw_path2 < 1 || P.max_raw_path2 > 64 || P.reserve_num < 1 ||
+      P.reserve_num > 16 || P.node_cap < 2 || P.node_cap > 65535 || !(P.sample_inflate_x >= 0.0) || !(P.sample_inflate_y >= 0.0)) {
+    set_err("topay_topo_paths: parameters out of range (max_raw_path 1..4096, max_raw_path2 1..64, reserve_num 1..16, node_cap 2..65535)");
+    return TOPAY_ERR_INVALID_ARG;
+  }
+  if (cap_paths < P.reserve_num) { set_err("topay_topo_paths: cap_paths is smaller than reserve_num"); return TOPAY_ERR_INVALID_ARG; }
+  std::vector<int> mid((size_t)n, 0);
+  int pt_cap = 0;
+  for (int p = 0; p < n; p++) {
+    mid[p] = map_ids ? map_ids[p] : 0;
+    if (mid[p] < 0 || mid[p] >= TOPAY_MAX_MAPS) return TOPAY_ERR_INVALID_ARG;
+    if (!c->have_map[mid[p]]) { set_err("map slot not set"); return TOPAY_ERR_NO_MAP; }
+    const DevMap& m = c->hmaps[mid[p]];
+    if (!m.esdf2d_inflate || !m.esdf2d_critical) {
+      set_err("topay_topo_paths: map slot " + std::to_string(mid[p]) + " has no front-end fields (esdf_buffer_2d_inflate / _critical): fill it with "
+              "topay_build_esdf_fields (or topay_build_esdf / _batch), not topay_set_map");
+      return TOPAY_ERR_NO_MAP;
+    }
+    pt_cap = std::max(pt_cap, topo_pt_cap(m.dims[0], m.dims[1]));
+  }
+  HIPCHK(hipSetDevice(c->device));
+  const size_t N = (size_t)n, nn = N * P.node_cap;
+  const int nbuf = 2 * P.max_raw_path2 + 2 * P.reserve_num;
+  topay_status s;
+  const TopoLayout lay(N, P, nbuf);
+  if ((s = c->tp_i.ensure(lay.total * 4)) != TOPAY_OK || (s = c->tp_d.ensure(nn * 2 * 8)) != TOPAY_OK ||
+      (s = c->tp_raw.ensure(N * P.max_raw_path * TOPAY_TOPO_RAWLEN * 2)) != TOPAY_OK ||
+      (s = c->tp_pts.ensure(N * (size_t)nbuf * (size_t)pt_cap * 16)) != TOPAY_OK)
+    return s;
+  const size_t io_d = N * 4 + N * (size_t)cap_paths * cap_points * 2, io_i = N * (3 + (size_t)cap_paths + 8);
+  if ((s = c->tp_io.ensure(io_d * 8 + io_i * 4)) != TOPAY_OK) return s;
+  double* d_start = c->tp_io.as<double>();
+  double* d_end = d_start + 2 * N;
+  double* d_out = d_end + 2 * N;
+  int* d_mid = (int*)(d_out + N * (size_t)cap_paths * cap_points * 2);
+  int* d_crit = d_mid + N;
+  int* d_np = d_crit + N;
+  int* d_len = d_np + N;
+  int* d_stats = d_len + N * cap_paths;
+  HIPCHK(hipMemcpyAsync(d_start, start_xy, N * 16, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(d_end, end_xy, N * 16, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(d_mid, mid.data(), N * 4, hipMemcpyHostToDevice, c->stream));
+  if (critical) HIPCHK(hipMemcpyAsync(d_crit, critical, N * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemsetAsync(d_out, 0, N * (size_t)cap_paths * cap_points * 16, c->stream));
+  topay::TopoBatch B;
+  B.n = n; B.cap_paths = cap_paths; B.cap_points = cap_points; B.pt_cap = pt_cap; B.nbuf = nbuf; B.inst_base = first_instance;
+  B.map_id = d_mid; B.start = d_start; B.end = d_end; B.critical = critical ? d_crit : nullptr;
+  B.P.sample_inflate_x = P.sample_inflate_x; B.P.sample_inflate_y = P.sample_inflate_y; B.P.clearance = P.clearance;
+  B.P.ratio_to_short = P.ratio_to_short; B.P.max_sample_num = P.max_sample_num; B.P.max_raw_path = P.max_raw_path;
+  B.P.max_raw_path2 = P.max_raw_path2; B.P.reserve_num = P.reserve_num; B.P.node_cap = P.node_cap; B.P.reserved = 0; B.P.seed = P.seed;
+  int* ti = c->tp_i.as<int>();
+  B.nd_type = ti + lay.type; B.nd_nnb = ti + lay.nnb; B.guards = ti + lay.guards; B.nd_nb = ti + lay.nb;
+  B.raw_len = ti + lay.raw_len; B.keep = ti + lay.keep; B.pts_len = ti + lay.pts_len; B.meta = ti + lay.meta;
+  B.nd_pos = c->tp_d.as<double>();
+  B.raw = c->tp_raw.as<unsigned short>();
+  B.pts = c->tp_pts.as<double>();
+  B.n_paths = d_np; B.path_len = d_len; B.path_xy = d_out; B.stats = d_stats;
+  c->tp_n = 0;
+  HIPCHK(hipEventRecord(c->ev0, c->stream));
+  hipLaunchKernelGGL(topay::k_topo, dim3((unsigned)n), dim3(64), 0, c->stream, (const DevMap*)c->dmaps.p, B);   // one wave per query
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->ev1, c->stream));
+  HIPCHK(hipMemcpyAsync(n_paths, d_np, N * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(path_len, d_len, N * cap_paths * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(path_xy, d_out, N * (size_t)cap_paths * cap_points * 16, hipMemcpyDeviceToHost, c->stream));
+  if (stats) HIPCHK(hipMemcpyAsync(stats, d_stats, N * 32, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+  c->last_ms = ms;
+  c->last_launches = 1;
+  c->tp_n = n; c->tp_pt_cap = pt_cap; c->tp_nbuf = nbuf; c->tp_P = P;
+  return TOPAY_OK;
+}
+
+topay_status topay_topo_graph(topay_ctx* c, int instance, int cap, int* id, int* type, double* pos_xy, int* n_neighbors, int* neighbors,
+                              int* n_nodes) {
+  if (!c || instance < 0 || instance >= c->tp_n || cap < 0) return TOPAY_ERR_INVALID_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  const topay_topo_params_t& P = c->tp_P;
+  const size_t N = (size_t)c->tp_n, o = (size_t)instance * P.node_cap;
+  const TopoLayout lay(N, P, c->tp_nbuf);
+  const int* ti = c->tp_i.as<int>();
+  const int* d_meta = ti + lay.meta + 8 * (size_t)instance;
+  int meta[8];
+  HIPCHK(memcpy_sync(c, meta, d_meta, sizeof(meta), hipMemcpyDeviceToHost));
+  const int created = std::min(std::max(meta[0], 0), P.node_cap);
+  std::vector<int> t((size_t)created), k((size_t)created), nb((size_t)created * TOPAY_TOPO_MAX_NB);
+  std::vector<double> pos((size_t)created * 2);
+  if (created > 0) {
+    HIPCHK(memcpy_sync(c, t.data(), ti + lay.type + o, (size_t)created * 4, hipMemcpyDeviceToHost));
+    HIPCHK(memcpy_sync(c, k.data(), ti + lay.nnb + o, (size_t)created * 4, hipMemcpyDeviceToHost));
+    HIPCHK(memcpy_sync(c, nb.data(), ti + lay.nb + o * TOPAY_TOPO_MAX_NB, (size_t)created * TOPAY_TOPO_MAX_NB * 4, hipMemcpyDeviceToHost));
+    HIPCHK(memcpy_sync(c, pos.data(), c->tp_d.as<double>() + 2 * o, (size_t)created * 16, hipMemcpyDeviceToHost));
+  }
+  int m = 0;
+  for (int i = 0; i < created; i++) {
+    if (t[i] == 0) continue;   // erased by pruneGraph
+    if (m < cap) {
+      if (id) id[m] = i;
+      if (type) type[m] = t[i];
+      if (pos_xy) { pos_xy[2 * m] = pos[2 * (size_t)i]; pos_xy[2 * m + 1] = pos[2 * (size_t)i + 1]; }
+      if (n_neighbors) n_neighbors[m] = k[i];
+      if (neighbors)
+        for (int j = 0; j < TOPAY_TOPO_MAX_NB; j++) neighbors[(size_t)m * TOPAY_TOPO_MAX_NB + j] = j < k[i] ? nb[(size_t)i * TOPAY_TOPO_MAX_NB + j] : 0;
+    }
+    m++;
+  }
+  if (n_nodes) *n_nodes = m;
+  return TOPAY_OK;
+}
+
+topay_status topay_topo_raw_paths(topay_ctx* c, int instance, int which, int cap_paths, int cap_points, int* n_paths, int* path_len,
+                                  double* path_xy) {
+  if (!c || instance < 0 || instance >= c->tp_n || which < 0 || which > 1 || cap_paths < 0 || cap_points < 0 || !n_paths || !path_len || !path_xy)
+    return TOPAY_ERR_INVALID_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  const topay_topo_params_t& P = c->tp_P;
+  const size_t N = (size_t)c->tp_n, q = (size_t)instance;
+  const TopoLayout lay(N, P, c->tp_nbuf);
+  const int* ti = c->tp_i.as<int>();
+  const int* d_rawlen = ti + lay.raw_len;
+  const int* d_keep = ti + lay.keep;
+  const int* d_ptslen = ti + lay.pts_len;
+  const int* d_meta = ti + lay.meta;
+  int meta[8];
+  HIPCHK(memcpy_sync(c, meta, d_meta + 8 * q, sizeof(meta), hipMemcpyDeviceToHost));
+  const int n_keep = meta[3] == 0 ? std::min(std::max(meta[1], 0), P.max_raw_path2) : 0;
+  *n_paths = n_keep;
+  if (n_keep == 0) return TOPAY_OK;
+  std::vector<int> keep((size_t)n_keep);
+  HIPCHK(memcpy_sync(c, keep.data(), d_keep + q * P.max_raw_path2, (size_t)n_keep * 4, hipMemcpyDeviceToHost));
+  if (which == 0) {
+    const int created = std::min(std::max(meta[0], 0), P.node_cap);
+    std::vector<double> pos((size_t)created * 2);
+    HIPCHK(memcpy_sync(c, pos.data(), c->tp_d.as<double>() + 2 * q * P.node_cap, (size_t)created * 16, hipMemcpyDeviceToHost));
+    std::vector<int> rl((size_t)P.max_raw_path);
+    HIPCHK(memcpy_sync(c, rl.data(), d_rawlen + q * P.max_raw_path, rl.size() * 4, hipMemcpyDeviceToHost));
+    std::vector<unsigned short> ids(TOPAY_TOPO_RAWLEN);
+    for (int k = 0; k < n_keep && k < cap_paths; k++) {
+      const int r = keep[k], len = std::min(std::max(rl[r], 0), TOPAY_TOPO_RAWLEN);
+      HIPCHK(memcpy_sync(c, ids.data(), c->tp_raw.as<unsigned short>() + (q * P.max_raw_path + r) * TOPAY_TOPO_RAWLEN, (size_t)len * 2, hipMemcpyDeviceToHost));
+      path_len[k] = len;
+      for (int j = 0; j < len && j < cap_points; j++) {
+        const int nd = std::min((int)ids[j], created - 1);
+        path_xy[((size_t)k * cap_points + j) * 2] = pos[2 * (size_t)nd];
+        path_xy[((size_t)k * cap_points + j) * 2 + 1] = pos[2 * (size_t)nd + 1];
+      }
+    }
+  } else {
+    std::vector<int> pl((size_t)n_keep);
+    HIPCHK(memcpy_sync(c, pl.data(), d_ptslen + q * c->tp_nbuf, (size_t)n_keep * 4, hipMemcpyDeviceToHost));
+    for (int k = 0; k < n_keep && k < cap_paths; k++) {
+      const int len = std::min(std::max(pl[k], 0), c->tp_pt_cap);
+      path_len[k] = len;
+      const int w = std::min(len, cap_points);
+      if (w > 0)
+        HIPCHK(memcpy_sync(c, path_xy + (size_t)k * cap_points * 2, c->tp_pts.as<double>() + (q * c->tp_nbuf + k) * (size_t)c->tp_pt_cap * 2, (size_t)w * 16,
+                           hipMemcpyDeviceToHost));
+    }
+  }
   return TOPAY_OK;
 }
 
