@@ -42,23 +42,8 @@ static void set_err(const std::string& s) { g_err = s; }
     }                                                                                            \
   } while (0)
 
-// Tuning switches read from the environment exist only in builds with -DTOPAY_EXPERIMENTS (tools/ab_lib.sh); the product
-// library reads TOPAY_PERSISTENT / TOPAY_STEAL (launch scheme, used by the profiling scripts and the parity tests),
-// TOPAY_RCCL_LIB, and sets GPU_MAX_HW_QUEUES when it is loaded.
-#ifdef TOPAY_EXPERIMENTS
-static const char* exp_env(const char* name) { return getenv(name); }
-#else
-static const char* exp_env(const char*) { return nullptr; }
-// A tuning switch in the environment of the product library would be silently ignored (an A/B script then measures the
-// same build twice): say so, once per process, when the library is loaded.
-__attribute__((constructor)) static void topay_warn_ignored_switches() {
-  static const char* names[] = {"TOPAY_DISPATCH_GATE", "TOPAY_EDT_ENVELOPE", "TOPAY_FORCE_CLASS", "TOPAY_GATE_IN_SOLVE", "TOPAY_LDS_PAD",
-                                "TOPAY_OCC2_GAIN", "TOPAY_OVERSUBSCRIBE", "TOPAY_POISON", "TOPAY_RESERVE_SLOTS", "TOPAY_SHARE_BIAS0",
-                                "TOPAY_MW_C4", "TOPAY_MW_C5"};
-  for (const char* n : names)
-    if (getenv(n)) fprintf(stderr, "libtopay_hip: %s is set but ignored -- tuning switches exist only in -DTOPAY_EXPERIMENTS builds (tools/ab_lib.sh)\n", n);
-}
-#endif
+// From the environment the library reads TOPAY_PERSISTENT / TOPAY_STEAL (launch scheme, used by the profiling scripts and
+// the parity tests) and TOPAY_RCCL_LIB, and it sets GPU_MAX_HW_QUEUES when it is loaded; nothing else.
 
 struct DevBuf {
   void* p = nullptr;
@@ -77,13 +62,6 @@ struct DevBuf {
       }
     }
     bytes = n;
-    // debugging aid (TOPAY_POISON=<byte>): fill every fresh allocation, so that a read of memory nobody has written
-    // shows up on every run instead of only when the allocator hands out dirty pages
-    static const int poison = [] { const char* e = exp_env("TOPAY_POISON"); return e ? atoi(e) : -1; }();
-    if (poison >= 0) {
-      HIPCHK(hipMemset(p, poison, n));
-      HIPCHK(hipDeviceSynchronize());
-    }
     return TOPAY_OK;
   }
   void release() {
@@ -118,8 +96,7 @@ static const int kBucketMaxN[TOPAY_NBUCKET] = {10, 15, 21, 32, 42, 64, TOPAY_MAX
 static const int kBigFirst = 4;   // the classes of long candidates (N > 32) start here
 
 // Kernel of a launch class: rows per thread and waves per trajectory select the template; the LDS is sized by the
-// longest candidate actually in the class.  The classes of long candidates have a one-wave and a several-waves variant
-// (TOPAY_MW_C4 / TOPAY_MW_C5 = waves per trajectory for N <= 42 / N <= 64; N <= 170 always evaluates on four waves).
+// longest candidate actually in the class.
 typedef void (*solve_kernel_t)(DevBatch, const DevMap*, int);
 typedef void (*eval_kernel_t)(DevBatch, const DevMap*, int, int, int);
 struct ClassDef {
@@ -128,66 +105,31 @@ struct ClassDef {
   eval_kernel_t eval;
   int occ = 2;   // waves per SIMD the kernel is built for (512 / occ registers per lane; every kernel: 256, no AGPRs)
   solve_kernel_t lat = nullptr;   // helper-wave kernel of a one-wave class (topay_set_latency_mode): 4 waves per workgroup
-  // The waves the SOLVER's vectors are divided over and its rows per lane (elements per thread / 2): what the bits of a solve
-  // depend on (topay_class_of).  0 = as the evaluation.  The long classes run a one-wave solver on wave 0 of a four-wave
-  // workgroup whose other waves join the evaluations only (helper waves, topay_solve.h): solver_nw 1, helpers true.
-  int solver_nw = 0, solver_rmax = 0;
-  bool helpers = false;           // `solve` is a helper-wave kernel: its LDS carries the command block
-  int snw() const { return solver_nw ? solver_nw : nw; }
+  // The solver runs on ONE wave in every class; its rows per lane (elements per lane / 2) are what the bits of a solve depend on
+  // (topay_class_of).  0 = as the evaluation.  The long classes run it on wave 0 of a four-wave workgroup whose other waves
+  // join the evaluations only (helper waves, topay_solve.h).
+  int solver_rmax = 0;
   int srmax() const { return solver_rmax ? solver_rmax : rmax; }
+  bool helpers() const { return nw > 1; }   // `solve` is a helper-wave kernel: its LDS carries the command block
 };
 static const int kLatWaves = 4;
-static const ClassDef* class_table() {
-  static const ClassDef* tab = [] {
-    static ClassDef t[TOPAY_NBUCKET] = {
-        {10, 1, 1, k_solve1, k_eval1, 2, k_lat1}, {15, 2, 1, k_solve2, k_eval2, 2, k_lat2}, {21, 2, 1, k_solve2, k_eval2, 2, k_lat2},
-        {32, 3, 1, k_solve3, k_eval3, 2, k_lat3},
-        {42, 2, 4, k_long5, k_eval2w4, 2, nullptr, 1, 5, true}, {64, 2, 4, k_long5, k_eval2w4, 2, nullptr, 1, 5, true},
-        {TOPAY_MAX_N, 4, 4, k_long14, k_eval4w4, 2, nullptr, 1, 14, true}};
-    // Four waves per trajectory for N = 33..64 since round 4.  Round 3 (one wave per SIMD), one / two / four waves for both
-    // classes: 9.8-10.1k / 10.1k / 9.1k trajectories/s, strictly serial steps 1.15 / 1.00 / 1.03 s -- four waves halve a long
-    // candidate's solve but held four SIMDs for it.  With two waves per SIMD a wave holds half a SIMD, the common classes
-    // got faster and the long candidates set the length of a batch again (their launch was the longest of a serial step,
-    // 1.06-1.21 s): two / four waves for N = 43..64 now give 11.5-11.6k / 11.8-11.9k and serial steps of 1.07 / 0.95 s, four
-    // for N = 33..42 as well 0.94 s (tools/experiments/r4_mw.sh).
-    // Round 5: the SOLVER of the long classes runs on one wave (k_long5 / k_long14: 10 / 28 vector elements per lane) and only
-    // the evaluations use the four waves -- every reduction of the four-wave solver (two per history pair of the two-loop
-    // recursion) was a workgroup reduction through LDS and a barrier (k_solve2w4: VALU active 18.7 % of its wave cycles).
-#ifdef TOPAY_EXPERIMENTS
-    auto env_nw = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
-    const int w4 = env_nw("TOPAY_MW_C4", 4), w5 = env_nw("TOPAY_MW_C5", 4);
-    if (w4 == 1) t[4] = {42, 4, 1, k_solve4, k_eval4, 2};
-    else if (w4 == 2) t[4] = {42, 2, 2, k_solve2w2, k_eval2w2, 2};
-    if (w5 == 1) t[5] = {64, 6, 1, k_solve6, k_eval6, 2};
-    else if (w5 == 2) t[5] = {64, 3, 2, k_solve3w2, k_eval3w2, 2};
-    // TOPAY_LONG_SOLVER=4: the four-wave solver of round 4 for the long classes (A/B)
-    if (const char* e = getenv("TOPAY_LONG_SOLVER")) {
-      if (atoi(e) == 4) {
-        if (w4 == 4) t[4] = {42, 2, 4, k_solve2w4, k_eval2w4, 2};
-        if (w5 == 4) t[5] = {64, 2, 4, k_solve2w4, k_eval2w4, 2};
-        t[6] = {128, 3, 4, k_solve3w4, k_eval3w4, 2};   // (the four-wave solver holds 128 pieces: longer candidates are not launched in this A/B mode)
-      }
-    }
-#endif
-    return t;
-  }();
-  return tab;
-}
+// N <= 32: one wave per trajectory.  N = 33..170: the evaluations on four waves (round 4: the long candidates set the length
+// of a batch), the solver on wave 0 alone with 10 / 28 vector elements per lane (round 5: every reduction of a four-wave
+// solver was a workgroup reduction through LDS and a barrier).  Figures: docs/EXPERIMENTS.md.
+static const ClassDef kClassTable[TOPAY_NBUCKET] = {
+    {10, 1, 1, k_solve1, k_eval1, 2, k_lat1}, {15, 2, 1, k_solve2, k_eval2, 2, k_lat2}, {21, 2, 1, k_solve2, k_eval2, 2, k_lat2},
+    {32, 3, 1, k_solve3, k_eval3, 2, k_lat3},
+    {42, 2, 4, k_long5, k_eval2w4, 2, nullptr, 5}, {64, 2, 4, k_long5, k_eval2w4, 2, nullptr, 5},
+    {TOPAY_MAX_N, 4, 4, k_long14, k_eval4w4, 2, nullptr, 14}};
+static const ClassDef* class_table() { return kClassTable; }
+// work per SIMD-second of the two-waves-per-SIMD classes relative to one wave per SIMD (sizes the launches only; assumed
+// 1.0 / 1.2 / 1.4 / 1.7 / 2.0 gave 10.0k / 10.2k / 10.5k / 10.8k / 10.6k trajectories/s, docs/EXPERIMENTS.md)
+static const double kOcc2Gain = 1.7;
 static const int kLdsDoublesPerCU = 160 * 1024 / 8;
 static size_t class_lds_bytes(const ClassDef& cd, int nm) {
-  int d = lds_doubles_mw(nm, cd.nw);
-  // experiments build: TOPAY_LDS_PAD="<max_n of a class>:<doubles>[,...]" asks for more LDS than the class needs (what a
-  // workgroup less per compute unit costs)
-  if (const char* e = exp_env("TOPAY_LDS_PAD")) {
-    for (const char* q = e; q && *q;) {
-      int mn = 0, add = 0;
-      if (sscanf(q, "%d:%d", &mn, &add) == 2 && mn == cd.max_n) d += add;
-      q = strchr(q, ',');
-      if (q) q++;
-    }
-  }
+  const int d = lds_doubles_mw(nm, cd.nw);
   // + past-cost ring [8] + the solver state parked across an evaluation [40] (+ the command block of a helper-wave kernel)
-  return (size_t)(d + 8 + 40 + (cd.helpers ? TOPAY_CMD_DOUBLES : 0)) * sizeof(double);
+  return (size_t)(d + 8 + 40 + (cd.helpers() ? TOPAY_CMD_DOUBLES : 0)) * sizeof(double);
 }
 
 // Runs when the library is loaded: effective if the HIP runtime has not been initialised yet in this process
@@ -243,8 +185,6 @@ struct topay_ctx {
   int* h_started = nullptr;  // pinned host counter the solve kernels bump once per candidate (dispatch gate)
   int n_launched = 0;        // candidates the pending solve launched
   int n_gate = 0;            // ... of which the dispatch gate waits for (the classes of up to 32 pieces)
-  bool gate = true;
-  bool gate_in_solve = true;   // feasibility gate by the solving wave (TOPAY_GATE_IN_SOLVE=0: the separate kernel only)
   int latency_mode = 0;        // topay_set_latency_mode: 0 never, 1 batches of at most one candidate per SIMD, 2 always
   bool gate_done = false;      // the resident flags / report are those of the last solve
   // cancellation: planning call of every candidate, the window after a call's first feasible success (piece-evaluations)
@@ -261,7 +201,6 @@ struct topay_ctx {
   bool persistent = true;    // solve launches: one workgroup per SIMD slot pulling candidates from a queue
   bool steal = true;         // ... and draining the smaller classes' queues once its own is empty (TOPAY_STEAL=0: profiling)
   int simd_slots = 1024;
-  double occ2_gain = 1.7;    // work per SIMD-second of the two-waves-per-SIMD classes relative to one wave per SIMD (sizes the launches only)
   DevBuf qnext;
   DevBuf mc_i, mc_d, mc_k, mc_rs, mc_in;   // node tables, Reeds-Shepp words and inputs of the last topay_mcrrt_plan
   int mc_n = 0, mc_node_cap = 0;
@@ -507,27 +446,18 @@ static topay_status create_device_state(topay_ctx* c, int device) {
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
     c->simd_slots = 4 * prop.multiProcessorCount;   // four SIMDs per CU; a class built for two waves per SIMD launches two workgroups per slot
-    if (const char* og = exp_env("TOPAY_OCC2_GAIN")) c->occ2_gain = std::max(0.5, atof(og));
-    // A few slots are left to everything that is not a solve: the init kernel, the feasibility gate and the result
-    // gather of the OTHER batches in flight, the runtime's copy kernels, a collective.  Resident solver waves own their
-    // SIMD's whole register file, so on a device they fill completely such a kernel waits until workgroups exit.
-    // TOPAY_RESERVE_SLOTS=<n> keeps n slots free (default 0: use every slot).
-    {
-      const char* rs = exp_env("TOPAY_RESERVE_SLOTS");
-      const int reserve = rs ? atoi(rs) : 0;   // (measured: no gain from a standing reserve with two batches in flight)
-      if (reserve > 0 && reserve < c->simd_slots / 2) c->simd_slots -= reserve;
-    }
+    // Every slot is used.  Nothing is left to what is not a solve (the init kernel, the feasibility gate and the result
+    // gather of the OTHER batches in flight, the runtime's copy kernels, a collective), although resident solver waves own
+    // their SIMD's whole register file and such a kernel waits until workgroups exit: measured, no gain from a standing
+    // reserve with two batches in flight.
   }
   {
-    const char* g = exp_env("TOPAY_DISPATCH_GATE");
-    c->gate = !(g && g[0] == '0');
     void* hp = nullptr;
     HIPCHK(hipHostMalloc(&hp, 64, hipHostMallocMapped | hipHostMallocCoherent));
     c->h_started = (int*)hp;
     c->h_started[0] = 0;
     c->h_cancel = c->h_started + 8;   // same pinned block: topay_cancel's flag
     c->h_cancel[0] = 0;
-    { const char* ge = exp_env("TOPAY_GATE_IN_SOLVE"); c->gate_in_solve = !(ge && ge[0] == '0'); }
   }
   if (c->dmaps.ensure(sizeof(DevMap) * TOPAY_MAX_MAPS) != TOPAY_OK) return TOPAY_ERR_NO_DEVICE;
   memset(c->hmaps.data(), 0, sizeof(DevMap) * TOPAY_MAX_MAPS);
@@ -682,14 +612,9 @@ extern "C" topay_status topay_share_maps(topay_ctx* c, topay_ctx* owner, int fir
 }
 
 static int bucket_of(int N) {
-  // diagnostic: TOPAY_FORCE_CLASS=k sends every candidate that fits through launch class k (1-based) or a later one
-  static const int force = [] { const char* f = exp_env("TOPAY_FORCE_CLASS"); return f ? atoi(f) : 0; }();
-  int k0 = 0;
   for (int k = 0; k < topay_ctx::NBUCKET; k++)
-    if (N <= kBucketMaxN[k]) { k0 = k; break; }
-  if (N > kBucketMaxN[topay_ctx::NBUCKET - 1]) k0 = topay_ctx::NBUCKET - 1;
-  if (force >= 2 && force <= topay_ctx::NBUCKET) k0 = std::max(k0, force - 1);
-  return k0;
+    if (N <= kBucketMaxN[k]) return k;
+  return topay_ctx::NBUCKET - 1;
 }
 
 static bool batch_done(topay_ctx* p);
@@ -818,7 +743,7 @@ topay_status topay_build_esdf_fields(topay_ctx* c, int n_maps, int first_map_id,
   };
   // Lines of up to 512 cells (every benchmark map: 200 x 200 x 16) take the exhaustive-search passes (topay_edt.h:
   // k_edt_direct / k_edt_tile, 32-bit squared distances between the passes); longer lines the serial envelope passes.
-  const bool small_lines = std::max(nx, std::max(ny, nz)) <= 512 && exp_env("TOPAY_EDT_ENVELOPE") == nullptr;
+  const bool small_lines = std::max(nx, std::max(ny, nz)) <= 512;
   auto pick_w = [](long long lines) { int w = 1; for (int d = 1; d <= 64; d++) if (lines % d == 0) w = d; return w; };
   int* i1 = (int*)t1;
   int* i2 = (int*)t2;
@@ -1119,7 +1044,7 @@ topay_status topay_set_init_traj(topay_ctx* c, int batch, const int* path_len, c
   d.elapsed_us = c->elapsed.as<double>();
   d.start_us = c->startus.as<double>();
   d.hw_id = c->hwid.as<int>();
-  d.gate_in_solve = c->gate_in_solve ? 1 : 0;
+  d.gate_in_solve = 1;
   d.feas_flags = c->feas_flags.as<int>();
   d.feas_report = c->feas_report.as<double>();
   d.interrupted = c->interrupted.as<int>();
@@ -1163,13 +1088,12 @@ static void compute_grids(topay_ctx* c, const int* nm, double cus, int* grid) {
     double t = ct[k].nw == 1 ? 1.0 : (ct[k].nw == 2 ? 1.0 / 1.48 : 0.5);   // time of a workgroup per unit of work
     const double regs = (double)ct[k].nw / (4.0 * ct[k].occ), lds = (double)class_lds_bytes(ct[k], nm[k]) / (160.0 * 1024.0);
     rk[k] = std::max(regs, lds);
-    // a wave that shares its SIMD runs slower (two of them get through occ2_gain times the work of one); classes whose LDS
+    // a wave that shares its SIMD runs slower (two of them get through kOcc2Gain times the work of one); classes whose LDS
     // keeps them from sharing are not slowed down
-    if (ct[k].occ == 2 && lds <= 0.1875) t *= 2.0 / c->occ2_gain;
+    if (ct[k].occ == 2 && lds <= 0.1875) t *= 2.0 / kOcc2Gain;
     // the smallest class's workgroups cannot take over anybody's queue, the others can take over its: it gets less than its share
-    // (measured in round 3, tools/experiments/r3_bias.sh, factor 1.0 / 0.9 / 0.8 / 0.7: serial step 1.00 / 0.99 / 0.98 / 0.97 s)
-    static const double bias0 = [] { const char* e = exp_env("TOPAY_SHARE_BIAS0"); return e ? atof(e) : 0.8; }();
-    if (k == 0) t *= bias0;
+    // (measured in round 3, factor 1.0 / 0.9 / 0.8 / 0.7: serial step 1.00 / 0.99 / 0.98 / 0.97 s)
+    if (k == 0) t *= 0.8;
     for (int b : c->cls[k]) wt[k] += t * std::pow((double)c->hN[b], 1.5);
     need += wt[k] * rk[k];
   }
@@ -1204,14 +1128,16 @@ static hipError_t set_kernel_attributes(int device) {
   return g_attr_err[device % 16];
 }
 
-// Lowest class whose queue a workgroup of class k may go on with once its own is empty: a smaller class its kernel
-// covers AND whose candidates it solves to the same bits (the division of the L-BFGS vectors over the threads depends on
-// the waves per trajectory, so only classes with the same number of waves), and never across the long / common boundary
-// (a resident workgroup of a long class holds LDS or whole compute units the common classes' workgroups want).
+// Lowest class whose queue a workgroup of class k may go on with once its own is empty.  A stolen candidate is solved by
+// the STEALING class's kernel, which has at least as many rows per lane: the solver's elements sit in the same pairs of the
+// same lanes (the extra registers hold masked zeros) and the evaluation is order-identical over rows per thread, so the
+// bits are those of the candidate's own class.  Only classes whose workgroups have the same number of waves, and never
+// across the long / common boundary (a resident workgroup of a long class holds LDS or whole compute units the common
+// classes' workgroups want).
 static int steal_floor(int k) {
   const ClassDef* ct = class_table();
   int lo = k;
-  while (lo > 0 && ct[lo - 1].nw == ct[k].nw && ct[lo - 1].snw() == ct[k].snw() && ((lo - 1 >= kBigFirst) == (k >= kBigFirst))) lo--;
+  while (lo > 0 && ct[lo - 1].nw == ct[k].nw && ((lo - 1 >= kBigFirst) == (k >= kBigFirst))) lo--;
   return lo;
 }
 
@@ -1243,9 +1169,8 @@ static topay_status launch_classes(topay_ctx* c, bool persistent, Args... args) 
     // 8 % more workgroups than SIMD slots: in steady state 3-5 % of the SIMDs have no workgroup because the ones still
     // pending do not find LDS on the compute units where a SIMD is free (54-107 KB workgroups beside 21-36 KB ones); a few
     // pending workgroups more, mostly of the small classes, fill those.  Measured, interleaved on one box
-    // (TOPAY_OVERSUBSCRIBE=1.0 / 1.08): 10.01 / 10.20, 10.06 / 10.19, 10.04 / 10.07k trajectories/s; 1.2 is no better.
-    static const double over = [] { const char* e = exp_env("TOPAY_OVERSUBSCRIBE"); return e ? atof(e) : 1.08; }();
-    compute_grids(c, nmk, slots / 4.0 * over, pgrid);
+    // (1.0 / 1.08): 10.01 / 10.20, 10.06 / 10.19, 10.04 / 10.07k trajectories/s; 1.2 is no better.
+    compute_grids(c, nmk, slots / 4.0 * 1.08, pgrid);
   }
   HIPCHK(hipEventRecord(c->bstart, c->stream));  // params + resets on the main stream come first
   for (int k = topay_ctx::NBUCKET - 1; k >= 0; k--) {
@@ -1316,7 +1241,7 @@ topay_status topay_optimize_async(topay_ctx* c) {
     // memory (<= one bulk phase); results do not depend on it.
     std::lock_guard<std::mutex> lk(g_issue_mutex);
     topay_ctx* p = g_last_issued;
-    if (c->gate && p && p != c && p->pending && p->device == c->device && p->h_started) {
+    if (p && p != c && p->pending && p->device == c->device && p->h_started) {
       volatile int* cnt = p->h_started;
       const auto t0 = std::chrono::steady_clock::now();
       while (*cnt < p->n_gate) {
@@ -1394,7 +1319,7 @@ topay_status topay_synchronize(topay_ctx* c) {
     c->pending = false;
     // (a candidate whose history block could not hold the gate's scratch -- a small mem_size -- was left ungated by its
     // wave: the verdicts are then taken by the separate kernel, with scratch of the right size, at the first request)
-    c->gate_done = c->gate_in_solve && c->h_started[12] == 0;
+    c->gate_done = c->h_started[12] == 0;
     if (c->n_groups > 0 && c->cancel_budget > 0) {
       // The rule, applied once more to the finished batch so that the outcome does not depend on WHEN a candidate saw its
       // group's clock: a candidate counts iff its own work clock is within cancel_budget of the smallest clock of a
@@ -1465,7 +1390,6 @@ topay_status topay_set_groups(topay_ctx* c, const int* group_id, int cancel_budg
     if (had_groups) return upload_order(c, false);   // back to longest first
     return TOPAY_OK;
   }
-  if (!c->gate_in_solve) { set_err("cancellation needs the in-solve feasibility gate (switched off in this experiments build: TOPAY_GATE_IN_SOLVE=0)"); return TOPAY_ERR_UNSUPPORTED; }
   // The in-solve gate's scratch is the candidate's dead L-BFGS history block (mem_size x n doubles twice); a candidate whose
   // block is too short is left to the separate kernel and would never publish its call's clock: the window would silently
   // stay shut.  64 rows hold the gate's panels and sample times of a trajectory three times as long as its initial guess.
@@ -2717,7 +2641,7 @@ topay_status topay_class_of(int n_pieces, int* waves, int* elements_per_thread, 
   if (n_pieces <= 0 || n_pieces > TOPAY_MAX_N) return TOPAY_ERR_TOO_MANY_PIECES;
   const int k = bucket_of(n_pieces);
   const ClassDef& cd = class_table()[k];
-  if (waves) *waves = cd.snw();
+  if (waves) *waves = 1;
   if (elements_per_thread) *elements_per_thread = 2 * cd.srmax();
   if (class_index) *class_index = k;
   return TOPAY_OK;

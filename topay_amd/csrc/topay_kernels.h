@@ -145,9 +145,9 @@ __device__ __forceinline__ void eval_body(const DevBatch& Bt, const DevMap* maps
 template <int OCC>
 __device__ __noinline__ void feasibility_gate_in_solve(const FeasIO F, const TOPAY_GLB DevMap* mp) { feasibility_gate(F, mp); }
 
-// NWE = waves of the workgroup (= waves of an evaluation), NW = waves the solver runs on: NWE > NW = 1 is the helper-wave
-// scheme of the k_lat* kernels (topay_solve.h).
-template <int RMAX, int NW, int OCC, int NWE = NW, int RMAX_E = RMAX>
+// RMAX = rows per lane of the solver, which runs on one wave; NWE = waves of the workgroup (= waves of an evaluation, RMAX_E
+// rows per thread): NWE > 1 is the helper-wave scheme of the k_long* / k_lat* kernels (topay_solve.h).
+template <int RMAX, int OCC, int NWE = 1, int RMAX_E = RMAX>
 __device__ __forceinline__ void solve_one(const DevBatch& Bt, const DevMap* maps, int Nmax_lds, int b) {
   constexpr int NT = 64 * NWE;
   const unsigned long long t_begin = wall_clock64();
@@ -191,19 +191,19 @@ __device__ __forceinline__ void solve_one(const DevBatch& Bt, const DevMap* maps
   }
   int success = 0, interrupted = 0;
   double cost = 0.0;
-  if constexpr (NWE != NW) {
+  if constexpr (NWE != 1) {
     C.x = S.x;
     C.g = S.g;
     __syncthreads();   // x0 is in place for wave 0
-    if (C.wave == 0) solve_trajectory<RMAX, NW, OCC, NWE, RMAX_E>(C, mp, S, Bt.s1_past[b], pf, success, cost, interrupted);
+    if (C.wave == 0) solve_trajectory<RMAX, OCC, NWE, RMAX_E>(C, mp, S, Bt.s1_past[b], pf, success, cost, interrupted);
     else eval_helper_loop<RMAX_E, NWE, OCC>(C, mp, pf + 48);
   } else {
-    solve_trajectory<RMAX, NW, OCC>(C, mp, S, Bt.s1_past[b], pf, success, cost, interrupted);
+    solve_trajectory<RMAX, OCC>(C, mp, S, Bt.s1_past[b], pf, success, cost, interrupted);
   }
   // results: state of the last evaluation (getTraj(), moma_traj_opt.h:943-946) + traj_cost
   __syncthreads();
   store_result<NWE>(C, Bt, b);
-  if (Bt.gate_in_solve) {
+  if (Bt.gate_in_solve) {   // always 1 (DevBatch::gate_in_solve)
     // printConstraintsSituations of the returned trajectory (planner.cpp:878-880) by wave 0, from the result blocks just
     // written; panels and sample times go to the candidate's L-BFGS history blocks, which are dead now
     __syncthreads();
@@ -262,7 +262,7 @@ __device__ __forceinline__ void solve_one(const DevBatch& Bt, const DevMap* maps
 // The queues of one batch, own class first, then the smaller ones (see DevBatch::queue_next).  Without queues
 // (queue_next null: one workgroup per position of `order`) the loop body runs once, for order[blockIdx.x]: one call site
 // of the solve for both launch schemes, i.e. one copy of the solver in the kernel.
-template <int RMAX, int NW, int OCC, int NWE = NW, int RMAX_E = RMAX>
+template <int RMAX, int OCC, int NWE = 1, int RMAX_E = RMAX>
 __device__ __forceinline__ void drain_queues(const DevBatch& B, const DevMap* maps, int Nmax_lds, int my_class) {
   const bool queued = B.queue_next != nullptr;
   const int lowest = queued ? B.queue_lowest : my_class;
@@ -307,46 +307,45 @@ __device__ __forceinline__ void drain_queues(const DevBatch& B, const DevMap* ma
         continue;
       }
       if (pos >= count) break;
-      solve_one<RMAX, NW, OCC, NWE, RMAX_E>(B, maps, Nmax_lds, B.order[off + pos]);
+      solve_one<RMAX, OCC, NWE, RMAX_E>(B, maps, Nmax_lds, B.order[off + pos]);
       __syncthreads();
     }
   }
 }
 
-// Persistent launch: the grid is one workgroup per SIMD slot (or fewer; a workgroup of NW waves takes NW slots), and
+// Persistent launch: the grid is one workgroup per SIMD slot (or fewer; a workgroup of NWE waves takes NWE slots), and
 // every workgroup takes candidates from the launch's queue -- positions of `order`, longest first -- until it is empty.
 // The hardware dispatcher places workgroups in order on a fixed round-robin of XCDs / shader engines and stalls on a
 // full one while others have room (about 10 % of the slots stay empty when it has to place 8000 workgroups of unequal
 // length); a resident workgroup that fetches its next candidate itself leaves no slot idle and starts candidates
 // strictly in queue order.  Which workgroup solves which candidate is timing-dependent, the result of a candidate is
 // not (nothing is shared between candidates).
-template <int RMAX, int NW, int OCC, int NWE = NW, int RMAX_E = RMAX>
+template <int RMAX, int OCC, int NWE = 1, int RMAX_E = RMAX>
 __device__ __forceinline__ void solve_body(const DevBatch& Bt, const DevMap* maps, int Nmax_lds) {
-  drain_queues<RMAX, NW, OCC, NWE, RMAX_E>(Bt, maps, Nmax_lds, Bt.queue_class);   // the batch is the kernel argument (scalar loads, no copy)
+  drain_queues<RMAX, OCC, NWE, RMAX_E>(Bt, maps, Nmax_lds, Bt.queue_class);   // the batch is the kernel argument (scalar loads, no copy)
 }
 
 // One wave per trajectory: k_solve<rows per lane> for N <= 10 / 21 / 32, built for two waves per SIMD (256 registers, no
 // AGPRs: besides the occupancy, this keeps the register allocator from parking values in AGPRs across the calls, the
-// copies this image's compiler misplaces -- tools/isa_lint.py).  Several waves per trajectory (topay_eval_mw.h):
-// k_solve<rows per thread>w<waves>, rows <= 64 x waves x rows per thread, one wave per SIMD.
-#define TOPAY_SOLVE_KERNEL(NAME, R, W, OCC)                                                                         \
-  __global__ void __launch_bounds__(64 * W, OCC) NAME(DevBatch Bt, const DevMap* maps, int Nmax_lds) { \
-    solve_body<R, W, OCC>(Bt, maps, Nmax_lds);                                                             \
+// copies this image's compiler misplaces -- tools/isa_lint.py).
+#define TOPAY_SOLVE_KERNEL(NAME, R, OCC)                                                             \
+  __global__ void __launch_bounds__(64, OCC) NAME(DevBatch Bt, const DevMap* maps, int Nmax_lds) {   \
+    solve_body<R, OCC>(Bt, maps, Nmax_lds);                                                          \
   }
-// Helper-wave kernels for a handful of candidates (a planning call on an otherwise idle device): the one-wave solver of
-// rows-per-lane RS on wave 0, evaluations on WE waves with RE rows per thread.  Results are those of k_solve<RS>, bit for bit.
+// Helper-wave kernels (the long classes; a handful of candidates -- a planning call on an otherwise idle device): the one-wave
+// solver of rows-per-lane RS on wave 0, evaluations on WE waves with RE rows per thread.  Results are those of k_solve<RS>, bit for bit.
 #define TOPAY_LATENCY_KERNEL(NAME, RS, RE, WE, OCC)                                                        \
   __global__ void __launch_bounds__(64 * WE, OCC) NAME(DevBatch Bt, const DevMap* maps, int Nmax_lds) {    \
-    solve_body<RS, 1, OCC, WE, RE>(Bt, maps, Nmax_lds);                                                    \
+    solve_body<RS, OCC, WE, RE>(Bt, maps, Nmax_lds);                                                       \
   }
 #define TOPAY_EVAL_KERNEL(NAME, R, W, OCC)                                                                          \
   __global__ void __launch_bounds__(64 * W, OCC) NAME(DevBatch Bt, const DevMap* maps, int stage, int repeats, int Nmax_lds) { \
     eval_body<R, W, OCC>(Bt, maps, stage, Nmax_lds, repeats);                                              \
   }
 #ifndef TOPAY_NO_KERNEL_TABLE   // (tools: a probe that instantiates one kernel of its own)
-TOPAY_SOLVE_KERNEL(k_solve1, 1, 1, 2)
-TOPAY_SOLVE_KERNEL(k_solve2, 2, 1, 2)
-TOPAY_SOLVE_KERNEL(k_solve3, 3, 1, 2)
+TOPAY_SOLVE_KERNEL(k_solve1, 1, 2)
+TOPAY_SOLVE_KERNEL(k_solve2, 2, 2)
+TOPAY_SOLVE_KERNEL(k_solve3, 3, 2)
 // the long classes (N = 33..64 / 65..170): one-wave solver with 10 / 28 vector elements per lane on wave 0, evaluations on
 // four waves with 2 / 4 system rows per thread
 TOPAY_LATENCY_KERNEL(k_long5, 5, 2, 4, 2)
@@ -366,16 +365,6 @@ TOPAY_EVAL_KERNEL(k_eval4w4, 4, 4, 2)
 TOPAY_EVAL_KERNEL(k_eval4, 4, 1, 2)
 TOPAY_EVAL_KERNEL(k_eval6, 6, 1, 2)
 TOPAY_EVAL_KERNEL(k_eval2w4, 2, 4, 2)
-#ifdef TOPAY_EXPERIMENTS
-// A/B variants (tools/ab_lib.sh builds with -DTOPAY_EXPERIMENTS): the one-wave kernels of the long classes and four waves
-// for N <= 64
-TOPAY_SOLVE_KERNEL(k_solve2w4, 2, 4, 2)
-TOPAY_SOLVE_KERNEL(k_solve3w4, 3, 4, 2)
-TOPAY_SOLVE_KERNEL(k_solve4, 4, 1, 2)
-TOPAY_SOLVE_KERNEL(k_solve6, 6, 1, 2)
-TOPAY_SOLVE_KERNEL(k_solve2w2, 2, 2, 2)
-TOPAY_SOLVE_KERNEL(k_solve3w2, 3, 2, 2)
-#endif
 #endif  // TOPAY_NO_KERNEL_TABLE
 
 // feasibility gate (printConstraintsSituations / checkFeasible) of every candidate's returned trajectory

@@ -41,19 +41,17 @@ struct SolveIO {
   int cancel_budget;
 };
 
-// Vector operations on the n-element L-BFGS vectors.  A lane owns EPL / 2 pairs of adjacent elements: register t holds
-// element 128 (t / 2) + 2 lane + (t % 2), n <= 64 EPL, n even (10 N - 8), every vector and history row starts on a
-// 16-byte boundary (n_max is even) -- so a pair moves with one 16-byte load or store: half the memory instructions per
-// byte, which is what bounds a single wave (the counter of outstanding loads has 63 steps, whatever their width).
+// Vector operations on the n-element L-BFGS vectors, on the one wave the solver runs on.  Lane `tid` owns EPL / 2 pairs of
+// adjacent elements, the pairs 64 p + tid: register t holds element 128 (t / 2) + 2 tid + (t % 2), n <= 64 EPL, n even
+// (10 N - 8), every vector and history row starts on a 16-byte boundary (n_max is even) -- so a pair moves with one
+// 16-byte load or store: half the memory instructions per byte, which is what bounds a single wave (the counter of
+// outstanding loads has 63 steps, whatever their width).
 // Every load of an operation is issued before its arithmetic (clamped index + mask instead of a trip-count loop, whose
 // iterations the compiler serialises): a single wave has nothing else to hide the HBM / L2 latency behind.
 typedef double dpair __attribute__((vector_size(16)));   // plain vector type: loads through address-space pointers need no constructor
 typedef const TOPAY_GLB dpair* glb_cpp;
 typedef TOPAY_GLB dpair* glb_pp;
-// (NT = threads per trajectory: 64 for the one-wave kernels; an NW-wave workgroup divides the pairs over 64 NW threads,
-// thread tid owning the pairs NT p + tid)
-template <int NT = 64>
-__device__ __forceinline__ bool vec_in(int tid, int t, int n) { return 2 * (NT * (t >> 1) + tid) < n; }
+__device__ __forceinline__ bool vec_in(int tid, int t, int n) { return 2 * (64 * (t >> 1) + tid) < n; }
 // Pair i (elements 2 i, 2 i + 1) of an n-element row (n even, 16-byte aligned): a raw BUFFER load whose descriptor ends at
 // the row's n-th element, so pairs beyond the row come back as zeros from the hardware's range check -- no index clamp
 // and no select per loaded value (the two-loop recursion is bound by instruction issue: 8 of its 48 vector instructions
@@ -80,42 +78,42 @@ __device__ __forceinline__ dpair row_pair_or_zero(glb_cdp row, int n, int i) {
   return q;
 #endif
 }
-template <int EPL, int NT = 64>
+template <int EPL>
 __device__ __forceinline__ void vec_load(glb_cdp a, int n, int tid, double (&v)[EPL]) {
   static_assert(EPL % 2 == 0, "pairs");
 #pragma unroll
   for (int p = 0; p < EPL / 2; p++) {
-    const dpair q = row_pair_or_zero(a, n, NT * p + tid);   // (pairs beyond n: zeros; every user masks them anyway)
+    const dpair q = row_pair_or_zero(a, n, 64 * p + tid);   // (pairs beyond n: zeros; every user masks them anyway)
     v[2 * p] = q[0];
     v[2 * p + 1] = q[1];
   }
 }
-template <int EPL, int NT = 64>
+template <int EPL>
 __device__ __forceinline__ void vec_store(glb_dp a, int n, int tid, const double (&v)[EPL]) {
   const glb_pp ap = (glb_pp)a;
 #pragma unroll
   for (int p = 0; p < EPL / 2; p++) {
-    const int i = NT * p + tid;
+    const int i = 64 * p + tid;
     dpair q;
     q[0] = v[2 * p];
     q[1] = v[2 * p + 1];
     if (2 * i < n) ap[i] = q;
   }
 }
-// a thread's share of sum a[e] b[e]: its elements in ascending t (the caller finishes with the fixed wave / workgroup tree)
-template <int EPL, int NT = 64>
+// a lane's share of sum a[e] b[e]: its elements in ascending t (the caller finishes with the fixed wave tree, wave_sum)
+template <int EPL>
 __device__ __forceinline__ double vec_dot_part(glb_cdp a, glb_cdp b, int n, int tid) {
   double av[EPL], bv[EPL];
-  vec_load<EPL, NT>(a, n, tid, av);
-  vec_load<EPL, NT>(b, n, tid, bv);
+  vec_load<EPL>(a, n, tid, av);
+  vec_load<EPL>(b, n, tid, bv);
   double s = 0.0;
 #pragma unroll
-  for (int t = 0; t < EPL; t++) s += vec_in<NT>(tid, t, n) ? av[t] * bv[t] : 0.0;
+  for (int t = 0; t < EPL; t++) s += vec_in(tid, t, n) ? av[t] * bv[t] : 0.0;
   return s;
 }
 
-// Helper waves (the kernels for a handful of candidates, topay_kernels.h: k_lat*).  With NWE > NW = 1 the workgroup has NWE
-// waves but the solver runs on wave 0 alone -- its vectors, reductions and two-loop recursion are those of the one-wave
+// Helper waves (the kernels of the long classes and for a handful of candidates, topay_kernels.h: k_long*, k_lat*).  With
+// NWE > 1 the workgroup has NWE waves but the solver runs on wave 0 alone -- its vectors, reductions and two-loop recursion are those of the one-wave
 // kernels, so the bits of a solve are the one-wave bits -- and the other waves only join the evaluations (which are
 // order-identical for any number of waves, topay_eval_mw.h): wave 0 posts the evaluation's inputs in a command block in
 // LDS, every wave meets at a workgroup barrier and evaluates.  What that shortens is the sample passes of the two sweeps (a
@@ -152,34 +150,22 @@ __device__ __forceinline__ void eval_helper_loop(EvalCtx& C, const TOPAY_GLB Dev
 #else
 #define LSTAMP(k) do { } while (0)
 #endif
-template <int RMAX, int NW = 1, int OCC = 2, int NWE = NW, int RMAX_E = RMAX>
+// The solver runs on one wave (RMAX rows, 2 RMAX vector elements per lane).  NWE = waves of the workgroup = waves of an
+// evaluation (RMAX_E rows per thread): with NWE > 1 the caller runs this on wave 0 and eval_helper_loop on the others -- helper
+// waves join a one-wave solver.
+template <int RMAX, int OCC = 2, int NWE = 1, int RMAX_E = RMAX>
 __device__ __forceinline__ void solve_trajectory(EvalCtx& C, const TOPAY_GLB DevMap* mp, SolveIO& S, int s1_past,
-                                                 lds_dp pf /* LDS [8 + 40], then the command block if NWE != NW */, int& success_out,
+                                                 lds_dp pf /* LDS [8 + 40], then the command block if NWE != 1 */, int& success_out,
                                                  double& cost_out, int& interrupted_out) {
-  static_assert(NWE == NW || NW == 1, "helper waves join a one-wave solver");
-  constexpr bool HELPERS = NWE != NW;
+  constexpr bool HELPERS = NWE != 1;
   dev_params_ref P = dev_params();
-  constexpr int NT = 64 * NW;    // threads that run the solver
   // barrier among the solver's threads (with helper waves: wave 0 alone -- no workgroup barrier outside the hand-shake)
   auto ssync = [&]() {
     if constexpr (HELPERS) { wave_global_sync(); lds_sync(); }
     else __syncthreads();
   };
   const int tid = C.tid, n = __builtin_amdgcn_readfirstlane(C.n);
-  constexpr int EPL = 2 * RMAX;  // decision-vector elements per thread: n <= NT * EPL
-  // sums / maxima over the trajectory's threads in a fixed order: the wave tree, then (NW > 1) the waves' partial results
-  // through LDS, (w0 + w1) + (w2 + w3)
-  const int wave = __builtin_amdgcn_readfirstlane(C.wave);
-  const lds_dp c_red = C.red;
-  int rp = 0;
-  auto wsum = [&](double v) -> double {
-    if constexpr (NW == 1) return wave_sum(v);
-    else return wg_sum<NW>(c_red, rp, wave, v);
-  };
-  auto wmax = [&](double v) -> double {
-    if constexpr (NW == 1) return wave_max(v);
-    else return wg_max<NW>(c_red, rp, wave, v);
-  };
+  constexpr int EPL = 2 * RMAX;  // decision-vector elements per lane: n <= 64 * EPL; sums / maxima over them: the fixed wave tree
   int stage = 1;
   int alm_iter = 0;
   bool success = false, interrupted = false;
@@ -212,7 +198,7 @@ __device__ __forceinline__ void solve_trajectory(EvalCtx& C, const TOPAY_GLB Dev
     // ------------------------------------------------------------------ interruption point (moma_traj_opt.cpp:402, 887)
     if (stage == 2 && (S.grp_tau || S.cancel_flag)) {
       // one thread reads (the values may change between two reads), everybody gets its verdict: lane 0's through a
-      // broadcast inside the wave, through the parked-state block across waves
+      // broadcast inside the wave
       int stop = 0;
       if (tid == 0) {
         const int clock = (st_s1_ev + st_s2_ev + evals) * C.N;   // piece-evaluations done so far
@@ -225,15 +211,7 @@ __device__ __forceinline__ void solve_trajectory(EvalCtx& C, const TOPAY_GLB Dev
         if (S.cancel_flag && (evals & poll_mask) == 0) stop |= *S.cancel_flag != 0;
 #endif
       }
-      if constexpr (NW == 1) {
-        stop = __shfl(stop, 0);
-      } else {
-        TOPAY_LDS int* sw = (TOPAY_LDS int*)(pf + 46);
-        __syncthreads();
-        if (tid == 0) sw[0] = stop;
-        __syncthreads();
-        stop = sw[0];
-      }
+      stop = __shfl(stop, 0);
       if (stop) {
         st_s2_ret = TOPAY_INTERRUPTED; st_s2_it += k; st_s2_ev += evals;
         interrupted = true;
@@ -295,7 +273,6 @@ __device__ __forceinline__ void solve_trajectory(EvalCtx& C, const TOPAY_GLB Dev
     lt_ = (long long)__builtin_amdgcn_s_memtime();
 #endif
     if (NWE > 1) wg_lds_barrier();   // every wave is out of the evaluation's last reduction before the scratch is used again
-    rp = 0;
     {
       // (read back as wave-uniform values: scalar registers, scalar branches, scalar base addresses for the vector loads)
       lds_cdp pk = pf + 8;
@@ -339,25 +316,25 @@ __device__ __forceinline__ void solve_trajectory(EvalCtx& C, const TOPAY_GLB Dev
       double gmax = 0.0, xmax = 0.0;
       {
         double gv[EPL], xv[EPL], dv[EPL];
-        vec_load<EPL, NT>(S.g, n, tid, gv);
-        vec_load<EPL, NT>(S.x, n, tid, xv);
+        vec_load<EPL>(S.g, n, tid, gv);
+        vec_load<EPL>(S.x, n, tid, xv);
 #pragma unroll
         for (int t = 0; t < EPL; t++) {
-          const bool in = vec_in<NT>(tid, t, n);
+          const bool in = vec_in(tid, t, n);
           dv[t] = -gv[t];
           gmax = in ? fmax(gmax, fabs(gv[t])) : gmax;
           xmax = in ? fmax(xmax, fabs(xv[t])) : xmax;
         }
-        vec_store<EPL, NT>(S.d, n, tid, dv);
+        vec_store<EPL>(S.d, n, tid, dv);
       }
-      gmax = wmax(gmax);
-      xmax = wmax(xmax);
+      gmax = wave_max(gmax);
+      xmax = wave_max(xmax);
       k = 0;
       if (gmax / fmax(1.0, xmax) < lp.g_epsilon) {
         ret = TOPAY_LBFGS_CONVERGENCE;
         go = GO_RUN_END;
       } else {
-        step = 1.0 / sqrt(wsum(vec_dot_part<EPL, NT>(S.d, S.d, n, tid)));
+        step = 1.0 / sqrt(wave_sum(vec_dot_part<EPL>(S.d, S.d, n, tid)));
         k = 1;
         end = 0;
         bound = 0;
@@ -377,7 +354,7 @@ __device__ __forceinline__ void solve_trajectory(EvalCtx& C, const TOPAY_GLB Dev
           nu = stp;
           brackt = true;
         } else {
-          const double gs = wsum(vec_dot_part<EPL, NT>(S.g, S.d, n, tid));
+          const double gs = wave_sum(vec_dot_part<EPL>(S.g, S.d, n, tid));
           if (gs < dstest) mu = stp;
           else accepted = true;
         }
@@ -397,11 +374,11 @@ __device__ __forceinline__ void solve_trajectory(EvalCtx& C, const TOPAY_GLB Dev
       if (ls == 0) {
         {
           double pv[EPL], dv[EPL], xv[EPL];
-          vec_load<EPL, NT>(S.xp, n, tid, pv);
-          vec_load<EPL, NT>(S.d, n, tid, dv);
+          vec_load<EPL>(S.xp, n, tid, pv);
+          vec_load<EPL>(S.d, n, tid, dv);
 #pragma unroll
           for (int t = 0; t < EPL; t++) xv[t] = pv[t] + stp * dv[t];
-          vec_store<EPL, NT>(S.x, n, tid, xv);
+          vec_store<EPL>(S.x, n, tid, xv);
         }
         go = GO_EVAL;
       } else if (ls < 0) {
@@ -409,10 +386,10 @@ __device__ __forceinline__ void solve_trajectory(EvalCtx& C, const TOPAY_GLB Dev
         fx = f;
         {
           double pv[EPL], qv[EPL];
-          vec_load<EPL, NT>(S.xp, n, tid, pv);
-          vec_load<EPL, NT>(S.gp, n, tid, qv);
-          vec_store<EPL, NT>(S.x, n, tid, pv);
-          vec_store<EPL, NT>(S.g, n, tid, qv);
+          vec_load<EPL>(S.xp, n, tid, pv);
+          vec_load<EPL>(S.gp, n, tid, qv);
+          vec_store<EPL>(S.x, n, tid, pv);
+          vec_store<EPL>(S.g, n, tid, qv);
         }
         ret = ls;
         go = GO_RUN_END;
@@ -427,17 +404,17 @@ __device__ __forceinline__ void solve_trajectory(EvalCtx& C, const TOPAY_GLB Dev
           double gmax = 0.0, xmax = 0.0;
           {
             double gv[EPL], xv[EPL];
-            vec_load<EPL, NT>(S.g, n, tid, gv);
-            vec_load<EPL, NT>(S.x, n, tid, xv);
+            vec_load<EPL>(S.g, n, tid, gv);
+            vec_load<EPL>(S.x, n, tid, xv);
 #pragma unroll
             for (int t = 0; t < EPL; t++) {
-              const bool in = vec_in<NT>(tid, t, n);
+              const bool in = vec_in(tid, t, n);
               gmax = in ? fmax(gmax, fabs(gv[t])) : gmax;
               xmax = in ? fmax(xmax, fabs(xv[t])) : xmax;
             }
           }
-          gmax = wmax(gmax);
-          xmax = wmax(xmax);
+          gmax = wave_max(gmax);
+          xmax = wave_max(xmax);
           if (gmax / fmax(1.0, xmax) < lp.g_epsilon) { ret = TOPAY_LBFGS_CONVERGENCE; fin = true; }
         }
         if (!fin && past > 0) {
@@ -462,24 +439,24 @@ __device__ __forceinline__ void solve_trajectory(EvalCtx& C, const TOPAY_GLB Dev
           double ys = 0.0, yy = 0.0, ss = 0.0, gg = 0.0;
           {
             double xv[EPL], pv[EPL], gv[EPL], qv[EPL], sv[EPL], yv[EPL], dv[EPL];
-            vec_load<EPL, NT>(S.x, n, tid, xv);
-            vec_load<EPL, NT>(S.xp, n, tid, pv);
-            vec_load<EPL, NT>(S.g, n, tid, gv);
-            vec_load<EPL, NT>(S.gp, n, tid, qv);
+            vec_load<EPL>(S.x, n, tid, xv);
+            vec_load<EPL>(S.xp, n, tid, pv);
+            vec_load<EPL>(S.g, n, tid, gv);
+            vec_load<EPL>(S.gp, n, tid, qv);
 #pragma unroll
             for (int t = 0; t < EPL; t++) {
-              const bool in = vec_in<NT>(tid, t, n);
+              const bool in = vec_in(tid, t, n);
               const double se = xv[t] - pv[t], ye = gv[t] - qv[t], gpe = qv[t];
               sv[t] = se;
               yv[t] = ye;
               ys += in ? ye * se : 0.0; yy += in ? ye * ye : 0.0; ss += in ? se * se : 0.0; gg += in ? gpe * gpe : 0.0;
               dv[t] = -gv[t];
             }
-            vec_store<EPL, NT>(sE, n, tid, sv);
-            vec_store<EPL, NT>(yE, n, tid, yv);
-            vec_store<EPL, NT>(S.d, n, tid, dv);
+            vec_store<EPL>(sE, n, tid, sv);
+            vec_store<EPL>(yE, n, tid, yv);
+            vec_store<EPL>(S.d, n, tid, dv);
           }
-          ys = wsum(ys); yy = wsum(yy); ss = wsum(ss); gg = wsum(gg);
+          ys = wave_sum(ys); yy = wave_sum(yy); ss = wave_sum(ss); gg = wave_sum(gg);
           // 1/ys is stored instead of ys: one division per iteration instead of two per history pair.
           // Every lane stores the same value; each lane later reads back its own store.
           S.hist_ys[end] = 1.0 / ys;
@@ -502,9 +479,9 @@ __device__ __forceinline__ void solve_trajectory(EvalCtx& C, const TOPAY_GLB Dev
             double dr[EPL];
             {
               double gv[EPL];
-              vec_load<EPL, NT>(S.g, n, tid, gv);
+              vec_load<EPL>(S.g, n, tid, gv);
 #pragma unroll
-              for (int t = 0; t < EPL; t++) dr[t] = vec_in<NT>(tid, t, n) ? -gv[t] : 0.0;
+              for (int t = 0; t < EPL; t++) dr[t] = vec_in(tid, t, n) ? -gv[t] : 0.0;
             }
             double sb[PF][EPL], yb[PF][EPL], rb[PF];
             // [mem <= 256]: every lane writes / reads the same entry (LDS broadcast).  The ring lives in the evaluation's
@@ -527,7 +504,7 @@ __device__ __forceinline__ void solve_trajectory(EvalCtx& C, const TOPAY_GLB Dev
               const glb_cdp yj = (glb_cdp)((glb_ccp)S.hist_y + ro);
 #pragma unroll
               for (int p = 0; p < EPL / 2; p++) {
-                const int i = NT * p + tid;
+                const int i = 64 * p + tid;
                 const dpair sv = row_pair_or_zero<true>(sj, n, i), yv = row_pair_or_zero<true>(yj, n, i);   // zeros beyond the row; streaming
                 sb[slot][2 * p] = sv[0];
                 sb[slot][2 * p + 1] = sv[1];
@@ -544,7 +521,7 @@ __device__ __forceinline__ void solve_trajectory(EvalCtx& C, const TOPAY_GLB Dev
               double part = 0.0;
 #pragma unroll
               for (int t = 0; t < EPL; t++) part = fma(sb[u][t], dr[t], part);
-              const double al = wsum(part) * rb[u];
+              const double al = wave_sum(part) * rb[u];
               alpha[i] = al;
 #pragma unroll
               for (int t = 0; t < EPL; t++) dr[t] = fma(-al, yb[u][t], dr[t]);
@@ -574,7 +551,7 @@ __device__ __forceinline__ void solve_trajectory(EvalCtx& C, const TOPAY_GLB Dev
               double part = 0.0;
 #pragma unroll
               for (int t = 0; t < EPL; t++) part = fma(yb[u][t], dr[t], part);
-              const double beta = wsum(part) * rb[u];
+              const double beta = wave_sum(part) * rb[u];
               const double co = av - beta;
 #pragma unroll
               for (int t = 0; t < EPL; t++) dr[t] = fma(co, sb[u][t], dr[t]);
@@ -594,7 +571,7 @@ __device__ __forceinline__ void solve_trajectory(EvalCtx& C, const TOPAY_GLB Dev
 #pragma unroll
             for (int u = 0; u < PF - 1; u++)
               if (i0 + u < boundu) step2(u, i0 + u);
-            vec_store<EPL, NT>(S.d, n, tid, dr);
+            vec_store<EPL>(S.d, n, tid, dr);
             SUBSTAMP_END(C, 10);  // two-loop recursion
           }
           step = 1.0;
@@ -608,10 +585,10 @@ __device__ __forceinline__ void solve_trajectory(EvalCtx& C, const TOPAY_GLB Dev
       // lbfgs.hpp:559-573 + line-search prologue 288-311
       {
         double xv[EPL], gv[EPL];
-        vec_load<EPL, NT>(S.x, n, tid, xv);
-        vec_load<EPL, NT>(S.g, n, tid, gv);
-        vec_store<EPL, NT>(S.xp, n, tid, xv);
-        vec_store<EPL, NT>(S.gp, n, tid, gv);
+        vec_load<EPL>(S.x, n, tid, xv);
+        vec_load<EPL>(S.g, n, tid, gv);
+        vec_store<EPL>(S.xp, n, tid, xv);
+        vec_store<EPL>(S.gp, n, tid, gv);
       }
       stp = step;
       count = 0;
@@ -622,7 +599,7 @@ __device__ __forceinline__ void solve_trajectory(EvalCtx& C, const TOPAY_GLB Dev
       int err = 0;
       if (!(stp > 0.0)) err = TOPAY_LBFGSERR_INVALIDPARAMETERS;
       else {
-        dginit = wsum(vec_dot_part<EPL, NT>(S.gp, S.d, n, tid));
+        dginit = wave_sum(vec_dot_part<EPL>(S.gp, S.d, n, tid));
         if (0.0 < dginit) err = TOPAY_LBFGSERR_INCREASEGRADIENT;
       }
       if (err) {
@@ -634,11 +611,11 @@ __device__ __forceinline__ void solve_trajectory(EvalCtx& C, const TOPAY_GLB Dev
         dstest = lp.s_curv_coeff * dginit;
         {
           double pv[EPL], dv[EPL], xv[EPL];
-          vec_load<EPL, NT>(S.xp, n, tid, pv);
-          vec_load<EPL, NT>(S.d, n, tid, dv);
+          vec_load<EPL>(S.xp, n, tid, pv);
+          vec_load<EPL>(S.d, n, tid, dv);
 #pragma unroll
           for (int t = 0; t < EPL; t++) xv[t] = pv[t] + stp * dv[t];
-          vec_store<EPL, NT>(S.x, n, tid, xv);
+          vec_store<EPL>(S.x, n, tid, xv);
         }
         mode = MODE_LS;
         go = GO_EVAL;

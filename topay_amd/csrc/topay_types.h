@@ -147,7 +147,7 @@ struct DevBatch {
   int queue_lowest;   // 0: drain the smaller classes' queues too; = queue_class: own queue only (TOPAY_STEAL=0, profiling)
   // feasibility gate inside the solve (printConstraintsSituations of the returned trajectory by the wave that solved it;
   // its scratch is the candidate's own, by then dead, L-BFGS history block): verdicts and extremes per candidate
-  int gate_in_solve;
+  int gate_in_solve;   // always 1: the field and its tests stay until a change that may alter the solve kernels' code (it moves every later kernel argument)
   int* gate_truncated; // one counter in pinned host memory: candidates whose history block was too short for the gate's scratch
   int* feas_flags;    // [B][2]
   double* feas_report;// [B][38]
