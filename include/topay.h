@@ -400,6 +400,75 @@ topay_status topay_topo_graph(topay_ctx* ctx, int instance, int cap, int* id, in
 topay_status topay_topo_raw_paths(topay_ctx* ctx, int instance, int which, int cap_paths, int cap_points, int* n_paths,
                                   int* path_len /* cap_paths */, double* path_xy /* cap_paths x cap_points x 2 */);
 
+/* == Planner::planMomaParallel (src/planner/src/planner.cpp:792-1061), the whole planning call, for n calls at once: start
+ * state, goal state and map slot in, the winning trajectory out.  Every stage is the kernel of its own entry point above and
+ * every intermediate result stays on the device; only per-candidate counts, lengths and statuses come back between the
+ * stages (they size the next launch and the solver's workspace).  Per call p, try t = 0 (plain fields), then t = 1 (the
+ * critical field, planner.cpp:961-963) for the calls that have no winner yet:
+ *   candidates   select_paths of topay_topo_paths (critical = t) in its order; for t = 0 the topay_plan2d_jps path
+ *                (threshold chassis_colli_radius + jps_margin) is appended when it is not empty (a JPS path of more than
+ *                512 points is a candidate that fails with search status -2: it is not kept).  No candidate: the try
+ *                fails.  More than max_candidates: the reference throws "Too many paths to optimize" (planner.cpp:829):
+ *                status -3 for that call, nothing more is run for it, the other calls are not affected.
+ *   candidate k  getDensePath(path, dense_step, start[2], end[2], max_v, max_w), then MCRRTs::plan(start, end, dense) with
+ *                `end` as given; a search without a path (or with fewer than 2 states, or a dense path outside 2..255
+ *                entries: search status -2) fails the candidate.
+ *   solve        the survivors of all calls of the try are ONE batch: init paths = the whole-body paths, column 0 of
+ *                boundary_vel = start_v and zeros elsewhere (planner.cpp:873-875), map slot = the call's, group = the call
+ *                with cancel_budget (topay_set_groups); topay_optimize, then the gate.  A candidate counts iff success, gate
+ *                passed and not interrupted.  One that needs more than 170 pieces fails as topay_set_init_traj reports it.
+ *   winner       the first candidate, in candidate order, whose total duration is strictly the smallest (planner.cpp:999-1010;
+ *                rule and summation order of topay_scenario_records / topay_get_total_durations).
+ * A call that fails both tries has status 0: the reference would now try OMPL's planners (planner.cpp:974-993), which are
+ * outside this library.
+ * The result of a call depends on nothing but the call: with c = first_call + p the roadmap draws with instance 2 c + t and
+ * the search of candidate k with instance 16 c + 8 t + k, so a call may be batched with any others, in any order.
+ *   result[p][8]             status (1 winner, 0 none, -3 too many candidates), try that decided the call (the winner's, else
+ *                            the last one attempted; -1 none), candidates of try 0, of try 1, winner k or -1, the winner's
+ *                            pieces, roadmap status of the last try attempted, the winner's index in the batch of its try
+ *                            or -1 (what the per-candidate getters take while that batch is the resident one; a
+ *                            position in the batch, hence the one entry that depends on what the call is batched with)
+ *   candidates[p][2][8][4]   (optional) stage, n_pieces, search status, solver stage-2 status; stage: 0 absent, 1 search
+ *                            failed, 2 too many pieces, 3 solver failed, 4 gate failed, 5 interrupted, 6 counts
+ *   winner_cost_duration[p][2]  (optional) the winner's traj_cost and total duration (NaN without a winner)
+ * The winners' durations, coefficients, knots and whole-body init paths are gathered on the device into a store of the
+ * context (the second try reuses the workspace); it stays valid until the next topay_plan_calls or topay_destroy and is what
+ * topay_plan_get_trajs (layout of topay_get_results, per call instead of per candidate) and topay_plan_get_front_path read;
+ * a call without a winner contributes zero pieces / zero states.  Afterwards the context's resident batch is the last
+ * try's that had a candidate to solve: the getters above keep working on it.
+ * Errors: TOPAY_ERR_NO_MAP when a call's slot has no front-end fields (topay_set_map); TOPAY_ERR_INVALID_ARG for n <= 0, NULL
+ * start / end / result, max_candidates outside 1..8 or a stage's parameters out of range.  A solve in flight is waited for.
+ * Device memory: per call of a front-end launch 1.1 MB of roadmap state (defaults, 200 x 200 map), 0.1 MB of raw paths and
+ * 64 KB of dense paths; per candidate 0.27 MB of search state (node_cap 2048) and the solver's workspace (topay_workspace_bytes:
+ * 0.4 MB at 11 pieces); the 21 bytes per map cell and JPS search are chunked to 2 GB.  The front-end runs in launches of at
+ * most 1024 calls (a constant: results do not depend on it), so n calls need about min(n, 1024) x 2.2 MB + n x 3 x 0.4 MB.
+ * topay_plan_test_chunk (test hook): another number of calls per front-end launch for this context, 0 = the constant.
+ * topay_plan_stage_ms: device time of the last topay_plan_calls by stage, from pairs of HIP events around the stage's
+ * launches on the context's stream (uploads, allocations and the host's waits between the stages are outside), 8 doubles:
+ * roadmap, JPS, candidate table + dense paths, search (with its hand-off), init (hand-off + k_init), solve, gate + winner,
+ * store gather. */
+typedef struct {
+  topay_topo_params_t topo;      /* topay_topo_default_params */
+  topay_mcrrt_params_t mcrrt;    /* topay_mcrrt_default_params */
+  double dense_step;             /* 1.414  (planner.cpp:858) */
+  double jps_margin;             /* 0.1: plan2dJPS threshold = chassis_colli_radius + jps_margin (planner.cpp:816) */
+  int cancel_budget;             /* 2400 piece-evaluations = the 100 ms of planner.cpp:946; 0 = no cancellation */
+  int max_candidates;            /* 8 = traj_opters.size() (planner.cpp:59, 829); at most 8 */
+  int critical_retry;            /* 1: second try on the critical field for calls without a success (961-963) */
+  int reserved;
+} topay_plan_params_t;
+void topay_plan_default_params(topay_plan_params_t* p);
+topay_status topay_plan_calls(topay_ctx* ctx, int n, const int* map_ids /* n, NULL = slot 0 */, const double* start /* n x 10 */,
+                              const double* end /* n x 10 */, const double* start_v /* n x 10, NULL = zeros */,
+                              const topay_plan_params_t* params /* NULL = defaults */, unsigned long long first_call,
+                              int* result /* n x 8 */, int* candidates /* n x 2 x 8 x 4, optional */,
+                              double* winner_cost_duration /* n x 2, optional */);
+topay_status topay_plan_get_trajs(topay_ctx* ctx, int n, const int* call_idx, int cap_pieces, int* piece_off, double* durations,
+                                  double* coeffs, double* knots_xy);
+topay_status topay_plan_get_front_path(topay_ctx* ctx, int call, int cap_states, int* n_states, double* states /* x 10 */);
+topay_status topay_plan_stage_ms(topay_ctx* ctx, double* ms /* 8 */);
+topay_status topay_plan_test_chunk(topay_ctx* ctx, int calls);
+
 /* ompl::base::ReedsSheppStateSpace(rho) for n pose pairs (x, y, theta): distance[i] = distance(from_i, to_i), word[i] /
  * lengths[i][5] = the shortest path's segment word (0..17, OMPL's reedsSheppPathType numbering) and signed segment lengths
  * in units of rho, pose[i] = interpolate(from_i, to_i, t[i]) when t is given.  Output pointers may be NULL. */

@@ -79,6 +79,17 @@ class TopoParams(C.Structure):
 TOPO_MAX_NB = 32   # TOPAY_TOPO_MAX_NB
 
 
+class PlanParams(C.Structure):
+    """topay_plan_params_t (include/topay.h): the stages' parameters and the planner's constants of a planning call."""
+    _fields_ = [("topo", TopoParams), ("mcrrt", McrrtParams), ("dense_step", C.c_double), ("jps_margin", C.c_double),
+                ("cancel_budget", C.c_int), ("max_candidates", C.c_int), ("critical_retry", C.c_int), ("reserved", C.c_int)]
+
+
+PLAN_RESULT_KEYS = ["status", "try", "candidates0", "candidates1", "winner", "n_pieces", "topo_status", "winner_batch_index"]
+PLAN_STAGES = ["absent", "search_failed", "too_many_pieces", "solver_failed", "gate_failed", "interrupted", "counts"]
+PLAN_STAGE_MS_KEYS = ["roadmap", "jps", "dense", "search", "init", "solve", "gate_winner", "store"]
+
+
 class Record(C.Structure):
     """topay_record_t: the 32-byte per-scenario record of the multi-GPU exchange."""
     _fields_ = [("scenario_id", C.c_int), ("best_candidate", C.c_int), ("status", C.c_int), ("n_pieces", C.c_int),
@@ -137,6 +148,14 @@ def load(path=None):
                                    c_dp, c_ip]
     L.topay_topo_graph.argtypes = [C.c_void_p, C.c_int, C.c_int, c_ip, c_ip, c_dp, c_ip, c_ip, c_ip]
     L.topay_topo_raw_paths.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_ip, c_ip, c_dp]
+    if hasattr(L, "topay_plan_calls"):   # (older builds of the library under tools/libs, A/B runs)
+        L.topay_plan_default_params.argtypes = [C.POINTER(PlanParams)]
+        L.topay_plan_default_params.restype = None
+        L.topay_plan_calls.argtypes = [C.c_void_p, C.c_int, c_ip, c_dp, c_dp, c_dp, C.POINTER(PlanParams), C.c_ulonglong, c_ip, c_ip, c_dp]
+        L.topay_plan_get_trajs.argtypes = [C.c_void_p, C.c_int, c_ip, C.c_int, c_ip, c_dp, c_dp, c_dp]
+        L.topay_plan_get_front_path.argtypes = [C.c_void_p, C.c_int, C.c_int, c_ip, c_dp]
+        L.topay_plan_stage_ms.argtypes = [C.c_void_p, c_dp]
+        L.topay_plan_test_chunk.argtypes = [C.c_void_p, C.c_int]
     L.topay_reeds_shepp.argtypes = [C.c_void_p, C.c_int, c_dp, c_dp, c_dp, C.c_double, c_dp, c_ip, c_dp, c_dp]
     L.topay_dense_path.argtypes = [C.c_void_p, C.c_int, c_ip, c_dp, C.c_double, c_dp, c_dp, C.c_double, C.c_double, C.c_int, c_ip, c_dp]
     L.topay_connect_check_num.argtypes = [C.c_int, c_dp, c_dp, c_dp, C.c_double, c_ip]
@@ -343,6 +362,7 @@ class MomaTrajOptBatch:
         self.batch = 0
         self.traj_cost = None
         self._map_dims = {}
+        self._plan_pieces = None
 
     def close(self):
         if getattr(self, "h", None):
@@ -670,6 +690,65 @@ class MomaTrajOptBatch:
             if len(paths[p]) > 8:
                 raise ValueError(f"query {p}: {len(paths[p])} candidate paths (at most 8: too many paths to optimize)")
         return paths
+
+    def plan_params(self, topo=None, mcrrt=None, **kw):
+        """PlanParams with the defaults of topay_plan_default_params; topo / mcrrt: dicts of fields of the two stages' blocks."""
+        p = PlanParams()
+        self.L.topay_plan_default_params(C.byref(p))
+        for k, v in (topo or {}).items():
+            setattr(p.topo, k, v)
+        for k, v in (mcrrt or {}).items():
+            setattr(p.mcrrt, k, v)
+        for k, v in kw.items():
+            setattr(p, k, v)
+        return p
+
+    def plan_calls(self, start, end, map_ids=None, start_v=None, params=None, first_call=0):
+        """Planner::planMomaParallel for n calls (topay_plan_calls): start / end [n, 10] states.  Returns (result [n, 8] --
+        PLAN_RESULT_KEYS --, candidates [n, 2, 8, 4] = (stage, n_pieces, search status, solver stage-2 status) per try and
+        candidate, winner_cost_duration [n, 2]).  The winners stay in the context's store: plan_trajs / plan_front_path."""
+        st = np.ascontiguousarray(start, dtype=np.float64).reshape(-1, 10)
+        en = np.ascontiguousarray(end, dtype=np.float64).reshape(-1, 10)
+        n = len(st)
+        mid = None if map_ids is None else np.ascontiguousarray(map_ids, dtype=np.int32)
+        sv = None if start_v is None else np.ascontiguousarray(start_v, dtype=np.float64).reshape(n, 10)
+        res, cand, wcd = np.zeros((n, 8), dtype=np.int32), np.zeros((n, 2, 8, 4), dtype=np.int32), np.zeros((n, 2))
+        _chk(self.L, self.L.topay_plan_calls(self.h, n, _ip(mid), _dp(st), _dp(en), _dp(sv), None if params is None else C.byref(params),
+                                             int(first_call), _ip(res), _ip(cand), _dp(wcd)))
+        self._plan_pieces = np.where(res[:, 0] == 1, res[:, 5], 0)
+        return res, cand, wcd
+
+    def plan_trajs(self, calls):
+        """The winners of a selection of calls of the last plan_calls, packed like getTrajs: piece_off[n+1], durations[P],
+        coeffs[P, 9, 6], knots_xy[P + n, 2] (a call without a winner has no pieces)."""
+        if self._plan_pieces is None:
+            raise TopayError("plan_trajs: no plan_calls has been run on this context")
+        idx = np.ascontiguousarray(calls, dtype=np.int32)
+        n = len(idx)
+        cap = int(self._plan_pieces[idx].sum()) if n else 0
+        off = np.zeros(n + 1, dtype=np.int32)
+        dur, coef, kn = np.zeros(cap), np.zeros(cap * 54), np.zeros(2 * (cap + n))
+        _chk(self.L, self.L.topay_plan_get_trajs(self.h, n, _ip(idx), cap, _ip(off), _dp(dur), _dp(coef), _dp(kn)))
+        return dict(piece_off=off, durations=dur, coeffs=coef.reshape(cap, 9, 6), knots_xy=kn.reshape(cap + n, 2))
+
+    def plan_front_path(self, call):
+        """The whole-body init path ([m, 10]) the winner of `call` was optimised from; empty without a winner."""
+        n = C.c_int(0)
+        _chk(self.L, self.L.topay_plan_get_front_path(self.h, int(call), 0, C.byref(n), None))
+        out = np.zeros((n.value, 10))
+        if n.value:
+            _chk(self.L, self.L.topay_plan_get_front_path(self.h, int(call), n.value, C.byref(n), _dp(out)))
+        return out
+
+    def plan_test_chunk(self, calls):
+        """Test hook: calls per front-end launch of plan_calls on this context (0 = the library's constant, 1024)."""
+        _chk(self.L, self.L.topay_plan_test_chunk(self.h, int(calls)))
+
+    def plan_stage_ms(self):
+        """Device time of the last plan_calls by stage (PLAN_STAGE_MS_KEYS), milliseconds."""
+        ms = np.zeros(8)
+        _chk(self.L, self.L.topay_plan_stage_ms(self.h, _dp(ms)))
+        return dict(zip(PLAN_STAGE_MS_KEYS, ms.tolist()))
 
     def mcrrt_params(self, **kw):
         p = McrrtParams()

@@ -99,6 +99,7 @@ __global__ void k_dense_path(int n, const double* raw, const long long* off, con
                              const double* eyaw, double v_max, double w_max, int cap, double* out, int* out_len) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= n) return;
+  if (len[p] < 1) { out_len[p] = 0; return; }   // an empty slot of a planning call's candidate table (the public entry refuses such a path)
   out_len[p] = dense_path(raw + 2 * off[p], len[p], step_size, syaw[p], eyaw[p], v_max, w_max, out + (size_t)p * cap * 4, cap);
 }
 

@@ -24,6 +24,7 @@
 #include "topay_mcrrt.h"
 #include "topay_jps.h"
 #include "topay_topo.h"
+#include "topay_plan.h"
 #include "topay_yaml.h"
 
 #include "topay_kernels.h"
@@ -207,6 +208,17 @@ struct topay_ctx {
   DevBuf tp_i, tp_d, tp_raw, tp_pts, tp_io;   // graphs, raw paths and point buffers of the last topay_topo_paths (topay_topo_graph / _raw_paths)
   int tp_n = 0, tp_pt_cap = 0, tp_nbuf = 0;
   topay_topo_params_t tp_P;
+  // topay_plan_calls: the raw paths, candidate table + dense paths, search inputs / results, the try's init paths and boundary
+  // velocities, index blocks of the hand-offs, and the winner store (durations, coefficients, knots, init paths)
+  DevBuf pl_raw, pl_jps_io, pl_io, pl_tab, pl_mc, pl_paths, pl_bvel, pl_sel, pl_win, ps_dur, ps_coef, ps_kn, ps_front;
+  struct PlanStored { int n_pieces = 0, piece0 = 0, knot0 = 0, front0 = 0, front_len = 0; };
+  std::vector<PlanStored> ps_calls;   // per call of the last topay_plan_calls: where its winner lies in the store
+  size_t ps_pieces = 0, ps_winners = 0, ps_states = 0;
+  std::vector<hipEvent_t> pl_events;
+  std::vector<int> pl_event_stage;
+  std::vector<char> pl_event_done;
+  int pl_chunk = 0;   // topay_plan_test_chunk: calls per front-end launch, 0 = the constant
+  double pl_stage_ms[8] = {0};
   DevBuf paths, path_off, path_len, bvel, bacc, scratch;
   DevBuf N, s1_past, map_id, head, tail, start_xy, goal_xy, init_xy, x0;
   DevBuf x, work, hist_s, hist_y, hist_ys, hist_alpha, lu;
@@ -520,8 +532,11 @@ void topay_destroy(topay_ctx* c) {
                     &c->map_id, &c->head, &c->tail, &c->start_xy, &c->goal_xy, &c->init_xy, &c->x0, &c->x, &c->work,
                     &c->hist_s, &c->hist_y, &c->hist_ys, &c->hist_alpha, &c->lu, &c->poff, &c->noff, &c->group_id, &c->group_tau, &c->interrupted, &c->success, &c->cost, &c->stats,
                     &c->xyerr, &c->coef, &c->T, &c->knots, &c->alm, &c->fout, &c->order, &c->trace, &c->elapsed, &c->startus, &c->hwid, &c->sbuf, &c->mstash, &c->feas_cseq, &c->feas_tk, &c->feas_report, &c->feas_flags, &c->edt_occ, &c->edt_tmp1,
-                    &c->edt_tmp2, &c->edt_v, &c->edt_z, &c->edt_out2, &c->edt_out3, &c->pb_io, &c->qnext, &c->mc_i, &c->mc_d, &c->mc_k, &c->mc_rs, &c->mc_in, &c->tp_i, &c->tp_d, &c->tp_raw, &c->tp_pts, &c->tp_io};
+                    &c->edt_tmp2, &c->edt_v, &c->edt_z, &c->edt_out2, &c->edt_out3, &c->pb_io, &c->qnext, &c->mc_i, &c->mc_d, &c->mc_k, &c->mc_rs, &c->mc_in, &c->tp_i, &c->tp_d, &c->tp_raw, &c->tp_pts, &c->tp_io,
+                    &c->pl_raw, &c->pl_jps_io, &c->pl_io, &c->pl_tab, &c->pl_mc, &c->pl_paths, &c->pl_bvel, &c->pl_sel, &c->pl_win, &c->ps_dur, &c->ps_coef,
+                    &c->ps_kn, &c->ps_front};
   for (DevBuf* b : bufs) b->release();
+  for (hipEvent_t e : c->pl_events) (void)hipEventDestroy(e);
   for (int i = 0; i < TOPAY_MAX_MAPS; i++) { c->map2d[i].release(); c->map3d[i].release(); c->map2d_inf[i].release(); c->map2d_crit[i].release(); }
   for (auto& a : c->map_arenas) a.buf.release();
   for (int k = 0; k < topay_ctx::NBUCKET; k++) {
@@ -896,8 +911,13 @@ topay_status topay_get_map(topay_ctx* c, int map_id, double* esdf2d, double* esd
   return TOPAY_OK;
 }
 
-topay_status topay_set_init_traj(topay_ctx* c, int batch, const int* path_len, const double* init_paths,
-                                 const double* boundary_vel, const double* boundary_acc, const int* map_ids) {
+}  // extern "C"
+
+// topay_set_init_traj with the init paths and the boundary velocities where `kind` says they are: in host memory (the
+// public entry) or already on the device (topay_plan_calls: the whole-body paths the search left there).  Lengths and map
+// slots are host data either way: they size the workspace.
+static topay_status set_init_traj_impl(topay_ctx* c, int batch, const int* path_len, const double* init_paths, const double* boundary_vel,
+                                       const double* boundary_acc, const int* map_ids, hipMemcpyKind kind) {
   if (!c || batch <= 0 || !path_len || !init_paths) return TOPAY_ERR_INVALID_ARG;
   HIPCHK(hipSetDevice(c->device));
   if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }   // inputs of a solve in flight stay untouched
@@ -937,11 +957,11 @@ topay_status topay_set_init_traj(topay_ctx* c, int batch, const int* path_len, c
   ENS(init_xy, (size_t)batch * 2 * TOPAY_MAX_N * 8);
   ENS(x0, (size_t)batch * (10 * TOPAY_MAX_N - 8) * 8);
   ENS(order, (size_t)batch * 4);
-  HIPCHK(memcpy_sync(c, c->paths.p, init_paths, tot * 10 * 8, hipMemcpyHostToDevice));
+  HIPCHK(memcpy_sync(c, c->paths.p, init_paths, tot * 10 * 8, kind));
   HIPCHK(memcpy_sync(c, c->path_off.p, off.data(), (size_t)(batch + 1) * 8, hipMemcpyHostToDevice));
   HIPCHK(memcpy_sync(c, c->path_len.p, path_len, (size_t)batch * 4, hipMemcpyHostToDevice));
   HIPCHK(memcpy_sync(c, c->map_id.p, mids.data(), (size_t)batch * 4, hipMemcpyHostToDevice));
-  if (boundary_vel) HIPCHK(memcpy_sync(c, c->bvel.p, boundary_vel, (size_t)batch * 20 * 8, hipMemcpyHostToDevice));
+  if (boundary_vel) HIPCHK(memcpy_sync(c, c->bvel.p, boundary_vel, (size_t)batch * 20 * 8, kind));
   else HIPCHK(hipMemsetAsync(c->bvel.p, 0, (size_t)batch * 20 * 8, c->stream));
   if (boundary_acc) HIPCHK(memcpy_sync(c, c->bacc.p, boundary_acc, (size_t)batch * 20 * 8, hipMemcpyHostToDevice));
   else HIPCHK(hipMemsetAsync(c->bacc.p, 0, (size_t)batch * 20 * 8, c->stream));
@@ -1060,6 +1080,13 @@ topay_status topay_set_init_traj(topay_ctx* c, int batch, const int* path_len, c
   HIPCHK(hipMemsetAsync(c->stats.p, 0, (size_t)batch * 32, c->stream));
   c->have_traj = true;
   return TOPAY_OK;
+}
+
+extern "C" {
+
+topay_status topay_set_init_traj(topay_ctx* c, int batch, const int* path_len, const double* init_paths,
+                                 const double* boundary_vel, const double* boundary_acc, const int* map_ids) {
+  return set_init_traj_impl(c, batch, path_len, init_paths, boundary_vel, boundary_acc, map_ids, hipMemcpyHostToDevice);
 }
 
 topay_status topay_reset(topay_ctx* c) {
@@ -1629,6 +1656,19 @@ topay_status topay_whole_body_collision(topay_ctx* c, int map_id, int n, const d
   return TOPAY_OK;
 }
 
+}  // extern "C"
+
+// getDensePath for n_paths raw paths that are on the device, results left there (the public entry and topay_plan_calls).
+static topay_status dense_launch(topay_ctx* c, int n_paths, const double* d_raw, const long long* d_off, const int* d_len, double step_size,
+                                 const double* d_syaw, const double* d_eyaw, double v_max, double w_max, int cap_per_path, double* d_out, int* d_olen) {
+  hipLaunchKernelGGL(k_dense_path, dim3((n_paths + 63) / 64), dim3(64), 0, c->stream, n_paths, d_raw, d_off, d_len, step_size, d_syaw, d_eyaw, v_max,
+                     w_max, cap_per_path, d_out, d_olen);
+  HIPCHK(hipGetLastError());
+  return TOPAY_OK;
+}
+
+extern "C" {
+
 // GraphSearch::getDensePath (graph_search.cpp:119-176) for n_paths raw 2-D paths at once.
 topay_status topay_dense_path(topay_ctx* c, int n_paths, const int* raw_len, const double* raw_xy, double step_size, const double* start_yaw,
                               const double* end_yaw, double v_max, double w_max, int cap_per_path, int* out_len, double* out) {
@@ -1652,10 +1692,12 @@ topay_status topay_dense_path(topay_ctx* c, int n_paths, const int* raw_len, con
   HIPCHK(hipMemcpyAsync(d_len.p, raw_len, (size_t)n_paths * 4, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(d_yaw.p, start_yaw, (size_t)n_paths * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(d_yaw.as<double>() + n_paths, end_yaw, (size_t)n_paths * 8, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(k_dense_path, dim3((n_paths + 63) / 64), dim3(64), 0, c->stream, n_paths, (const double*)d_raw.as<double>(),
-                     (const long long*)d_off.as<long long>(), (const int*)d_len.as<int>(), step_size, (const double*)d_yaw.as<double>(),
-                     (const double*)(d_yaw.as<double>() + n_paths), v_max, w_max, cap_per_path, d_out.as<double>(), d_olen.as<int>());
-  HIPCHK(hipGetLastError());
+  if ((s = dense_launch(c, n_paths, d_raw.as<double>(), d_off.as<long long>(), d_len.as<int>(), step_size, d_yaw.as<double>(),
+                        d_yaw.as<double>() + n_paths, v_max, w_max, cap_per_path, d_out.as<double>(), d_olen.as<int>())) != TOPAY_OK) {
+    DevBuf* fb[] = {&d_raw, &d_off, &d_len, &d_yaw, &d_out, &d_olen};
+    for (DevBuf* b : fb) b->release();
+    return s;
+  }
   HIPCHK(hipMemcpyAsync(out_len, d_olen.p, (size_t)n_paths * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipMemcpyAsync(out, d_out.p, (size_t)n_paths * cap_per_path * 32, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -1733,10 +1775,15 @@ topay_status topay_params_from_yaml(const char* path_or_text, topay_params_t* pa
   return TOPAY_OK;
 }
 
-topay_status topay_plan2d_jps(topay_ctx* c, int n, const int* map_ids, const double* start_xy, const double* end_xy, double threshold,
-                              int cap_points, int* out_len, double* out_xy, int* stats) {
-  if (!c || n < 0 || cap_points < 2 || (n > 0 && (!start_xy || !end_xy || !out_len || !out_xy))) return TOPAY_ERR_INVALID_ARG;
-  if (n == 0) return TOPAY_OK;
+}  // extern "C"
+
+// Device results of a stage launcher: where the launch left them (valid until the buffers are sized again).
+struct JpsDev { int* len; double* out; int* stats; };
+
+// plan2dJPS for n host-side (start, goal) pairs; the results stay on the device in `io` (the public entry copies them
+// back, topay_plan_calls hands them on).  out_ext: write the paths there (n x cap_points x 2) instead of into `io`.
+static topay_status jps_impl(topay_ctx* c, int n, const int* map_ids, const double* start_xy, const double* end_xy, double threshold, int cap_points,
+                             DevBuf& io, double* out_ext, JpsDev* dev, hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr) {
   std::vector<int> mid((size_t)n, 0);
   long long ncell = 0;
   for (int p = 0; p < n; p++) {
@@ -1750,15 +1797,17 @@ topay_status topay_plan2d_jps(topay_ctx* c, int n, const int* map_ids, const dou
   // chunks of at most 2 GB of it
   const size_t per = (size_t)ncell * 21;
   const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)2 << 30) / std::max<size_t>(per, 1)));
-  ScopedDevBuf ws, io;
+  ScopedDevBuf ws;
   topay_status s;
   if ((s = ws.ensure((size_t)chunk * per + 64)) != TOPAY_OK) return s;
-  const size_t io_d = (size_t)n * 4 + (size_t)n * cap_points * 2, io_i = (size_t)n * 4;
+  const size_t out_d = out_ext ? 0 : (size_t)n * cap_points * 2;
+  const size_t io_d = (size_t)n * 4 + out_d, io_i = (size_t)n * 4;
   if ((s = io.ensure(io_d * 8 + io_i * 4)) != TOPAY_OK) { ws.release(); return s; }
   double* d_start = io.as<double>();
   double* d_end = d_start + 2 * (size_t)n;
-  double* d_out = d_end + 2 * (size_t)n;
-  int* d_mid = (int*)(d_out + (size_t)n * cap_points * 2);
+  double* d_own = d_end + 2 * (size_t)n;
+  double* d_out = out_ext ? out_ext : d_own;
+  int* d_mid = (int*)(d_own + out_d);
   int* d_len = d_mid + n;
   int* d_stats = d_len + n;
   HIPCHK(hipMemcpyAsync(d_start, start_xy, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
@@ -1772,6 +1821,7 @@ topay_status topay_plan2d_jps(topay_ctx* c, int n, const int* map_ids, const dou
   B.heap = B.hpos + (size_t)chunk * ncell;
   B.flag = (unsigned char*)(B.heap + (size_t)chunk * ncell);
   B.out_len = d_len; B.out_xy = d_out; B.stats = d_stats;
+  if (ev_begin) HIPCHK(hipEventRecord(ev_begin, c->stream));
   for (int i0 = 0; i0 < n; i0 += chunk) {
     B.inst0 = i0;
     B.n = std::min(chunk, n - i0);
@@ -1779,12 +1829,26 @@ topay_status topay_plan2d_jps(topay_ctx* c, int n, const int* map_ids, const dou
     hipLaunchKernelGGL(topay::k_jps, dim3((unsigned)B.n), dim3(64), 0, c->stream, (const DevMap*)c->dmaps.p, B);   // one wave per search
     HIPCHK(hipGetLastError());
   }
-  HIPCHK(hipMemcpyAsync(out_len, d_len, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(out_xy, d_out, (size_t)n * cap_points * 16, hipMemcpyDeviceToHost, c->stream));
-  if (stats) HIPCHK(hipMemcpyAsync(stats, d_stats, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+  if (ev_end) HIPCHK(hipEventRecord(ev_end, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));   // (the search state is released on the way out)
+  dev->len = d_len; dev->out = d_out; dev->stats = d_stats;
+  return TOPAY_OK;
+}
+
+extern "C" {
+
+topay_status topay_plan2d_jps(topay_ctx* c, int n, const int* map_ids, const double* start_xy, const double* end_xy, double threshold,
+                              int cap_points, int* out_len, double* out_xy, int* stats) {
+  if (!c || n < 0 || cap_points < 2 || (n > 0 && (!start_xy || !end_xy || !out_len || !out_xy))) return TOPAY_ERR_INVALID_ARG;
+  if (n == 0) return TOPAY_OK;
+  ScopedDevBuf io;
+  JpsDev d;
+  topay_status s = jps_impl(c, n, map_ids, start_xy, end_xy, threshold, cap_points, io, nullptr, &d);
+  if (s != TOPAY_OK) return s;
+  HIPCHK(hipMemcpyAsync(out_len, d.len, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(out_xy, d.out, (size_t)n * cap_points * 16, hipMemcpyDeviceToHost, c->stream));
+  if (stats) HIPCHK(hipMemcpyAsync(stats, d.stats, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  ws.release();
-  io.release();
   return TOPAY_OK;
 }
 
@@ -1824,10 +1888,17 @@ struct TopoLayout {
   }
 };
 
-topay_status topay_topo_paths(topay_ctx* c, int n, const int* map_ids, const double* start_xy, const double* end_xy, const int* critical,
-                              const topay_topo_params_t* prm, unsigned long long first_instance, int cap_paths, int cap_points, int* n_paths,
-                              int* path_len, double* path_xy, int* stats) {
-  if (!c || n <= 0 || !start_xy || !end_xy || !n_paths || !path_len || !path_xy || cap_points < 2) return TOPAY_ERR_INVALID_ARG;
+}  // extern "C"
+
+struct TopoDev { int* n_paths; int* path_len; double* path_xy; int* stats; };
+
+// findTopoPaths for n host-side queries; the results stay on the device (in the context's tp_io, or the paths at out_ext:
+// n x cap_paths x cap_points x 2).  inst (optional, host): the instance number of every query instead of first_instance +
+// query.  The public entry copies the results back and clears the unwritten part of the paths first (clear_out).
+static topay_status topo_impl(topay_ctx* c, int n, const int* map_ids, const double* start_xy, const double* end_xy, const int* critical,
+                              const topay_topo_params_t* prm, unsigned long long first_instance, const unsigned long long* inst, int cap_paths,
+                              int cap_points, double* out_ext, bool clear_out, TopoDev* dev, hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr) {
+  if (!c || n <= 0 || !start_xy || !end_xy || cap_points < 2) return TOPAY_ERR_INVALID_ARG;
   topay_topo_params_t P;
   if (prm) P = *prm;
   else topay_topo_default_params(&P);
@@ -1860,12 +1931,15 @@ topay_status topay_topo_paths(topay_ctx* c, int n, const int* map_ids, const dou
       (s = c->tp_raw.ensure(N * P.max_raw_path * TOPAY_TOPO_RAWLEN * 2)) != TOPAY_OK ||
       (s = c->tp_pts.ensure(N * (size_t)nbuf * (size_t)pt_cap * 16)) != TOPAY_OK)
     return s;
-  const size_t io_d = N * 4 + N * (size_t)cap_paths * cap_points * 2, io_i = N * (3 + (size_t)cap_paths + 8);
+  const size_t out_d = out_ext ? 0 : N * (size_t)cap_paths * cap_points * 2;
+  const size_t io_d = N * 4 + out_d + N, io_i = N * (3 + (size_t)cap_paths + 8);
   if ((s = c->tp_io.ensure(io_d * 8 + io_i * 4)) != TOPAY_OK) return s;
   double* d_start = c->tp_io.as<double>();
   double* d_end = d_start + 2 * N;
-  double* d_out = d_end + 2 * N;
-  int* d_mid = (int*)(d_out + N * (size_t)cap_paths * cap_points * 2);
+  unsigned long long* d_inst = (unsigned long long*)(d_end + 2 * N);
+  double* d_own = (double*)(d_inst + N);
+  double* d_out = out_ext ? out_ext : d_own;
+  int* d_mid = (int*)(d_own + out_d);
   int* d_crit = d_mid + N;
   int* d_np = d_crit + N;
   int* d_len = d_np + N;
@@ -1874,9 +1948,11 @@ topay_status topay_topo_paths(topay_ctx* c, int n, const int* map_ids, const dou
   HIPCHK(hipMemcpyAsync(d_end, end_xy, N * 16, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(d_mid, mid.data(), N * 4, hipMemcpyHostToDevice, c->stream));
   if (critical) HIPCHK(hipMemcpyAsync(d_crit, critical, N * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemsetAsync(d_out, 0, N * (size_t)cap_paths * cap_points * 16, c->stream));
+  if (inst) HIPCHK(hipMemcpyAsync(d_inst, inst, N * 8, hipMemcpyHostToDevice, c->stream));
+  if (clear_out) HIPCHK(hipMemsetAsync(d_out, 0, N * (size_t)cap_paths * cap_points * 16, c->stream));
   topay::TopoBatch B;
   B.n = n; B.cap_paths = cap_paths; B.cap_points = cap_points; B.pt_cap = pt_cap; B.nbuf = nbuf; B.inst_base = first_instance;
+  B.inst = inst ? d_inst : nullptr;
   B.map_id = d_mid; B.start = d_start; B.end = d_end; B.critical = critical ? d_crit : nullptr;
   B.P.sample_inflate_x = P.sample_inflate_x; B.P.sample_inflate_y = P.sample_inflate_y; B.P.clearance = P.clearance;
   B.P.ratio_to_short = P.ratio_to_short; B.P.max_sample_num = P.max_sample_num; B.P.max_raw_path = P.max_raw_path;
@@ -1889,20 +1965,37 @@ topay_status topay_topo_paths(topay_ctx* c, int n, const int* map_ids, const dou
   B.pts = c->tp_pts.as<double>();
   B.n_paths = d_np; B.path_len = d_len; B.path_xy = d_out; B.stats = d_stats;
   c->tp_n = 0;
-  HIPCHK(hipEventRecord(c->ev0, c->stream));
+  HIPCHK(hipEventRecord(ev_begin ? ev_begin : c->ev0, c->stream));
   hipLaunchKernelGGL(topay::k_topo, dim3((unsigned)n), dim3(64), 0, c->stream, (const DevMap*)c->dmaps.p, B);   // one wave per query
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev1, c->stream));
-  HIPCHK(hipMemcpyAsync(n_paths, d_np, N * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(path_len, d_len, N * cap_paths * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(path_xy, d_out, N * (size_t)cap_paths * cap_points * 16, hipMemcpyDeviceToHost, c->stream));
-  if (stats) HIPCHK(hipMemcpyAsync(stats, d_stats, N * 32, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipEventRecord(ev_end ? ev_end : c->ev1, c->stream));
+  dev->n_paths = d_np; dev->path_len = d_len; dev->path_xy = d_out; dev->stats = d_stats;
+  c->tp_n = n; c->tp_pt_cap = pt_cap; c->tp_nbuf = nbuf; c->tp_P = P;   // (valid once the stream has been waited for)
+  return TOPAY_OK;
+}
+
+extern "C" {
+
+topay_status topay_topo_paths(topay_ctx* c, int n, const int* map_ids, const double* start_xy, const double* end_xy, const int* critical,
+                              const topay_topo_params_t* prm, unsigned long long first_instance, int cap_paths, int cap_points, int* n_paths,
+                              int* path_len, double* path_xy, int* stats) {
+  if (!c || n <= 0 || !start_xy || !end_xy || !n_paths || !path_len || !path_xy || cap_points < 2) return TOPAY_ERR_INVALID_ARG;
+  TopoDev d;
+  const size_t N = (size_t)n;
+  topay_status s = topo_impl(c, n, map_ids, start_xy, end_xy, critical, prm, first_instance, nullptr, cap_paths, cap_points, nullptr, true, &d);
+  if (s != TOPAY_OK) return s;
+  const int keep_n = c->tp_n;
+  c->tp_n = 0;   // (the graphs are readable once the results have arrived)
+  HIPCHK(hipMemcpyAsync(n_paths, d.n_paths, N * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(path_len, d.path_len, N * cap_paths * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(path_xy, d.path_xy, N * (size_t)cap_paths * cap_points * 16, hipMemcpyDeviceToHost, c->stream));
+  if (stats) HIPCHK(hipMemcpyAsync(stats, d.stats, N * 32, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   float ms = 0.f;
   HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
   c->last_ms = ms;
   c->last_launches = 1;
-  c->tp_n = n; c->tp_pt_cap = pt_cap; c->tp_nbuf = nbuf; c->tp_P = P;
+  c->tp_n = keep_n;
   return TOPAY_OK;
 }
 
@@ -2007,6 +2100,50 @@ void topay_mcrrt_default_params(topay_mcrrt_params_t* p) {
   p->seed = 42;
 }
 
+}  // extern "C"
+
+// Inputs and results of one launch of the joint-space search, all on the device.
+struct McIo {
+  const long long* off; const int* len; const double* car; const double* start; const double* end; const int* mid;
+  const unsigned long long* inst;   // instance numbers, or null: first_instance + search
+  int* wb_len; double* wb; int* stats; double* cmax;
+};
+
+// MCRRTs::plan for n searches whose inputs are on the device; sizes the node tables, leaves the results on the device.
+static topay_status mcrrt_launch(topay_ctx* c, int n, const topay_mcrrt_params_t& P, unsigned long long first_instance, int cap_per_path, const McIo& io) {
+  const size_t nn = (size_t)n * P.node_cap;
+  topay_status s;
+  if ((s = c->mc_i.ensure(nn * 5 * 4)) != TOPAY_OK || (s = c->mc_d.ensure(nn * 8 * 8)) != TOPAY_OK ||
+      (s = c->mc_k.ensure(nn * TOPAY_MC_KEYW * 8)) != TOPAY_OK || (s = c->mc_rs.ensure((size_t)n * 2 * cap_per_path * sizeof(topay::RsPath))) != TOPAY_OK)
+    return s;
+  HIPCHK(hipMemsetAsync(io.wb, 0, (size_t)n * cap_per_path * 10 * 8, c->stream));
+  HIPCHK(hipMemsetAsync(io.cmax, 0, (size_t)n * 8, c->stream));
+  topay_status ps = push_params(c);
+  if (ps != TOPAY_OK) return ps;
+  topay::McrrtBatch B;
+  B.n = n; B.layer_cap = cap_per_path; B.inst_base = first_instance; B.inst = io.inst;
+  B.map_id = io.mid; B.car_off = io.off; B.car_len = io.len; B.car = io.car; B.start = io.start; B.end = io.end;
+  B.P.goal_sample_rate = P.goal_sample_rate; B.P.check_colli_res = P.check_colli_res; B.P.rs_rho = P.rs_turning_radius;
+  B.P.max_iter = P.max_iter; B.P.max_sample_tries = P.max_sample_tries; B.P.node_cap = P.node_cap; B.P.reserved = 0; B.P.seed = P.seed;
+  int* ni = c->mc_i.as<int>();
+  B.nd_layer = ni; B.nd_state = ni + nn; B.nd_parent = ni + 2 * nn; B.nd_nchild = ni + 3 * nn; B.nd_mark = ni + 4 * nn;
+  B.nd_cost = c->mc_d.as<double>(); B.nd_q = B.nd_cost + nn; B.nd_key = c->mc_k.as<unsigned long long>();
+  B.rs = (topay::RsPath*)c->mc_rs.p;
+  B.wb_len = io.wb_len; B.wb = io.wb; B.stats = io.stats; B.cmax = io.cmax;
+  c->mc_n = 0;
+  hipLaunchKernelGGL(topay::k_mcrrt, dim3((unsigned)n), dim3(64), 0, c->stream, (const DevMap*)c->dmaps.p, B);
+  HIPCHK(hipGetLastError());
+  c->mc_n = n;
+  c->mc_node_cap = P.node_cap;
+  return TOPAY_OK;
+}
+
+static bool mcrrt_params_ok(const topay_mcrrt_params_t& P) {
+  return !(P.max_iter < 0 || P.max_sample_tries < 1 || P.node_cap < 2 || !(P.check_colli_res > 0.0) || !(P.rs_turning_radius > 0.0));
+}
+
+extern "C" {
+
 topay_status topay_mcrrt_plan(topay_ctx* c, int n, const int* map_ids, const int* path_len, const double* car_paths, const double* start,
                               const double* end, const topay_mcrrt_params_t* prm, unsigned long long first_instance, int cap_per_path,
                               int* wb_len, double* wb_path, int* stats, double* c_max) {
@@ -2014,7 +2151,7 @@ topay_status topay_mcrrt_plan(topay_ctx* c, int n, const int* map_ids, const int
   topay_mcrrt_params_t P;
   if (prm) P = *prm;
   else topay_mcrrt_default_params(&P);
-  if (P.max_iter < 0 || P.max_sample_tries < 1 || P.node_cap < 2 || !(P.check_colli_res > 0.0) || !(P.rs_turning_radius > 0.0)) return TOPAY_ERR_INVALID_ARG;
+  if (!mcrrt_params_ok(P)) return TOPAY_ERR_INVALID_ARG;
   if (n == 0) return TOPAY_OK;
   std::vector<long long> off((size_t)n + 1, 0);
   std::vector<int> mid((size_t)n, 0);
@@ -2030,14 +2167,11 @@ topay_status topay_mcrrt_plan(topay_ctx* c, int n, const int* map_ids, const int
     if (!c->have_map[mid[p]]) return TOPAY_ERR_NO_MAP;
   }
   HIPCHK(hipSetDevice(c->device));
-  const size_t nn = (size_t)n * P.node_cap, tot = (size_t)off[n];
+  const size_t tot = (size_t)off[n];
   topay_status s;
   // inputs: map ids, lengths (int), offsets (i64), chassis paths, start, end (f64); outputs: wb_len, stats (int), wb, c_max (f64)
   const size_t in_i = (size_t)n * 2 + (size_t)n * 9, in_l = (size_t)n + 1, in_d = 4 * tot + 20 * (size_t)n + (size_t)n * cap_per_path * 10 + n;
-  if ((s = c->mc_in.ensure(in_l * 8 + in_d * 8 + in_i * 4)) != TOPAY_OK || (s = c->mc_i.ensure(nn * 5 * 4)) != TOPAY_OK ||
-      (s = c->mc_d.ensure(nn * 8 * 8)) != TOPAY_OK || (s = c->mc_k.ensure(nn * TOPAY_MC_KEYW * 8)) != TOPAY_OK ||
-      (s = c->mc_rs.ensure((size_t)n * 2 * cap_per_path * sizeof(topay::RsPath))) != TOPAY_OK)
-    return s;
+  if ((s = c->mc_in.ensure(in_l * 8 + in_d * 8 + in_i * 4)) != TOPAY_OK) return s;
   long long* d_off = c->mc_in.as<long long>();
   double* d_car = (double*)(d_off + in_l);
   double* d_start = d_car + 4 * tot;
@@ -2054,28 +2188,15 @@ topay_status topay_mcrrt_plan(topay_ctx* c, int n, const int* map_ids, const int
   HIPCHK(hipMemcpyAsync(d_end, end, 10 * (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(d_mid, mid.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(d_len, path_len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemsetAsync(d_wb, 0, ((size_t)n * cap_per_path * 10 + n) * 8, c->stream));
-  topay_status ps = push_params(c);
-  if (ps != TOPAY_OK) return ps;
-  topay::McrrtBatch B;
-  B.n = n; B.layer_cap = cap_per_path; B.inst_base = first_instance;
-  B.map_id = d_mid; B.car_off = d_off; B.car_len = d_len; B.car = d_car; B.start = d_start; B.end = d_end;
-  B.P.goal_sample_rate = P.goal_sample_rate; B.P.check_colli_res = P.check_colli_res; B.P.rs_rho = P.rs_turning_radius;
-  B.P.max_iter = P.max_iter; B.P.max_sample_tries = P.max_sample_tries; B.P.node_cap = P.node_cap; B.P.reserved = 0; B.P.seed = P.seed;
-  int* ni = c->mc_i.as<int>();
-  B.nd_layer = ni; B.nd_state = ni + nn; B.nd_parent = ni + 2 * nn; B.nd_nchild = ni + 3 * nn; B.nd_mark = ni + 4 * nn;
-  B.nd_cost = c->mc_d.as<double>(); B.nd_q = B.nd_cost + nn; B.nd_key = c->mc_k.as<unsigned long long>();
-  B.rs = (topay::RsPath*)c->mc_rs.p;
-  B.wb_len = d_wlen; B.wb = d_wb; B.stats = d_stats; B.cmax = d_cmax;
-  hipLaunchKernelGGL(topay::k_mcrrt, dim3((unsigned)n), dim3(64), 0, c->stream, (const DevMap*)c->dmaps.p, B);
-  HIPCHK(hipGetLastError());
+  McIo io;
+  io.off = d_off; io.len = d_len; io.car = d_car; io.start = d_start; io.end = d_end; io.mid = d_mid; io.inst = nullptr;
+  io.wb_len = d_wlen; io.wb = d_wb; io.stats = d_stats; io.cmax = d_cmax;
+  if ((s = mcrrt_launch(c, n, P, first_instance, cap_per_path, io)) != TOPAY_OK) return s;
   HIPCHK(hipMemcpyAsync(wb_len, d_wlen, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipMemcpyAsync(wb_path, d_wb, (size_t)n * cap_per_path * 80, hipMemcpyDeviceToHost, c->stream));
   if (stats) HIPCHK(hipMemcpyAsync(stats, d_stats, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
   if (c_max) HIPCHK(hipMemcpyAsync(c_max, d_cmax, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  c->mc_n = n;
-  c->mc_node_cap = P.node_cap;
   return TOPAY_OK;
 }
 
@@ -2670,6 +2791,475 @@ topay_status topay_last_kernel_ms(topay_ctx* c, double* ms, int* launches) {
 topay_status topay_last_helper_launches(topay_ctx* c, int* n) {
   if (!c || !n) return TOPAY_ERR_INVALID_ARG;
   *n = c->last_helper_launches;
+  return TOPAY_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// topay_plan_calls: Planner::planMomaParallel (planner.cpp:792-1061) with every hand-off on the device (topay_plan.h)
+// ---------------------------------------------------------------------------------------------------------------------
+// Calls per launch of the front-end stages (roadmap, JPS, dense paths, search).  The instance numbers of the draws are
+// those of the call, so results do not depend on it; it bounds the roadmap's 1.1 MB per query.
+#ifndef TOPAY_PLAN_CHUNK
+#define TOPAY_PLAN_CHUNK 1024
+#endif
+static const int kPlanChunk = TOPAY_PLAN_CHUNK;
+static const int kPlanDenseCap = 256;   // entries per dense path kept (the search takes at most 255 layers)
+static const int kPlanJpsCap = 512;     // points per JPS path kept
+
+// A device buffer that keeps its first `used` bytes when it has to grow.
+static topay_status grow_keep(topay_ctx* c, DevBuf& b, size_t need, size_t used) {
+  if (need <= b.bytes) return TOPAY_OK;
+  DevBuf nb;
+  topay_status s = nb.ensure(std::max(need, 2 * b.bytes));
+  if (s != TOPAY_OK) return s;
+  if (used > 0 && b.p) {
+    hipError_t e = memcpy_sync(c, nb.p, b.p, used, hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) { nb.release(); set_err(std::string("grow_keep: ") + hipGetErrorString(e)); return TOPAY_ERR_NO_DEVICE; }
+  }
+  b.release();
+  b = nb;
+  return TOPAY_OK;
+}
+
+// Device time of one stage: a pair of events around its launches on the context's stream, read once the call has finished.
+// Only pairs whose end has been recorded in THIS call are read (an error return between begin and end leaves none behind).
+struct PlanClock {
+  topay_ctx* c;
+  size_t used = 0;
+  explicit PlanClock(topay_ctx* c_) : c(c_) {}
+  int reserve(int stage) {   // a pair for a launcher that records the events itself, around its kernels only; then done(id)
+    if (used + 2 > c->pl_events.size()) {
+      hipEvent_t a = nullptr, b = nullptr;
+      if (hipEventCreate(&a) != hipSuccess) return -1;
+      if (hipEventCreate(&b) != hipSuccess) { (void)hipEventDestroy(a); return -1; }
+      c->pl_events.push_back(a);
+      c->pl_events.push_back(b);
+    }
+    c->pl_event_stage.resize(c->pl_events.size() / 2);
+    c->pl_event_done.resize(c->pl_events.size() / 2);
+    const int id = (int)(used / 2);
+    c->pl_event_stage[id] = stage;
+    c->pl_event_done[id] = 0;
+    used += 2;
+    return id;
+  }
+  hipEvent_t ev(int id, int which) { return id < 0 ? nullptr : c->pl_events[2 * (size_t)id + which]; }
+  void done(int id) { if (id >= 0) c->pl_event_done[id] = 1; }
+  int begin(int stage) {
+    const int id = reserve(stage);
+    if (id >= 0) (void)hipEventRecord(ev(id, 0), c->stream);
+    return id;
+  }
+  void end(int id) {
+    if (id >= 0 && hipEventRecord(ev(id, 1), c->stream) == hipSuccess) done(id);
+  }
+  void collect() {
+    (void)hipStreamSynchronize(c->stream);
+    for (size_t i = 0; i + 1 < used; i += 2) {
+      float ms = 0.f;
+      if (c->pl_event_done[i / 2] && hipEventElapsedTime(&ms, c->pl_events[i], c->pl_events[i + 1]) == hipSuccess)
+        c->pl_stage_ms[c->pl_event_stage[i / 2]] += ms;
+    }
+  }
+};
+
+struct PlanTry {   // the survivors of one try, over all front-end launches: the batch that is solved
+  std::vector<int> call, k, len, mid;
+  std::vector<long long> off{0};
+};
+
+// One try (t = 0 plain, 1 critical) for the calls `act`: front-end in launches of kPlanChunk calls, one solve, winners
+// into the store.  Fills the calls' rows of result / cand (n x 2 x 8 x 4) / wcd.
+static topay_status plan_try(topay_ctx* c, int t, const std::vector<int>& act, const std::vector<int>& mids, const double* start, const double* end,
+                             const double* start_v, const topay_plan_params_t& P, unsigned long long first_call, int* result, int* cand,
+                             double* wcd, PlanClock& clk) {
+  topay_status s;
+  PlanTry T;
+  const int cap_paths = P.topo.reserve_num;
+  const size_t chunk = (size_t)(c->pl_chunk > 0 ? c->pl_chunk : kPlanChunk);
+  for (size_t a0 = 0; a0 < act.size(); a0 += chunk) {
+    const int nc = (int)std::min<size_t>(chunk, act.size() - a0);
+    const size_t NC = (size_t)nc, NS = NC * TOPAY_PLAN_MAX_CAND;
+    // ---- the launch's calls: inputs of the caller, gathered on the host
+    std::vector<double> sxy(2 * NC), exy(2 * NC), st10(10 * NC), en10(10 * NC), sv10(10 * NC, 0.0);
+    std::vector<int> cmid(NC), crit(NC, t);
+    std::vector<unsigned long long> inst(NC), call_no(NC);
+    int cap_points = 2;
+    for (int q = 0; q < nc; q++) {
+      const int p = act[a0 + q];
+      memcpy(&st10[10 * (size_t)q], start + 10 * (size_t)p, 80);
+      memcpy(&en10[10 * (size_t)q], end + 10 * (size_t)p, 80);
+      if (start_v) memcpy(&sv10[10 * (size_t)q], start_v + 10 * (size_t)p, 80);
+      sxy[2 * (size_t)q] = start[10 * (size_t)p]; sxy[2 * (size_t)q + 1] = start[10 * (size_t)p + 1];
+      exy[2 * (size_t)q] = end[10 * (size_t)p]; exy[2 * (size_t)q + 1] = end[10 * (size_t)p + 1];
+      cmid[q] = mids[p];
+      call_no[q] = first_call + (unsigned long long)p;
+      inst[q] = 2ull * call_no[q] + (unsigned long long)t;
+      const DevMap& m = c->hmaps[cmid[q]];
+      cap_points = std::max(cap_points, topo_pt_cap(m.dims[0], m.dims[1]));   // no selected path has more points than its map's cap
+    }
+    const size_t topo_pts = NC * (size_t)cap_paths * cap_points;
+    if ((s = c->pl_raw.ensure((topo_pts + NC * kPlanJpsCap) * 16)) != TOPAY_OK) return s;
+    // calls: start | end | start_v (10 each), call numbers, map slots
+    if ((s = c->pl_io.ensure(NC * (30 * 8 + 8 + 4))) != TOPAY_OK) return s;
+    double* d_st = c->pl_io.as<double>();
+    double* d_en = d_st + 10 * NC;
+    double* d_sv = d_en + 10 * NC;
+    unsigned long long* d_callno = (unsigned long long*)(d_sv + 10 * NC);
+    int* d_cmid = (int*)(d_callno + NC);
+    HIPCHK(hipMemcpyAsync(d_st, st10.data(), NC * 80, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_en, en10.data(), NC * 80, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_sv, sv10.data(), NC * 80, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_callno, call_no.data(), NC * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_cmid, cmid.data(), NC * 4, hipMemcpyHostToDevice, c->stream));
+    // ---- roadmap, JPS
+    TopoDev td;
+    int id = clk.reserve(0);   // (the launchers record around their kernels: uploads, allocations and waits stay outside)
+    s = topo_impl(c, nc, cmid.data(), sxy.data(), exy.data(), crit.data(), &P.topo, 0, inst.data(), cap_paths, cap_points, c->pl_raw.as<double>(), false, &td,
+                  clk.ev(id, 0), clk.ev(id, 1));
+    if (s != TOPAY_OK) return s;
+    clk.done(id);
+    JpsDev jd;
+    jd.len = nullptr;
+    if (t == 0) {
+      id = clk.reserve(1);
+      s = jps_impl(c, nc, cmid.data(), sxy.data(), exy.data(), c->hp.chassis_colli_radius + P.jps_margin, kPlanJpsCap, c->pl_jps_io,
+                   c->pl_raw.as<double>() + 2 * topo_pts, &jd, clk.ev(id, 0), clk.ev(id, 1));
+      if (s != TOPAY_OK) return s;
+      clk.done(id);
+    }
+    // ---- candidate table, dense paths
+    const size_t tab_d = 2 * NS + NS /* raw_off */ + NS * kPlanDenseCap * 4, tab_i = NC + 2 * NS;
+    if ((s = c->pl_tab.ensure(tab_d * 8 + tab_i * 4)) != TOPAY_OK) return s;
+    double* d_syaw = c->pl_tab.as<double>();
+    double* d_eyaw = d_syaw + NS;
+    long long* d_rawoff = (long long*)(d_eyaw + NS);
+    double* d_dense = (double*)(d_rawoff + NS);
+    int* d_ncand = (int*)(d_dense + NS * kPlanDenseCap * 4);
+    int* d_rawlen = d_ncand + NC;
+    int* d_denselen = d_rawlen + NS;
+    topay::PlanCandArgs A;
+    A.n = nc; A.cap_paths = cap_paths; A.cap_points = cap_points; A.jps_cap = kPlanJpsCap; A.max_cand = P.max_candidates;
+    A.jps_base = (long long)topo_pts;
+    A.topo_np = td.n_paths; A.topo_len = td.path_len; A.jps_len = jd.len; A.start = d_st; A.end = d_en;
+    A.ncand = d_ncand; A.raw_off = d_rawoff; A.raw_len = d_rawlen; A.syaw = d_syaw; A.eyaw = d_eyaw;
+    id = clk.begin(2);
+    hipLaunchKernelGGL(topay::k_plan_candidates, dim3((nc + 63) / 64), dim3(64), 0, c->stream, A);
+    HIPCHK(hipGetLastError());
+    if ((s = dense_launch(c, (int)NS, c->pl_raw.as<double>(), d_rawoff, d_rawlen, P.dense_step, d_syaw, d_eyaw, c->hp.max_v, c->hp.max_w, kPlanDenseCap,
+                          d_dense, d_denselen)) != TOPAY_OK)
+      return s;
+    clk.end(id);
+    std::vector<int> ncand(NC), dlen(NS), tstat(NC * 8);
+    HIPCHK(hipMemcpyAsync(ncand.data(), d_ncand, NC * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(dlen.data(), d_denselen, NS * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(tstat.data(), td.stats, NC * 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::vector<int> sel;
+    int layer_cap = 2;
+    for (int q = 0; q < nc; q++) {
+      const int p = act[a0 + q];
+      int* r = result + 8 * (size_t)p;
+      r[1] = t;
+      r[2 + t] = std::abs(ncand[q]);
+      r[6] = tstat[8 * (size_t)q];
+      if (ncand[q] < 0) { r[0] = -3; continue; }
+      for (int k = 0; k < ncand[q]; k++) {
+        const int sl = q * TOPAY_PLAN_MAX_CAND + k;
+        sel.push_back(sl);
+        layer_cap = std::max(layer_cap, std::min(dlen[sl], 255));
+        if (cand) cand[(((size_t)p * 2 + t) * 8 + k) * 4] = topay::PLAN_SEARCH_FAILED;   // until it gets further
+      }
+    }
+    const int ni = (int)sel.size();
+    if (ni == 0) continue;
+    // ---- the search: hand-off kernel, k_mcrrt
+    const size_t NI = (size_t)ni;
+    const size_t mc_d = NI /* off */ + NI /* inst */ + 20 * NI + NI * layer_cap * 10 + NI, mc_i = NI * (1 + 1 + 1 + 1 + 8);
+    if ((s = c->pl_mc.ensure(mc_d * 8 + mc_i * 4)) != TOPAY_OK) return s;
+    long long* d_off = c->pl_mc.as<long long>();
+    unsigned long long* d_inst = (unsigned long long*)(d_off + NI);
+    double* d_s = (double*)(d_inst + NI);
+    double* d_e = d_s + 10 * NI;
+    double* d_wb = d_e + 10 * NI;
+    double* d_cmax = d_wb + NI * layer_cap * 10;
+    int* d_sel = (int*)(d_cmax + NI);
+    int* d_len = d_sel + NI;
+    int* d_mid = d_len + NI;
+    int* d_wlen = d_mid + NI;
+    int* d_mstat = d_wlen + NI;
+    HIPCHK(hipMemcpyAsync(d_sel, sel.data(), NI * 4, hipMemcpyHostToDevice, c->stream));
+    id = clk.begin(3);
+    hipLaunchKernelGGL(topay::k_plan_pack_search, dim3((ni + 63) / 64), dim3(64), 0, c->stream, ni, (const int*)d_sel, kPlanDenseCap, (const int*)d_denselen,
+                       (const double*)d_st, (const double*)d_en, (const int*)d_cmid, (const unsigned long long*)d_callno, t, d_off, d_len, d_s, d_e, d_mid,
+                       d_inst);
+    HIPCHK(hipGetLastError());
+    McIo io;
+    io.off = d_off; io.len = d_len; io.car = d_dense; io.start = d_s; io.end = d_e; io.mid = d_mid; io.inst = d_inst;
+    io.wb_len = d_wlen; io.wb = d_wb; io.stats = d_mstat; io.cmax = d_cmax;
+    if ((s = mcrrt_launch(c, ni, P.mcrrt, 0, layer_cap, io)) != TOPAY_OK) return s;
+    clk.end(id);
+    std::vector<int> wlen(NI), mstat(NI * 8);
+    HIPCHK(hipMemcpyAsync(wlen.data(), d_wlen, NI * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(mstat.data(), d_mstat, NI * 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::vector<int> src, src_call;
+    std::vector<long long> poff;
+    const int b0 = (int)T.call.size();
+    for (int i = 0; i < ni; i++) {
+      const int q = sel[i] / TOPAY_PLAN_MAX_CAND, k = sel[i] % TOPAY_PLAN_MAX_CAND, p = act[a0 + q];
+      if (cand) cand[(((size_t)p * 2 + t) * 8 + k) * 4 + 2] = mstat[8 * (size_t)i];
+      if (mstat[8 * (size_t)i] != 1 || wlen[i] < 2) continue;
+      src.push_back(i);
+      src_call.push_back(q);
+      poff.push_back(T.off.back());
+      T.call.push_back(p); T.k.push_back(k); T.len.push_back(wlen[i]); T.mid.push_back(mids[p]);
+      T.off.push_back(T.off.back() + wlen[i]);
+    }
+    const int nsv = (int)src.size();
+    if (nsv == 0) continue;
+    // ---- hand-off to the solver: ragged init paths and boundary velocities of the try, appended launch by launch
+    if ((s = grow_keep(c, c->pl_paths, (size_t)T.off.back() * 80, (size_t)poff[0] * 80)) != TOPAY_OK) return s;
+    if ((s = grow_keep(c, c->pl_bvel, T.call.size() * 160, (size_t)b0 * 160)) != TOPAY_OK) return s;
+    if ((s = c->pl_sel.ensure((size_t)nsv * 16)) != TOPAY_OK) return s;
+    long long* d_poff = c->pl_sel.as<long long>();
+    int* d_src = (int*)(d_poff + nsv);
+    int* d_srccall = d_src + nsv;
+    HIPCHK(hipMemcpyAsync(d_poff, poff.data(), (size_t)nsv * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_src, src.data(), (size_t)nsv * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_srccall, src_call.data(), (size_t)nsv * 4, hipMemcpyHostToDevice, c->stream));
+    id = clk.begin(4);
+    hipLaunchKernelGGL(topay::k_plan_pack_solver, dim3((unsigned)nsv), dim3(64), 0, c->stream, nsv, (const int*)d_src, (const int*)d_srccall, layer_cap,
+                       (const int*)d_wlen, (const double*)d_wb, (const long long*)d_poff, (const double*)d_sv, b0, c->pl_paths.as<double>(),
+                       c->pl_bvel.as<double>());
+    HIPCHK(hipGetLastError());
+    clk.end(id);
+    HIPCHK(hipStreamSynchronize(c->stream));   // (the launch's buffers are reused by the next one)
+  }
+  const int B = (int)T.call.size();
+  if (B == 0) return TOPAY_OK;   // no candidate of any call survived to the solve: the try fails for all of them
+  // ---- one batch: init, groups, solve, gate
+  int id = clk.begin(4);
+  s = set_init_traj_impl(c, B, T.len.data(), c->pl_paths.as<double>(), c->pl_bvel.as<double>(), nullptr, T.mid.data(), hipMemcpyDeviceToDevice);
+  clk.end(id);
+  if (s == TOPAY_ERR_TOO_MANY_PIECES) {   // every candidate needs more pieces than the build solves
+    if (cand)
+      for (int b = 0; b < B; b++) cand[(((size_t)T.call[b] * 2 + t) * 8 + T.k[b]) * 4] = topay::PLAN_TOO_MANY_PIECES;
+    return TOPAY_OK;
+  }
+  if (s != TOPAY_OK) return s;
+  if ((s = topay_set_groups(c, T.call.data(), P.cancel_budget)) != TOPAY_OK) return s;
+  if ((s = topay_optimize(c)) != TOPAY_OK) return s;
+  c->pl_stage_ms[5] += c->last_ms;
+  std::vector<int> feas(B);
+  id = clk.begin(6);
+  if ((s = topay_check_feasible(c, feas.data())) != TOPAY_OK) return s;
+  // ---- winners: per call one lane over its candidates (adjacent in the batch, in candidate order)
+  std::vector<int> qcall, first, count;
+  for (int b = 0; b < B; b++) {
+    if (qcall.empty() || qcall.back() != T.call[b]) { qcall.push_back(T.call[b]); first.push_back(b); count.push_back(0); }
+    count.back()++;
+  }
+  const int Q = (int)qcall.size();
+  if ((s = c->pl_win.ensure((size_t)Q * (16 + 12) + (size_t)B * 4)) != TOPAY_OK) return s;
+  double* d_wcd = c->pl_win.as<double>();
+  int* d_first = (int*)(d_wcd + 2 * (size_t)Q);
+  int* d_count = d_first + Q;
+  int* d_win = d_count + Q;
+  int* d_stage = d_win + Q;
+  HIPCHK(hipMemcpyAsync(d_first, first.data(), (size_t)Q * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(d_count, count.data(), (size_t)Q * 4, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(topay::k_plan_winner, dim3((Q + 63) / 64), dim3(64), 0, c->stream, c->db, Q, (const int*)d_first, (const int*)d_count, d_stage, d_win, d_wcd);
+  HIPCHK(hipGetLastError());
+  clk.end(id);
+  std::vector<int> win(Q), stage(B), sst((size_t)B * 8);
+  std::vector<double> hw(2 * (size_t)Q);
+  HIPCHK(hipMemcpyAsync(win.data(), d_win, (size_t)Q * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(stage.data(), d_stage, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(hw.data(), d_wcd, (size_t)Q * 16, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(sst.data(), c->stats.p, (size_t)B * 32, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (cand)
+    for (int b = 0; b < B; b++) {
+      int* e = cand + (((size_t)T.call[b] * 2 + t) * 8 + T.k[b]) * 4;
+      e[0] = stage[b]; e[1] = c->hN[b]; e[3] = c->hN[b] > 0 ? sst[(size_t)b * 8 + 3] : 0;
+    }
+  // ---- the winners into the store: trajectories in the layout of k_gather_results, init paths after them
+  std::vector<int> widx, woff{0}, foff{0};
+  for (int q = 0; q < Q; q++) {
+    if (win[q] < 0) continue;
+    const int p = qcall[q], b = win[q];
+    int* r = result + 8 * (size_t)p;
+    r[0] = 1; r[1] = t; r[4] = T.k[b]; r[5] = c->hN[b]; r[7] = b;
+    if (wcd) { wcd[2 * (size_t)p] = hw[2 * (size_t)q]; wcd[2 * (size_t)p + 1] = hw[2 * (size_t)q + 1]; }
+    topay_ctx::PlanStored& e = c->ps_calls[p];
+    e.n_pieces = c->hN[b];
+    e.piece0 = (int)c->ps_pieces + woff.back();
+    e.knot0 = (int)c->ps_pieces + (int)c->ps_winners + woff.back() + (int)widx.size();
+    e.front0 = (int)c->ps_states + foff.back();
+    e.front_len = T.len[b];
+    widx.push_back(b);
+    woff.push_back(woff.back() + c->hN[b]);
+    foff.push_back(foff.back() + T.len[b]);
+  }
+  const int W = (int)widx.size();
+  if (W == 0) return TOPAY_OK;
+  const size_t np = (size_t)woff.back(), P0 = c->ps_pieces, W0 = c->ps_winners, F0 = c->ps_states;
+  if ((s = grow_keep(c, c->ps_dur, (P0 + np) * 8, P0 * 8)) != TOPAY_OK || (s = grow_keep(c, c->ps_coef, (P0 + np) * 54 * 8, P0 * 54 * 8)) != TOPAY_OK ||
+      (s = grow_keep(c, c->ps_kn, 2 * (P0 + W0 + np + W) * 8, 2 * (P0 + W0) * 8)) != TOPAY_OK ||
+      (s = grow_keep(c, c->ps_front, (F0 + (size_t)foff.back()) * 80, F0 * 80)) != TOPAY_OK)
+    return s;
+  if ((s = c->pl_sel.ensure((size_t)W * 12 + 8)) != TOPAY_OK) return s;
+  int* d_idx = c->pl_sel.as<int>();
+  int* d_woff = d_idx + W;
+  int* d_foff = d_woff + W + 1;
+  HIPCHK(hipMemcpyAsync(d_idx, widx.data(), (size_t)W * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(d_woff, woff.data(), ((size_t)W + 1) * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(d_foff, foff.data(), ((size_t)W + 1) * 4, hipMemcpyHostToDevice, c->stream));
+  id = clk.begin(7);
+  hipLaunchKernelGGL(k_gather_results, dim3(W), dim3(64), 0, c->stream, c->db, W, (const int*)d_idx, (const int*)d_woff, c->ps_dur.as<double>() + P0,
+                     c->ps_coef.as<double>() + 54 * P0, c->ps_kn.as<double>() + 2 * (P0 + W0));
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(topay::k_plan_gather_front, dim3(W), dim3(64), 0, c->stream, W, (const int*)d_idx, (const double*)c->paths.as<double>(),
+                     (const long long*)c->path_off.as<long long>(), (const int*)d_foff, c->ps_front.as<double>() + 10 * F0);
+  HIPCHK(hipGetLastError());
+  clk.end(id);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->ps_pieces += np; c->ps_winners += (size_t)W; c->ps_states += (size_t)foff.back();
+  return TOPAY_OK;
+}
+
+extern "C" {
+
+void topay_plan_default_params(topay_plan_params_t* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  topay_topo_default_params(&p->topo);
+  topay_mcrrt_default_params(&p->mcrrt);
+  p->dense_step = 1.414;       // planner.cpp:858
+  p->jps_margin = 0.1;         // planner.cpp:816
+  p->cancel_budget = 2400;     // the 100 ms of planner.cpp:946 in piece-evaluations
+  p->max_candidates = 8;       // traj_opters.size(), planner.cpp:59
+  p->critical_retry = 1;       // planner.cpp:961-963
+}
+
+topay_status topay_plan_calls(topay_ctx* c, int n, const int* map_ids, const double* start, const double* end, const double* start_v,
+                              const topay_plan_params_t* params, unsigned long long first_call, int* result, int* candidates,
+                              double* winner_cost_duration) {
+  if (!c || n <= 0 || !start || !end || !result) return TOPAY_ERR_INVALID_ARG;
+  topay_plan_params_t P;
+  if (params) P = *params;
+  else topay_plan_default_params(&P);
+  if (P.max_candidates < 1 || P.max_candidates > TOPAY_PLAN_MAX_CAND || !(P.dense_step > 0.0) || P.cancel_budget < 0 || !mcrrt_params_ok(P.mcrrt) ||
+      P.topo.reserve_num < 1 || P.topo.reserve_num > 16) {
+    set_err("topay_plan_calls: parameters out of range (max_candidates 1..8, dense_step > 0, cancel_budget >= 0)");
+    return TOPAY_ERR_INVALID_ARG;
+  }
+  std::vector<int> mids((size_t)n, 0);
+  for (int p = 0; p < n; p++) {
+    mids[p] = map_ids ? map_ids[p] : 0;
+    if (mids[p] < 0 || mids[p] >= TOPAY_MAX_MAPS) return TOPAY_ERR_INVALID_ARG;
+    if (!c->have_map[mids[p]]) { set_err("map slot not set"); return TOPAY_ERR_NO_MAP; }
+    const DevMap& m = c->hmaps[mids[p]];
+    if (!m.esdf2d_inflate || !m.esdf2d_critical) {
+      set_err("topay_plan_calls: map slot " + std::to_string(mids[p]) + " has no front-end fields: fill it with topay_build_esdf*, not topay_set_map");
+      return TOPAY_ERR_NO_MAP;
+    }
+  }
+  HIPCHK(hipSetDevice(c->device));
+  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }
+  c->ps_calls.assign((size_t)n, topay_ctx::PlanStored());
+  c->ps_pieces = c->ps_winners = c->ps_states = 0;
+  for (int k = 0; k < 8; k++) c->pl_stage_ms[k] = 0.0;
+  for (int p = 0; p < n; p++) {
+    int* r = result + 8 * (size_t)p;
+    r[0] = 0; r[1] = -1; r[2] = 0; r[3] = 0; r[4] = -1; r[5] = 0; r[6] = 0; r[7] = -1;
+    if (winner_cost_duration) winner_cost_duration[2 * (size_t)p] = winner_cost_duration[2 * (size_t)p + 1] = 0.0 / 0.0;
+  }
+  if (candidates) memset(candidates, 0, (size_t)n * 2 * 8 * 4 * sizeof(int));
+  PlanClock clk(c);
+  topay_status s = TOPAY_OK;
+  for (int t = 0; t < 2 && s == TOPAY_OK; t++) {
+    if (t == 1 && !P.critical_retry) break;
+    std::vector<int> act;
+    for (int p = 0; p < n; p++)
+      if (result[8 * (size_t)p] == 0) act.push_back(p);
+    if (act.empty()) break;
+    s = plan_try(c, t, act, mids, start, end, start_v, P, first_call, result, candidates, winner_cost_duration, clk);
+  }
+  clk.collect();
+  if (s != TOPAY_OK) { c->ps_calls.clear(); return s; }
+  return TOPAY_OK;
+}
+
+topay_status topay_plan_get_trajs(topay_ctx* c, int n, const int* call_idx, int cap_pieces, int* piece_off, double* durations, double* coeffs,
+                                  double* knots_xy) {
+  if (!c || n < 0 || (n > 0 && (!call_idx || !piece_off))) return TOPAY_ERR_INVALID_ARG;
+  if (c->ps_calls.empty()) { set_err("topay_plan_get_trajs: no planning call has been run"); return TOPAY_ERR_NO_TRAJ; }
+  if (n == 0) return TOPAY_OK;
+  std::vector<int> off((size_t)n + 1, 0), sp((size_t)n, 0), sk((size_t)n, 0);
+  for (int k = 0; k < n; k++) {
+    if (call_idx[k] < 0 || call_idx[k] >= (int)c->ps_calls.size()) return TOPAY_ERR_INVALID_ARG;
+    const topay_ctx::PlanStored& e = c->ps_calls[call_idx[k]];
+    off[k + 1] = off[k] + e.n_pieces;
+    sp[k] = e.piece0; sk[k] = e.knot0;
+  }
+  const int np = off[n];
+  memcpy(piece_off, off.data(), ((size_t)n + 1) * sizeof(int));
+  if (np > cap_pieces) { set_err("topay_plan_get_trajs: cap_pieces too small for the selection"); return TOPAY_ERR_INVALID_ARG; }
+  if (!durations && !coeffs && !knots_xy) return TOPAY_OK;
+  HIPCHK(hipSetDevice(c->device));
+  const size_t ints = (size_t)4 * n + 1, dbl = (size_t)np + (size_t)np * 54 + (size_t)2 * (np + n);
+  topay_status s;
+  if ((s = c->pb_io.ensure(ints * 4 + 8 + dbl * 8)) != TOPAY_OK) return s;
+  int* d_sp = c->pb_io.as<int>();
+  int* d_sk = d_sp + n;
+  int* d_off = d_sk + n;
+  double* d_dur = (double*)(((uintptr_t)(d_off + n + 1) + 7) & ~(uintptr_t)7);
+  double* d_coef = d_dur + np;
+  double* d_kn = d_coef + (size_t)np * 54;
+  HIPCHK(hipMemcpyAsync(d_sp, sp.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(d_sk, sk.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(d_off, off.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemsetAsync(d_kn, 0, (size_t)2 * (np + n) * 8, c->stream));   // a call without a winner still owns one knot pair: zeros
+  if (np > 0) {
+    hipLaunchKernelGGL(topay::k_plan_store_gather, dim3(n), dim3(64), 0, c->stream, n, (const int*)d_sp, (const int*)d_sk, (const int*)d_off,
+                       (const double*)c->ps_dur.as<double>(), (const double*)c->ps_coef.as<double>(), (const double*)c->ps_kn.as<double>(), d_dur, d_coef, d_kn);
+    HIPCHK(hipGetLastError());
+  }
+  std::vector<double> host(dbl);
+  HIPCHK(memcpy_sync(c, host.data(), d_dur, dbl * 8, hipMemcpyDeviceToHost));
+  if (durations) memcpy(durations, host.data(), (size_t)np * 8);
+  if (coeffs) memcpy(coeffs, host.data() + np, (size_t)np * 54 * 8);
+  if (knots_xy) memcpy(knots_xy, host.data() + np + (size_t)np * 54, (size_t)2 * (np + n) * 8);
+  return TOPAY_OK;
+}
+
+topay_status topay_plan_get_front_path(topay_ctx* c, int call, int cap_states, int* n_states, double* states) {
+  if (!c || !n_states || cap_states < 0) return TOPAY_ERR_INVALID_ARG;
+  if (c->ps_calls.empty()) { set_err("topay_plan_get_front_path: no planning call has been run"); return TOPAY_ERR_NO_TRAJ; }
+  if (call < 0 || call >= (int)c->ps_calls.size()) return TOPAY_ERR_INVALID_ARG;
+  const topay_ctx::PlanStored& e = c->ps_calls[call];
+  *n_states = e.front_len;
+  const int w = std::min(e.front_len, cap_states);
+  if (w > 0 && states) {
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(memcpy_sync(c, states, c->ps_front.as<double>() + 10 * (size_t)e.front0, (size_t)w * 80, hipMemcpyDeviceToHost));
+  }
+  return TOPAY_OK;
+}
+
+topay_status topay_plan_test_chunk(topay_ctx* c, int calls) {
+  if (!c || calls < 0) return TOPAY_ERR_INVALID_ARG;
+  c->pl_chunk = calls;
+  return TOPAY_OK;
+}
+
+topay_status topay_plan_stage_ms(topay_ctx* c, double* ms) {
+  if (!c || !ms) return TOPAY_ERR_INVALID_ARG;
+  for (int k = 0; k < 8; k++) ms[k] = c->pl_stage_ms[k];
   return TOPAY_OK;
 }
 

@@ -306,6 +306,7 @@ enum { MC_EXPANDED = 1, MC_IN_TREE = 2, MC_IN_ANTI = 3 };   // MCRRTNode::NodeSt
 struct McrrtBatch {
   int n, layer_cap;
   unsigned long long inst_base;
+  const unsigned long long* inst;   // instance number per search (topay_plan_calls), or null: inst_base + search
   const int* map_id;
   const long long* car_off;   // first entry of instance p's chassis path in `car`
   const int* car_len;         // L_p
@@ -628,7 +629,7 @@ __global__ void __launch_bounds__(64) k_mcrrt(const DevMap* maps, const McrrtBat
   RsPath* rs = B.rs + (size_t)p * 2 * B.layer_cap;
   C.rs = rs;
   C.n = 0; C.overflow = 0; C.stamp = 0; C.checks = 0;
-  C.inst = B.inst_base + (unsigned long long)p;
+  C.inst = B.inst ? B.inst[p] : B.inst_base + (unsigned long long)p;
   C.iter = 0;
   const int L = C.L;
   C.near_min = L - 1;

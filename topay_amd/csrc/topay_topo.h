@@ -36,6 +36,7 @@ struct TopoBatch {
   int n, cap_paths, cap_points;
   int pt_cap, nbuf;             // points per point buffer (the cap of the largest map of the call), buffers per query: S[i] = i, D[i] = R2 + i, T[k][0..1] = 2 R2 + 2 k + (0, 1)
   unsigned long long inst_base;
+  const unsigned long long* inst;   // instance number per query (topay_plan_calls), or null: inst_base + query
   const int* map_id;
   const double* start;          // n x 2
   const double* end;            // n x 2
@@ -271,7 +272,7 @@ __global__ void __launch_bounds__(64) k_topo(const DevMap* maps, const TopoBatch
   // points a path of THIS query's map may have (the buffers are strided by the largest map of the call, B.pt_cap)
   const int pt_cap = min(B.pt_cap, 2 * (int)ceil(sqrt((double)C.nx * C.nx + (double)C.ny * C.ny)) + 512);
   const double sx = B.start[2 * (size_t)p], sy = B.start[2 * (size_t)p + 1], ex = B.end[2 * (size_t)p], ey = B.end[2 * (size_t)p + 1];
-  const unsigned long long inst = B.inst_base + (unsigned long long)p;
+  const unsigned long long inst = B.inst ? B.inst[p] : B.inst_base + (unsigned long long)p;
   int n_drawn = 0, n_passed = 0, nodes_before = 0, nodes_after = 0, raw_found = 0, n_filtered = 0;
   auto finish = [&](int status, int n_sel) {
     if (lane == 0) {
