@@ -55,7 +55,7 @@ struct TopoParams {   // == topay_topo_params_t
   unsigned long long seed;
 };
 
-// points per discretised / shortened path the device keeps room for (topay_hip.hip: topo_pt_cap)
+// points per discretised / shortened path the device keeps room for (topay_host_front.h: topo_pt_cap)
 inline int topo_pt_cap(int nx, int ny) { return 2 * (int)std::ceil(std::sqrt((double)nx * nx + (double)ny * ny)) + 512; }
 
 typedef std::array<double, 3> V3;

@@ -302,8 +302,11 @@ inline hipError_t hipGetDeviceCount(int* n) { *n = 1; return 0; }
 inline hipError_t hipSetDevice(int) { return 0; }
 inline hipError_t hipGetLastError() { return 0; }
 inline hipError_t hipDeviceSynchronize() { return 0; }
-template <typename T> inline hipError_t hipMalloc(T** p, size_t n) { *p = (T*)calloc(n ? n : 1, 1); return *p ? 0 : 2; }
-inline hipError_t hipFree(void* p) { free(p); return 0; }
+// Live hipMalloc / hipHostMalloc allocations, exported for the tests (a context must give back everything it took).
+inline long g_emu_live_allocs = 0;
+extern "C" __attribute__((used, visibility("default"))) inline long topay_emu_live_allocations() { return g_emu_live_allocs; }
+template <typename T> inline hipError_t hipMalloc(T** p, size_t n) { *p = (T*)calloc(n ? n : 1, 1); g_emu_live_allocs += *p != nullptr; return *p ? 0 : 2; }
+inline hipError_t hipFree(void* p) { g_emu_live_allocs -= p != nullptr; free(p); return 0; }
 inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { memcpy(d, s, n); return 0; }
 inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { memcpy(d, s, n); return 0; }
 inline hipError_t hipMemset(void* d, int v, size_t n) { memset(d, v, n); return 0; }
@@ -317,8 +320,8 @@ inline hipError_t hipStreamCreate(hipStream_t* s) { *s = nullptr; return 0; }
 inline hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned, int) { *s = nullptr; return 0; }
 inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = nullptr; return 0; }
 enum { hipHostMallocMapped = 2, hipHostMallocCoherent = 0x40000000 };
-inline hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = calloc(n ? n : 1, 1); return *p ? 0 : 2; }
-inline hipError_t hipHostFree(void* p) { free(p); return 0; }
+inline hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = calloc(n ? n : 1, 1); g_emu_live_allocs += *p != nullptr; return *p ? 0 : 2; }
+inline hipError_t hipHostFree(void* p) { g_emu_live_allocs -= p != nullptr; free(p); return 0; }
 inline hipError_t hipHostGetDevicePointer(void** d, void* h, unsigned) { *d = h; return 0; }
 enum { hipErrorNotReady = 600 };
 inline hipError_t hipStreamQuery(hipStream_t) { return 0; }

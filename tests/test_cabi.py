@@ -324,3 +324,67 @@ def test_a_field_with_a_single_z_layer_is_refused(cuboids_small):
     with pytest.raises(api.TopayError):
         o.set_map(w.origin, w.res, dims, w.min_b, w.max_b, w.esdf2d, e3)
     o.close()
+
+
+def test_a_destroyed_context_has_given_back_every_allocation():
+    """Device buffers own their memory (DevBuf frees in its destructor, topay_destroy frees the members by `delete`): the
+    emulator's count of live hipMalloc / hipHostMalloc allocations is the same after topay_destroy as before topay_create,
+    for a context that went through a map build, set_init_traj, a solve, the gate, a getter, the front-end entries with
+    function-local buffers (dense path, connect collision, Reeds-Shepp, JPS), the roadmap, the joint-space search and a
+    planning call.  The single entries are also balanced one by one while the context lives: a local buffer is freed by scope.
+
+    topay_dense_path has no input that fails after its allocations without faking an error: every argument check comes
+    before them, and what follows can only fail through a HIP call, which the emulator never fails.  So that path is
+    covered by construction (scope) and not by a case here."""
+    import gc
+
+    from conftest import EMU_LIB
+    from harness import workload as wl
+
+    L = api.load(EMU_LIB)
+    L.topay_emu_live_allocations.restype = C.c_long
+    live = L.topay_emu_live_allocations
+    tb = wl.TablesBatch(2, 2, base_seed=2024, nthreads=8)
+    gc.collect()                                   # (contexts of earlier tests that are garbage go now, not in between)
+    before = live()
+    p = api.default_params(L)
+    p.s1_lbfgs.max_iterations = 20
+    p.s2_lbfgs.max_iterations = 20
+    p.alm_max_outer = 1
+    opt = api.MomaTrajOptBatch(params=p, lib_path=EMU_LIB)
+    assert live() > before
+    slot = {s: k for k, s in enumerate(tb.scenarios)}
+    for s_ in tb.scenarios:
+        w = tb.world(s_)
+        opt.build_esdf(w.origin, w.res, w.dims, w.min_b, w.max_b, w.occ2d, w.occ3d, map_id=slot[s_])
+    mid = np.array([slot[s_] for s_ in tb.scen], dtype=np.int32)
+    opt.set_init_traj(tb.lens, tb.paths, map_ids=mid)
+    opt.optimize()
+    opt.check_feasible()
+    opt.getTraj(0)
+    offs = np.concatenate([[0], np.cumsum(tb.lens)])
+    start = np.array([tb.paths[offs[b]] for b in range(len(tb.lens))])
+    end = np.array([tb.paths[offs[b + 1] - 1] for b in range(len(tb.lens))])
+    held = live()                                  # what the context keeps; the entries below add nothing that outlives them
+    raw = [tb.paths[offs[b]:offs[b + 1], :2] for b in range(2)]
+    opt.dense_path(raw, start[:2, 2], end[:2, 2])
+    assert live() == held
+    n = 4
+    a = np.c_[np.linspace(-2, 2, n), np.zeros(n), np.zeros(n)]
+    b = a + np.array([0.5, 0.3, 0.1])
+    opt.connect_collision(np.full(n, 0.7), lambda e, fr: a[e] + fr[:, None] * (b[e] - a[e]), np.zeros((n, 7)), np.full((n, 7), 0.1), 0.1)
+    assert live() == held
+    opt.reeds_shepp(a, b, t=0.5)
+    assert live() == held
+    opt.plan2d_jps(start[:2, :2], end[:2, :2], map_ids=mid[:2])
+    assert live() == held
+    opt.topo_paths(start[:1, :2], end[:1, :2], opt.topo_params(seed=7, max_sample_num=200), map_ids=mid[:1])
+    car = np.concatenate([np.c_[tb.paths[offs[b]:offs[b + 1], :3], tb.dts[offs[b]:offs[b + 1]]] for b in range(2)])
+    opt.mcrrt_plan(tb.lens[:2], car, start[:2], end[:2], opt.mcrrt_params(seed=7, max_iter=50), map_ids=mid[:2])
+    first = [int(np.nonzero(tb.scen == s_)[0][0]) for s_ in tb.scenarios]
+    opt.plan_calls(start[first], end[first], map_ids=mid[first], params=opt.plan_params(topo=dict(max_sample_num=200), mcrrt=dict(max_iter=50)))
+    opt.plan_trajs([0, 1])
+    assert live() > before
+    opt.close()
+    assert live() == before
+    tb.close()

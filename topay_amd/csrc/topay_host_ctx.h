@@ -1,0 +1,586 @@
+// Host side of the C-ABI, part 1: the error text, owning device buffers and the carver of packed blocks, the launch-class
+// table, the context, parameters, create and destroy.
+
+#pragma once
+
+static thread_local std::string g_err;
+static void set_err(const std::string& s) { g_err = s; }
+#define HIPCHK(call)                                                                             \
+  do {                                                                                           \
+    hipError_t e_ = (call);                                                                      \
+    if (e_ != hipSuccess) {                                                                      \
+      set_err(std::string(#call) + ": " + hipGetErrorString(e_));                                \
+      return TOPAY_ERR_NO_DEVICE;                                                                \
+    }                                                                                            \
+  } while (0)
+
+// From the environment the library reads TOPAY_PERSISTENT / TOPAY_STEAL (launch scheme, used by the profiling scripts and
+// the parity tests) and TOPAY_RCCL_LIB, and it sets GPU_MAX_HW_QUEUES when it is loaded; nothing else.
+
+// The layout of a packed block, stated once: a list of take<T>(count) in the order of the sub-arrays.  Run on a null base it
+// gives the byte count (`off`), run on the buffer it gives the pointers (DevBuf::carve does both).
+struct Carver {
+  uintptr_t base;
+  size_t off = 0;
+  explicit Carver(void* b = nullptr) : base((uintptr_t)b) {}
+  template <typename T> T* take(size_t count) {
+    off = (off + alignof(T) - 1) & ~(alignof(T) - 1);
+    T* q = (T*)(base + off);
+    off += count * sizeof(T);
+    return q;
+  }
+};
+
+// A device buffer that owns its memory: freed when it goes out of scope (the early returns of the HIPCHK macro included) or with
+// the context it is a member of.  Move-only.
+struct DevBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept { *this = std::move(o); }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) { release(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; }
+    return *this;
+  }
+  ~DevBuf() { release(); }
+  topay_status ensure(size_t n) {
+    if (n <= bytes) return TOPAY_OK;
+    release();
+    const hipError_t e_ = hipMalloc(&p, n);
+    if (e_ != hipSuccess) {
+      p = nullptr;
+      set_err("device allocation of " + std::to_string(n >> 20) + " MiB failed: " + hipGetErrorString(e_));
+      return TOPAY_ERR_NO_DEVICE;
+    }
+    bytes = n;
+    return TOPAY_OK;
+  }
+  void release() {   // free early on purpose (a map slot being refilled, an arena, a workspace that is no longer needed)
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+  template <typename T> T* as() { return (T*)p; }
+  template <typename F> topay_status carve(F&& lay) {   // a packed block: sized by its layout, then the layout's pointers set
+    Carver size;
+    lay(size);
+    const topay_status s = ensure(size.off);
+    Carver at(p);
+    if (s == TOPAY_OK) lay(at);
+    return s;
+  }
+};
+
+// Launch buckets by number of pieces: upper bounds (inclusive) = one bucket per kernel template (rows per lane 1 / 2 / 3 / 4 / 6).
+// Each bucket is one launch on its own stream so that they run concurrently.  All streams have the SAME priority:
+// mixed priorities made the hardware preempt (context-save) the low-priority waves whenever high-priority work
+// arrived, and twice in ~80 runs one low-priority launch was starved for tens of seconds.  HIP maps the streams of one
+// priority onto a pool of GPU_MAX_HW_QUEUES (default 4) hardware queues shared by every stream of the process, and
+// streams that share a queue serialise (tools/queue_probe.hip); the library asks for 24 queues at load time (below: three contexts in
+// flight use 18, and another library's stream -- RCCL's -- that lands on the queue of a persistent solve launch waits a
+// whole solve; 32 and more are time-sliced by the scheduler firmware)
+// when the environment does not say otherwise.  With one wave per SIMD, four workgroups of the common classes (<= 21 /
+// 27 / 36 / 54 KB per wave) share a CU's 160 KB; the two rare classes of long candidates (<= 70 / 104 KB) cost their CU a
+// slot or two, which is why they are kept apart from each other.
+static const int kBucketMaxN[TOPAY_NBUCKET] = {10, 15, 21, 32, 42, 64, TOPAY_MAX_N};
+// Launch classes are finer than kernel templates where that saves LDS: the two-rows-per-lane kernel serves N <= 15 with
+// 27 KB and N <= 21 with 36 KB per workgroup (most candidates of the benchmark have 11..15 pieces).  LDS is what
+// limits how many workgroups a CU hosts beside a long candidate's: giving every class-1 workgroup the 38 KB of class 2
+// cost 8 % of the throughput, taking 9 KB from most of the two-rows workgroups pays the other way.
+static const int kBigFirst = 4;   // the classes of long candidates (N > 32) start here
+
+// Kernel of a launch class: rows per thread and waves per trajectory select the template; the LDS is sized by the
+// longest candidate actually in the class.
+typedef void (*solve_kernel_t)(DevBatch, const DevMap*, int);
+typedef void (*eval_kernel_t)(DevBatch, const DevMap*, int, int, int);
+struct ClassDef {
+  int max_n, rmax, nw;   // rows per thread and waves of an EVALUATION of the class (= threads of its workgroups / 64)
+  solve_kernel_t solve;
+  eval_kernel_t eval;
+  int occ = 2;   // waves per SIMD the kernel is built for (512 / occ registers per lane; every kernel: 256, no AGPRs)
+  solve_kernel_t lat = nullptr;   // helper-wave kernel of a one-wave class (topay_set_latency_mode): 4 waves per workgroup
+  // The solver runs on ONE wave in every class; its rows per lane (elements per lane / 2) are what the bits of a solve depend on
+  // (topay_class_of).  0 = as the evaluation.  The long classes run it on wave 0 of a four-wave workgroup whose other waves
+  // join the evaluations only (helper waves, topay_solve.h).
+  int solver_rmax = 0;
+  int srmax() const { return solver_rmax ? solver_rmax : rmax; }
+  bool helpers() const { return nw > 1; }   // `solve` is a helper-wave kernel: its LDS carries the command block
+};
+static const int kLatWaves = 4;
+// N <= 32: one wave per trajectory.  N = 33..170: the evaluations on four waves (round 4: the long candidates set the length
+// of a batch), the solver on wave 0 alone with 10 / 28 vector elements per lane (round 5: every reduction of a four-wave
+// solver was a workgroup reduction through LDS and a barrier).  Figures: docs/EXPERIMENTS.md.
+static const ClassDef kClassTable[TOPAY_NBUCKET] = {
+    {10, 1, 1, k_solve1, k_eval1, 2, k_lat1}, {15, 2, 1, k_solve2, k_eval2, 2, k_lat2}, {21, 2, 1, k_solve2, k_eval2, 2, k_lat2},
+    {32, 3, 1, k_solve3, k_eval3, 2, k_lat3},
+    {42, 2, 4, k_long5, k_eval2w4, 2, nullptr, 5}, {64, 2, 4, k_long5, k_eval2w4, 2, nullptr, 5},
+    {TOPAY_MAX_N, 4, 4, k_long14, k_eval4w4, 2, nullptr, 14}};
+// work per SIMD-second of the two-waves-per-SIMD classes relative to one wave per SIMD (sizes the launches only; assumed
+// 1.0 / 1.2 / 1.4 / 1.7 / 2.0 gave 10.0k / 10.2k / 10.5k / 10.8k / 10.6k trajectories/s, docs/EXPERIMENTS.md)
+static const double kOcc2Gain = 1.7;
+static const int kLdsDoublesPerCU = 160 * 1024 / 8;
+static size_t class_lds_bytes(const ClassDef& cd, int nm) {
+  const int d = lds_doubles_mw(nm, cd.nw);
+  // + past-cost ring [8] + the solver state parked across an evaluation [40] (+ the command block of a helper-wave kernel)
+  return (size_t)(d + 8 + 40 + (cd.helpers() ? TOPAY_CMD_DOUBLES : 0)) * sizeof(double);
+}
+
+// Runs when the library is loaded: effective if the HIP runtime has not been initialised yet in this process
+// (the runtime reads the variable once, at its first call).  A caller that initialises HIP first should export
+// GPU_MAX_HW_QUEUES=24 itself.
+__attribute__((constructor)) static void topay_request_hw_queues() { setenv("GPU_MAX_HW_QUEUES", "24", 0); }
+// Dispatch gate (topay_optimize_async): the context whose solve was issued last in this process.
+struct topay_ctx;
+static std::mutex g_issue_mutex;
+// Every live context of the process (topay_create / topay_destroy), for push_params.
+static std::mutex g_registry_mutex;
+static std::vector<topay_ctx*> g_contexts;
+
+static topay_ctx* g_last_issued = nullptr;
+
+struct topay_ctx {
+  int device = 0;
+  topay_params_t hp;
+  DevParams dp;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  // maps
+  std::vector<DevMap> hmaps = std::vector<DevMap>(TOPAY_MAX_MAPS);
+  std::vector<DevBuf> map2d = std::vector<DevBuf>(TOPAY_MAX_MAPS), map3d = std::vector<DevBuf>(TOPAY_MAX_MAPS);
+  std::vector<DevBuf> map2d_inf = std::vector<DevBuf>(TOPAY_MAX_MAPS), map2d_crit = std::vector<DevBuf>(TOPAY_MAX_MAPS);
+  // Maps built on the device as a batch live in one arena per build call (the construction writes the fields where
+  // they stay; the slots' descriptors point into it), kept until the context is destroyed.
+  struct MapArena { DevBuf buf; int first = 0, n = 0; };
+  std::vector<MapArena> map_arenas;
+  DevBuf dmaps;
+  std::vector<char> have_map = std::vector<char>(TOPAY_MAX_MAPS, 0);
+  // topay_share_maps: slot m of this context refers to the fields of map_owner[m] (null: its own); map_sharers = the
+  // contexts that refer to slots of this one.  When the owner refills or frees a slot, the sharers' slots are invalidated
+  // (have_map 0 -> TOPAY_ERR_NO_MAP) after their pending solves have finished: no context keeps a dangling descriptor.
+  std::vector<topay_ctx*> map_owner = std::vector<topay_ctx*>(TOPAY_MAX_MAPS, nullptr);
+  std::vector<topay_ctx*> map_sharers;
+  std::vector<int> h_map_id;   // map slot of every candidate of the resident batch
+  std::vector<int> h_path_len; // init-path states of every candidate (launch order inside a class)
+  // batch
+  int B = 0, Nmax = 0, total_states = 0, Pmax = 0;
+  // pieces / decision-vector elements of the candidates before b (packed per-candidate blocks, DevBatch::poff / noff)
+  std::vector<long long> h_poff, h_noff;
+  DevBuf poff, noff;
+  size_t workspace_bytes = 0;   // device memory of the resident batch (topay_workspace_bytes)
+  // per-trajectory N (0 = not representable, skipped); launch buckets by N (LDS is sized per bucket)
+  std::vector<int> hN;
+  static constexpr int NBUCKET = TOPAY_NBUCKET;
+  std::vector<int> cls[NBUCKET];
+  hipStream_t bstream[NBUCKET] = {nullptr};
+  hipEvent_t bevent[NBUCKET] = {nullptr};
+  hipEvent_t bstart = nullptr;
+  bool pending = false;  // a topay_optimize_async has been issued and not yet waited for
+  int* h_started = nullptr;  // pinned host counter the solve kernels bump once per candidate (dispatch gate)
+  int n_launched = 0;        // candidates the pending solve launched
+  int n_gate = 0;            // ... of which the dispatch gate waits for (the classes of up to 32 pieces)
+  int latency_mode = 0;        // topay_set_latency_mode: 0 never, 1 batches of at most one candidate per SIMD, 2 always
+  bool gate_done = false;      // the resident flags / report are those of the last solve
+  // cancellation: planning call of every candidate, the window after a call's first feasible success (piece-evaluations)
+  std::vector<int> h_group;
+  int n_groups = 0, cancel_budget = 0;
+  DevBuf group_id, group_tau, interrupted;
+  int* h_cancel = nullptr;     // pinned: topay_cancel
+  // the one exchange of the multi-GPU path: all-gather of per-scenario records over RCCL (topay_comm_init)
+  void* comm = nullptr;        // ncclComm_t
+  int comm_world = 0, comm_rank = 0;
+  hipStream_t comm_stream = nullptr;
+  DevBuf comm_send, comm_recv;
+  int gate_timeouts = 0;     // times the dispatch gate gave up waiting (topay_gate_timeouts)
+  bool persistent = true;    // solve launches: one workgroup per SIMD slot pulling candidates from a queue
+  bool steal = true;         // ... and draining the smaller classes' queues once its own is empty (TOPAY_STEAL=0: profiling)
+  int simd_slots = 1024;
+  DevBuf qnext;
+  DevBuf mc_i, mc_d, mc_k, mc_rs, mc_in;   // node tables, Reeds-Shepp words and inputs of the last topay_mcrrt_plan
+  int mc_n = 0, mc_node_cap = 0;
+  DevBuf tp_i, tp_d, tp_raw, tp_pts, tp_io;   // graphs, raw paths and point buffers of the last topay_topo_paths (topay_topo_graph / _raw_paths)
+  int tp_n = 0, tp_pt_cap = 0, tp_nbuf = 0;
+  topay_topo_params_t tp_P;
+  // topay_plan_calls: the raw paths, candidate table + dense paths, search inputs / results, the try's init paths and boundary
+  // velocities, index blocks of the hand-offs, and the winner store (durations, coefficients, knots, init paths)
+  DevBuf pl_raw, pl_jps_io, pl_io, pl_tab, pl_mc, pl_paths, pl_bvel, pl_sel, pl_win, ps_dur, ps_coef, ps_kn, ps_front;
+  struct PlanStored { int n_pieces = 0, piece0 = 0, knot0 = 0, front0 = 0, front_len = 0; };
+  std::vector<PlanStored> ps_calls;   // per call of the last topay_plan_calls: where its winner lies in the store
+  size_t ps_pieces = 0, ps_winners = 0, ps_states = 0;
+  std::vector<hipEvent_t> pl_events;
+  std::vector<int> pl_event_stage;
+  std::vector<char> pl_event_done;
+  int pl_chunk = 0;   // topay_plan_test_chunk: calls per front-end launch, 0 = the constant
+  double pl_stage_ms[8] = {0};
+  DevBuf paths, path_off, path_len, bvel, bacc, scratch;
+  DevBuf N, s1_past, map_id, head, tail, start_xy, goal_xy, init_xy, x0;
+  DevBuf x, work, hist_s, hist_y, hist_ys, hist_alpha, lu;
+  DevBuf success, cost, stats, xyerr, coef, T, knots, alm, fout, order, trace, elapsed, startus, hwid, sbuf, mstash, feas_cseq, feas_tk, feas_report, feas_flags, edt_occ, edt_tmp1, edt_tmp2, edt_v, edt_z, edt_out2, pb_io;
+  float last_edt_ms = 0.f;
+  int trace_cap = 0;
+  DevBatch db;
+  bool have_traj = false, solved = false;
+  double last_ms = 0.0;
+  int last_launches = 0, last_helper_launches = 0;
+};
+
+static void make_dev_params(const topay_params_t& p, DevParams& d) {
+  memset(&d, 0, sizeof(d));
+  d.relu_mu = p.relu_mu;
+  {
+    const double pe = p.relu_mu;
+    d.sl_half = 0.5 * pe;
+    d.sl_f3c = 1.0 / (pe * pe);
+    d.sl_f4c = -0.5 * d.sl_f3c / pe;
+    d.sl_d2c = 3.0 * d.sl_f3c;
+    d.sl_d3c = 4.0 * d.sl_f4c;
+  }
+  for (int i = 0; i < 9; i++) d.energy_weights[i] = p.energy_weights[i];
+  d.s1_time_weight = p.s1_time_weight; d.s1_moment_weight = p.s1_moment_weight; d.s1_acc_weight = p.s1_acc_weight;
+  d.s1_domega_weight = p.s1_domega_weight; d.s1_path_pos_weight = p.s1_path_pos_weight;
+  d.s2_time_weight = p.s2_time_weight; d.s2_moment_weight = p.s2_moment_weight; d.s2_acc_weight = p.s2_acc_weight;
+  d.s2_domega_weight = p.s2_domega_weight; d.s2_collision_weight = p.s2_collision_weight;
+  d.s2_mani_colli_weight = p.s2_mani_colli_weight; d.s2_self_colli_weight = p.s2_self_colli_weight;
+  d.s2_mani_pos_weight = p.s2_mani_pos_weight; d.s2_mani_vel_weight = p.s2_mani_vel_weight;
+  d.s2_mani_acc_weight = p.s2_mani_acc_weight; d.s2_mean_time_weight = p.s2_mean_time_weight;
+  for (int i = 0; i < 2; i++) {
+    d.alm_init_lambda[i] = p.alm_init_lambda[i]; d.alm_init_rho[i] = p.alm_init_rho[i];
+    d.alm_rho_max[i] = p.alm_rho_max[i]; d.alm_gamma[i] = p.alm_gamma[i];
+  }
+  d.alm_tolerance = p.alm_tolerance;
+  d.alm_max_outer = p.alm_max_outer;
+  d.alm_work_budget = p.alm_work_budget;
+  d.min_piece_num = p.min_piece_num;
+  d.sample_interval = p.sample_interval;
+  d.s1_normal_past = p.s1_normal_past; d.s1_shot_path_past = p.s1_shot_path_past;
+  d.s1_shot_path_horizon = p.s1_shot_path_horizon;
+  auto cp = [](const topay_lbfgs_params_t& a, DevLbfgs& b) {
+    b.mem_size = a.mem_size; b.past = a.past; b.max_iterations = a.max_iterations; b.max_linesearch = a.max_linesearch;
+    b.g_epsilon = a.g_epsilon; b.delta = a.delta; b.min_step = a.min_step; b.max_step = a.max_step;
+    b.f_dec_coeff = a.f_dec_coeff; b.s_curv_coeff = a.s_curv_coeff; b.cautious_factor = a.cautious_factor;
+    b.machine_prec = a.machine_prec;
+  };
+  cp(p.s1_lbfgs, d.s1_lbfgs);
+  cp(p.s2_lbfgs, d.s2_lbfgs);
+  d.chassis_height = p.chassis_height; d.chassis_colli_radius = p.chassis_colli_radius;
+  d.max_v = p.max_v; d.max_a = p.max_a; d.max_w = p.max_w; d.max_dw = p.max_dw;
+  for (int i = 0; i < 8; i++) d.colli_length[i] = p.colli_length[i];
+  int s = 0;
+  for (int i = 0; i < 16 && s < TOPAY_NSPH; i++)
+    if (p.colli_points[i] != 0.0) {  // moma_param.h:217-218
+      d.sph_off[s] = p.colli_points[i];
+      d.sph_r[s] = p.colli_point_radius[i];
+      s++;
+    }
+  for (int i = 0; i < 7; i++) {
+    d.joint_pos_limit_max[i] = p.joint_pos_limit_max[i];
+    d.joint_vel_limit[i] = p.joint_vel_limit[i];
+    d.joint_acc_limit[i] = p.joint_acc_limit[i];
+  }
+  for (int i = 0; i < 9; i++) d.relR[i] = p.relative_R[i];
+  for (int i = 0; i < 3; i++) d.relT[i] = p.relative_t[i];
+  // derived constants (DevParams): the expressions of the evaluation, operation by operation (this file is compiled with
+  // -ffp-contract=off like the device code, so the host's products and sums are the device's)
+  for (int a = 0; a < TOPAY_NSPH; a++)
+    for (int b = 0; b < TOPAY_NSPH; b++) {
+      const double rr = d.sph_r[a] + d.sph_r[b];
+      d.pair_rr2[a * TOPAY_NSPH + b] = rr * rr;
+    }
+  for (int k = 0; k < TOPAY_NSPH; k++) {
+    d.sph_viol[k] = d.sph_r[k] * 10.0 * 1.1;
+    d.sph_top[k] = d.chassis_height + d.relT[2] + d.sph_r[k];
+  }
+  d.p0z = d.chassis_height + d.relT[2];
+  d.max_vw = d.max_v * d.max_w;
+  d.max_a2 = d.max_a * d.max_a;
+  d.max_dw2 = d.max_dw * d.max_dw;
+  d.chassis_r105 = d.chassis_colli_radius * 1.05;
+  for (int i = 0; i < 7; i++) {
+    d.joint_vel_limit2[i] = d.joint_vel_limit[i] * d.joint_vel_limit[i];
+    d.joint_acc_limit2[i] = d.joint_acc_limit[i] * d.joint_acc_limit[i];
+  }
+}
+
+static int sphere_layout_ok(const topay_params_t& p) {
+  // the kernels hard-wire MomaParam's sphere-per-link layout {2,1,2,1,2,1,2,1}
+  const int want[8] = {2, 1, 2, 1, 2, 1, 2, 1};
+  for (int i = 0; i < 8; i++) {
+    int c = (p.colli_points[2 * i] != 0.0) + (p.colli_points[2 * i + 1] != 0.0);
+    if (c != want[i]) return 0;
+    if (want[i] == 1 && p.colli_points[2 * i] != 0.0) return 0;
+  }
+  return 1;
+}
+
+// Every copy goes through the context's own (non-blocking) stream: null-stream operations would wait for the solves of
+// every other context of the process (and they for it), which serialises batches that are meant to overlap.
+static hipError_t memcpy_sync(topay_ctx* c, void* dst, const void* src, size_t n, hipMemcpyKind kind) {
+  hipError_t e = hipMemcpyAsync(dst, src, n, kind, c->stream);
+  if (e != hipSuccess) return e;
+  return hipStreamSynchronize(c->stream);
+}
+// Typed copies of `count` elements, asynchronous on the same stream: the byte count comes from the pointer type.
+template <typename T> static hipError_t h2d(topay_ctx* c, T* dst, const T* src, size_t count) {
+  return hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyHostToDevice, c->stream);
+}
+template <typename T> static hipError_t d2h(topay_ctx* c, T* dst, const T* src, size_t count) {
+  return hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyDeviceToHost, c->stream);
+}
+
+static topay_status validate_params(const topay_params_t* params) {
+  if (params->int_K != TOPAY_K) { set_err("int_K must be 12 in this build"); return TOPAY_ERR_UNSUPPORTED; }
+  if (!sphere_layout_ok(*params)) { set_err("unsupported collision sphere layout"); return TOPAY_ERR_UNSUPPORTED; }
+  if (params->s1_lbfgs.mem_size <= 0 || params->s2_lbfgs.mem_size <= 0 || params->s1_lbfgs.mem_size > 256 ||
+      params->s2_lbfgs.mem_size > 256 || params->s1_lbfgs.past > 8 ||
+      params->s2_lbfgs.past > 8 || params->s1_shot_path_past > 8 || params->s1_normal_past > 8) {
+    set_err("lbfgs mem_size must be in 1..256 (the reference uses 256) and past <= 8");
+    return TOPAY_ERR_INVALID_ARG;
+  }
+  return TOPAY_OK;
+}
+
+static topay_status create_device_state(topay_ctx* c, int device) {
+  HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  HIPCHK(hipEventCreate(&c->ev0));
+  HIPCHK(hipEventCreate(&c->ev1));
+  HIPCHK(hipEventCreate(&c->bstart));
+  // One stream per launch class (the last class runs on the main stream), all non-blocking and never the null stream:
+  // two contexts then use ten of the sixteen hardware queues the library asks for, and no operation of one context
+  // waits for another context's solve.
+  for (int k = 0; k < topay_ctx::NBUCKET; k++) {
+    // (the two longest classes start on the main stream: streams are hardware queues, and 3 contexts x 7 streams beside
+    // torch's and RCCL's exceed the 24 the library asks for -- a gather that shares a queue with a persistent solve
+    // launch waits a whole solve, 9.1k instead of 10.0k trajectories/s through the RCCL path.  The N <= 64 class gets a
+    // stream of its own the first time a batch also holds candidates of more than 64 pieces, launch_classes.)
+    if (k >= topay_ctx::NBUCKET - 2) c->bstream[k] = c->stream;
+    else HIPCHK(hipStreamCreateWithFlags(&c->bstream[k], hipStreamNonBlocking));
+    HIPCHK(hipEventCreate(&c->bevent[k]));
+  }
+  {
+    { const char* se = getenv("TOPAY_STEAL"); c->steal = !(se && se[0] == '0'); }
+    const char* pe = getenv("TOPAY_PERSISTENT");
+    c->persistent = !(pe && pe[0] == '0');
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device));
+    c->simd_slots = 4 * prop.multiProcessorCount;   // four SIMDs per CU; a class built for two waves per SIMD launches two workgroups per slot
+    // Every slot is used.  Nothing is left to what is not a solve (the init kernel, the feasibility gate and the result
+    // gather of the OTHER batches in flight, the runtime's copy kernels, a collective), although resident solver waves own
+    // their SIMD's whole register file and such a kernel waits until workgroups exit: measured, no gain from a standing
+    // reserve with two batches in flight.
+  }
+  {
+    void* hp = nullptr;
+    HIPCHK(hipHostMalloc(&hp, 64, hipHostMallocMapped | hipHostMallocCoherent));
+    c->h_started = (int*)hp;
+    c->h_started[0] = 0;
+    c->h_cancel = c->h_started + 8;   // same pinned block: topay_cancel's flag
+    c->h_cancel[0] = 0;
+  }
+  if (c->dmaps.ensure(sizeof(DevMap) * TOPAY_MAX_MAPS) != TOPAY_OK) return TOPAY_ERR_NO_DEVICE;
+  memset(c->hmaps.data(), 0, sizeof(DevMap) * TOPAY_MAX_MAPS);
+  return TOPAY_OK;
+}
+
+// The owner is about to refill (or free) slots [first, first + n): every context that shares one of them finishes its
+// pending solve and loses the slot.
+static void invalidate_sharers(topay_ctx* owner, int first, int n) {
+  std::vector<topay_ctx*> sharers;
+  {
+    std::lock_guard<std::mutex> lk(g_registry_mutex);
+    sharers = owner->map_sharers;
+  }
+  for (topay_ctx* s : sharers) {
+    bool hit = false;
+    for (int m = first; m < first + n; m++) hit = hit || s->map_owner[m] == owner;
+    if (!hit) continue;
+    if (s->pending) (void)topay_synchronize(s);
+    for (int m = first; m < first + n; m++)
+      if (s->map_owner[m] == owner) {
+        s->map_owner[m] = nullptr;
+        s->have_map[m] = 0;
+        memset(&s->hmaps[m], 0, sizeof(DevMap));
+        // a resident batch that uses the slot cannot be solved, evaluated or gated any more: it has to be set again
+        if (s->have_traj && std::find(s->h_map_id.begin(), s->h_map_id.end(), m) != s->h_map_id.end()) { s->have_traj = false; s->solved = false; }
+      }
+    bool any = false;
+    for (int m = 0; m < TOPAY_MAX_MAPS; m++) any = any || s->map_owner[m] == owner;
+    if (!any) {
+      std::lock_guard<std::mutex> lk(g_registry_mutex);
+      owner->map_sharers.erase(std::remove(owner->map_sharers.begin(), owner->map_sharers.end(), s), owner->map_sharers.end());
+    }
+  }
+}
+// slots [first, first + n) of c stop referring to another context's fields (c fills them itself, or goes away)
+static void drop_shared_slots(topay_ctx* c, int first, int n) {
+  std::lock_guard<std::mutex> lk(g_registry_mutex);
+  for (int m = first; m < first + n; m++) {
+    topay_ctx* o = c->map_owner[m];
+    if (!o) continue;
+    c->map_owner[m] = nullptr;
+    bool any = false;
+    for (int q = 0; q < TOPAY_MAX_MAPS; q++) any = any || c->map_owner[q] == o;
+    if (!any) o->map_sharers.erase(std::remove(o->map_sharers.begin(), o->map_sharers.end(), c), o->map_sharers.end());
+  }
+}
+
+static int bucket_of(int N) {
+  for (int k = 0; k < topay_ctx::NBUCKET; k++)
+    if (N <= kBucketMaxN[k]) return k;
+  return topay_ctx::NBUCKET - 1;
+}
+
+// what the __constant__ parameter block of each device holds (last push)
+static DevParams g_pushed_dp[16];
+static bool g_pushed_valid[16] = {false};
+static topay_status push_params(topay_ctx* c) {
+  // Contexts of one process may carry different parameters, and the kernels read them from one __constant__ block for
+  // as long as they run: refresh it before every launch, and if a solve of another context with *different*
+  // parameters is still in flight on this device, let it finish first (contexts with equal parameters overlap freely).
+  {
+    std::lock_guard<std::mutex> lk(g_registry_mutex);
+    for (topay_ctx* q : g_contexts)
+      if (q != c && q->pending && q->device == c->device && memcmp(&q->dp, &c->dp, sizeof(DevParams)) != 0) {
+        HIPCHK(hipStreamSynchronize(q->stream));
+      }
+  }
+  HIPCHK(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_P), &c->dp, sizeof(DevParams), 0, hipMemcpyHostToDevice, c->stream));
+  g_pushed_dp[c->device % 16] = c->dp;
+  g_pushed_valid[c->device % 16] = true;
+  return TOPAY_OK;
+}
+
+extern "C" {
+
+const char* topay_last_error(void) { return g_err.c_str(); }
+
+topay_status topay_default_params(topay_params_t* p) {
+  if (!p) return TOPAY_ERR_INVALID_ARG;
+  memset(p, 0, sizeof(*p));
+  // src/planner/params/optimizer.yaml
+  p->int_K = 12; p->min_piece_num = 3; p->relu_mu = 1.0e-3; p->sample_interval = 1.5;
+  const double ew[9] = {0.33, 1, 1, 1, 1, 1, 1, 1, 1};
+  for (int i = 0; i < 9; i++) p->energy_weights[i] = ew[i];
+  p->s1_time_weight = 20.0; p->s1_moment_weight = 1000.0; p->s1_acc_weight = 1000.0; p->s1_domega_weight = 1000.0;
+  p->s1_path_pos_weight = 200000.0; p->s1_normal_past = 2; p->s1_shot_path_past = 8; p->s1_shot_path_horizon = 0.5;
+  auto lb = [](topay_lbfgs_params_t& l) {  // lbfgs.hpp:15-129 defaults
+    l.mem_size = 8; l.g_epsilon = 1.0e-5; l.past = 3; l.delta = 1.0e-6; l.max_iterations = 0; l.max_linesearch = 64;
+    l.min_step = 1.0e-20; l.max_step = 1.0e+20; l.f_dec_coeff = 1.0e-4; l.s_curv_coeff = 0.9; l.cautious_factor = 1.0e-6;
+    l.machine_prec = 1.0e-16;
+  };
+  lb(p->s1_lbfgs); lb(p->s2_lbfgs);
+  p->s1_lbfgs.mem_size = 256; p->s1_lbfgs.g_epsilon = 0.0; p->s1_lbfgs.min_step = 0.0; p->s1_lbfgs.delta = 1.0e-2;
+  p->s1_lbfgs.max_iterations = 8000; p->s1_lbfgs.past = 2;
+  p->s2_lbfgs.mem_size = 256; p->s2_lbfgs.past = 3; p->s2_lbfgs.g_epsilon = 0.0; p->s2_lbfgs.min_step = 1.0e-32;
+  p->s2_lbfgs.delta = 1.0e-4; p->s2_lbfgs.max_iterations = 8000;
+  p->s2_time_weight = 50.0; p->s2_moment_weight = 300.0; p->s2_acc_weight = 3000.0; p->s2_domega_weight = 3000.0;
+  p->s2_collision_weight = 500000.0; p->s2_mani_colli_weight = 500000.0; p->s2_self_colli_weight = 500000.0;
+  p->s2_mani_pos_weight = 500.0; p->s2_mani_vel_weight = 500.0; p->s2_mani_acc_weight = 500.0;
+  p->s2_mean_time_weight = 5000.0;
+  for (int i = 0; i < 2; i++) {
+    p->alm_init_lambda[i] = 0.0; p->alm_init_rho[i] = 1.0e4; p->alm_rho_max[i] = 1.0e10; p->alm_gamma[i] = 9.0;
+  }
+  p->alm_tolerance = 0.01;
+  p->alm_max_outer = 30;
+  p->alm_work_budget = 24000;
+  // src/simulator/fake_moma/include/fake_moma/moma_param.h:36-126
+  p->chassis_height = 0.155; p->chassis_colli_radius = 0.4;
+  p->max_v = 1.0; p->max_a = 0.8; p->max_w = 1.25; p->max_dw = 1.0;
+  const double cl[8] = {0.139, 0.1015, 0.1525, 0.1035, 0.1285, 0.0815, 0.144, 0.05};
+  const double cp[16] = {0.139 - 0.09, 0.139, 0.0, 0.1015, 0.1525 - 0.08, 0.1525, 0.0, 0.1035,
+                         0.1285 - 0.07, 0.1285, 0.0, 0.0815, 0.144 - 0.07, 0.144, 0.0, 0.1};
+  const double cr[16] = {0.06, 0.06, 0.0, 0.08, 0.04, 0.04, 0.0, 0.07, 0.035, 0.035, 0.0, 0.06, 0.035, 0.035, 0.0, 0.08};
+  for (int i = 0; i < 8; i++) p->colli_length[i] = cl[i];
+  for (int i = 0; i < 16; i++) {
+    p->colli_points[i] = cp[i];
+    p->colli_point_radius[i] = (cr[i] > 1e-4 && cr[i] < 0.055) ? 0.055 : cr[i];  // moma_param.h:110-112
+  }
+  const double qm[7] = {3.1, 2.26, 3.1, 2.355, 3.1, 2.23, 6.28};
+  for (int i = 0; i < 7; i++) { p->joint_pos_limit_max[i] = qm[i]; p->joint_vel_limit[i] = 2.35; p->joint_acc_limit[i] = 6.28; }
+  const double rr[9] = {0.7071068, 0.7071068, 0.0, -0.7071068, 0.7071068, 0.0, 0.0, 0.0, 1.0};
+  for (int i = 0; i < 9; i++) p->relative_R[i] = rr[i];
+  p->relative_t[0] = 0.0; p->relative_t[1] = 0.115; p->relative_t[2] = 0.016;
+  return TOPAY_OK;
+}
+
+topay_status topay_set_params(topay_ctx* c, const topay_params_t* params) {
+  if (!c || !params) return TOPAY_ERR_INVALID_ARG;
+  topay_status vs = validate_params(params);
+  if (vs != TOPAY_OK) return vs;
+  HIPCHK(hipSetDevice(c->device));
+  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }
+  // what the resident batch was laid out with: number of pieces (init step) and history depth (workspace)
+  const bool relayout = params->sample_interval != c->hp.sample_interval || params->min_piece_num != c->hp.min_piece_num ||
+                        std::max(params->s1_lbfgs.mem_size, params->s2_lbfgs.mem_size) != std::max(c->hp.s1_lbfgs.mem_size, c->hp.s2_lbfgs.mem_size) ||
+                        params->max_v != c->hp.max_v || params->max_a != c->hp.max_a || params->max_w != c->hp.max_w || params->max_dw != c->hp.max_dw;
+  c->hp = *params;
+  make_dev_params(*params, c->dp);
+  if (relayout) { c->have_traj = false; c->solved = false; }
+  return TOPAY_OK;
+}
+
+topay_status topay_create(const topay_params_t* params, int device, topay_ctx** out) {
+  if (!params || !out) return TOPAY_ERR_INVALID_ARG;
+  { topay_status vs = validate_params(params); if (vs != TOPAY_OK) return vs; }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    set_err("no HIP device available: the MI355X HIP path is required (there is no CPU fallback)");
+    return TOPAY_ERR_NO_DEVICE;
+  }
+  if (device < 0 || device >= ndev) { set_err("device index out of range"); return TOPAY_ERR_INVALID_ARG; }
+  HIPCHK(hipSetDevice(device));
+  topay_ctx* c = new topay_ctx();
+  c->device = device;
+  c->hp = *params;
+  make_dev_params(*params, c->dp);
+  // a failure below releases what has been created so far (topay_destroy copes with a partly built context)
+  const topay_status st = create_device_state(c, device);
+  if (st != TOPAY_OK) { topay_destroy(c); return st; }
+  {
+    std::lock_guard<std::mutex> lk(g_registry_mutex);
+    g_contexts.push_back(c);
+  }
+  *out = c;
+  return TOPAY_OK;
+}
+
+void topay_destroy(topay_ctx* c) {
+  if (!c) return;
+  if (c->pending) (void)topay_synchronize(c);
+  invalidate_sharers(c, 0, TOPAY_MAX_MAPS);
+  drop_shared_slots(c, 0, TOPAY_MAX_MAPS);
+  {
+    std::lock_guard<std::mutex> lk(g_registry_mutex);
+    g_contexts.erase(std::remove(g_contexts.begin(), g_contexts.end(), c), g_contexts.end());
+  }
+  (void)hipSetDevice(c->device);
+  for (hipEvent_t e : c->pl_events) (void)hipEventDestroy(e);
+  for (int k = 0; k < topay_ctx::NBUCKET; k++) {
+    if (c->bevent[k]) (void)hipEventDestroy(c->bevent[k]);
+    if (c->bstream[k] && c->bstream[k] != c->stream) (void)hipStreamDestroy(c->bstream[k]);
+  }
+  {
+    std::lock_guard<std::mutex> lk(g_issue_mutex);
+    if (g_last_issued == c) g_last_issued = nullptr;
+  }
+  (void)topay_comm_destroy(c);
+  if (c->h_started) (void)hipHostFree(c->h_started);
+  if (c->bstart) (void)hipEventDestroy(c->bstart);
+  if (c->ev0) (void)hipEventDestroy(c->ev0);
+  if (c->ev1) (void)hipEventDestroy(c->ev1);
+  if (c->stream) (void)hipStreamDestroy(c->stream);
+  delete c;   // the device buffers are members: freed here
+}
+
+topay_status topay_params_from_yaml(const char* path_or_text, topay_params_t* params, char* ignored, int ignored_cap) {
+  if (!path_or_text || !params) return TOPAY_ERR_INVALID_ARG;
+  std::string ign, err;
+  const topay_status s = topay_yaml::apply_source(path_or_text, params, ign, err);
+  if (s != TOPAY_OK) { set_err("topay_params_from_yaml: " + err); return s; }
+  if (ignored && ignored_cap > 0) {
+    strncpy(ignored, ign.c_str(), (size_t)ignored_cap - 1);
+    ignored[ignored_cap - 1] = 0;
+  }
+  return TOPAY_OK;
+}
+
+}  // extern "C"
