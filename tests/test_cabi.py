@@ -388,3 +388,58 @@ def test_a_destroyed_context_has_given_back_every_allocation():
     opt.close()
     assert live() == before
     tb.close()
+
+
+@pytest.fixture(scope="module")
+def three_class_batch(cuboids_small):
+    """Three candidates in three launch classes (N = 5, 12, 33: the classes N <= 10, <= 15 and <= 42) on the lane emulator,
+    laid out and then solved with a cap of three iterations per stage and one ALM round.  Shared by the layout tests below."""
+    from conftest import EMU_LIB, serpentine_path, set_map
+
+    paths = [serpentine_path(L) for L in (5.0, 12.0, 34.0)]
+    lens = np.array([len(q) for q in paths], dtype=np.int32)
+    p = api.default_params(api.load(EMU_LIB))
+    p.s1_lbfgs.max_iterations = 3
+    p.s2_lbfgs.max_iterations = 3
+    p.alm_max_outer = 1
+    emu = api.MomaTrajOptBatch(params=p, lib_path=EMU_LIB)
+    set_map(emu, cuboids_small["world"])
+    emu.set_init_traj(lens, np.concatenate(paths))
+    laid_out = dict(n_pieces=list(emu.n_pieces()), workspace=emu.workspace_bytes())
+    emu.optimizeTraj(lens, np.concatenate(paths))
+    yield emu, laid_out
+    emu.close()
+
+
+def test_workspace_of_three_launch_classes_is_unchanged(three_class_batch):
+    """Every allocation of the resident batch is sized by the layout constants of topay_types.h (kHeadLen ... kInitXyStride):
+    the sum for N = 5, 12, 33 with the default history depth is the figure the build before those constants reported for
+    this same batch (taken by running this body on commit 73de4fd)."""
+    emu, laid_out = three_class_batch
+    assert laid_out["n_pieces"] == [5, 12, 33]
+    assert laid_out["workspace"] == 2439396
+
+
+def test_candidate_views_agree_across_getters_and_gates(three_class_batch):
+    """The host's offsets and the kernels' views of a candidate's blocks: getTraj(i) (host copies at h_poff) against the slices of
+    getTrajs([0, 1, 2]) (k_gather_results), bit for bit; and the feasibility report of the gate inside the solve, then -- after
+    load_solution has invalidated it -- of the separate gate kernel, against the values commit 73de4fd gave for this batch
+    (tests/golden/cabi_layout_reports.npy: [in-solve, kernel][candidate][38], recorded with this body)."""
+    emu, _ = three_class_batch
+    pk = emu.getTrajs([0, 1, 2])
+    assert list(pk["piece_off"]) == [0, 5, 17, 50]
+    for i in range(3):
+        tr = emu.getTraj(i)
+        a, b = pk["piece_off"][i], pk["piece_off"][i + 1]
+        assert pk["durations"][a:b].tobytes() == tr["durations"].tobytes()
+        assert pk["coeffs"][a:b].tobytes() == tr["coeffs"].tobytes()
+        assert pk["knots_xy"][a + i:b + i + 1].tobytes() == tr["knots_xy"].tobytes()
+    gold = np.load(os.path.join(ROOT, "tests", "golden", "cabi_layout_reports.npy"))
+    f, st, rep = emu.check_feasible(report=True)
+    assert list(f) == [True, False, False] and list(st) == [True, False, False]
+    assert rep.tobytes() == gold[0].tobytes()
+    alm = emu.alm_state()[0]
+    emu.load_solution(0, emu.get_x(0), alm[:2], alm[2:])
+    f, st, rep = emu.check_feasible(report=True)
+    assert list(f) == [True, False, False] and list(st) == [True, False, False]
+    assert rep.tobytes() == gold[1].tobytes()

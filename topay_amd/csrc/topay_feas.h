@@ -10,7 +10,7 @@
 //      lane so that the number of samples and their values are the reference's.
 //   3. lanes <-> samples: state, velocity, acceleration, the 12 sphere centres, 1 + 12 ESDF values; lane-local
 //      extrema, wave max / min at the end.
-// report[38] = { |v|, |a|, |omega|, |domega| maxima, |q| max[7], |dq| max[7], |d2q| max[7], chassis min distance,
+// report[kReportLen] = { |v|, |a|, |omega|, |domega| maxima, |q| max[7], |dq| max[7], |d2q| max[7], chassis min distance,
 // sphere min distance[12] }.
 #pragma once
 #include "topay_eval.h"
@@ -25,7 +25,7 @@ struct FeasIO {
   double* cseq;         // scratch [(panels + 1)][2]
   double* tk;           // scratch [samples]
   long long cap_panels, cap_samples;
-  double* report;       // [38]
+  double* report;       // [kReportLen]
   int* feasible;        // [2]: printConstraintsSituations, checkFeasible
   // Counter bumped (verdicts left 0 / 0, nothing sampled) when the scratch cannot hold the trajectory's panels and sample
   // times: the in-solve gate borrows the candidate's L-BFGS history block, which a small mem_size makes short -- the host
@@ -104,7 +104,7 @@ __device__ __forceinline__ void feasibility_gate(const FeasIO& F, const TOPAY_GL
   for (int i = 0; i < N; i++) Ttot += F.T[i];  // getTotalDuration (minco.hpp:304-313)
   if (!(Ttot > 0.0 && Ttot < 1.0e4)) {         // no trajectory (failed solve left NaNs): infeasible, nothing to sample
     if (lane == 0) {
-      for (int k = 0; k < 38; k++) F.report[k] = 0.0 / 0.0;
+      for (int k = 0; k < kReportLen; k++) F.report[k] = 0.0 / 0.0;
       F.feasible[0] = 0;
       F.feasible[1] = 0;
     }
@@ -119,7 +119,7 @@ __device__ __forceinline__ void feasibility_gate(const FeasIO& F, const TOPAY_GL
   if (num > F.cap_panels || (long long)(Ttot / 0.01) + 2 > F.cap_samples) {
     // the scratch cannot hold this trajectory: nothing is sampled (a truncated sweep would miss the tail's violations)
     if (lane == 0) {
-      for (int k = 0; k < 38; k++) F.report[k] = 0.0 / 0.0;
+      for (int k = 0; k < kReportLen; k++) F.report[k] = 0.0 / 0.0;
       F.feasible[0] = 0;
       F.feasible[1] = 0;
       if (F.truncated) {

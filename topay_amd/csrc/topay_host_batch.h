@@ -10,7 +10,7 @@ static topay_status run_init(topay_ctx* c) {
   const int scratch_stride = (3 * c->Pmax + 1 + TOPAY_MAX_N) * ND;
   hipLaunchKernelGGL(k_init, dim3((B + 63) / 64), dim3(64), 0, c->stream, c->db, c->paths.as<double>(),
                      c->path_off.as<long long>(), c->path_len.as<int>(), c->bvel.as<double>(), c->bacc.as<double>(),
-                     c->scratch.as<double>(), scratch_stride, TOPAY_MAX_N, 10 * TOPAY_MAX_N - 8);
+                     c->scratch.as<double>(), scratch_stride, TOPAY_MAX_N, kX0Stride);
   HIPCHK(hipGetLastError());
   return TOPAY_OK;
 }
@@ -52,20 +52,20 @@ static topay_status set_init_traj_impl(topay_ctx* c, int batch, const int* path_
   ENS(N, (size_t)batch * 4);
   ENS(s1_past, (size_t)batch * 4);
   ENS(map_id, (size_t)batch * 4);
-  ENS(head, (size_t)batch * 27 * 8);
-  ENS(tail, (size_t)batch * 27 * 8);
+  ENS(head, (size_t)batch * kHeadLen * 8);
+  ENS(tail, (size_t)batch * kHeadLen * 8);
   ENS(start_xy, (size_t)batch * 2 * 8);
   ENS(goal_xy, (size_t)batch * 2 * 8);
-  ENS(init_xy, (size_t)batch * 2 * TOPAY_MAX_N * 8);
-  ENS(x0, (size_t)batch * (10 * TOPAY_MAX_N - 8) * 8);
+  ENS(init_xy, (size_t)batch * kInitXyStride * 8);
+  ENS(x0, (size_t)batch * kX0Stride * 8);
   ENS(order, (size_t)batch * 4);
-  HIPCHK(memcpy_sync(c, c->paths.p, init_paths, tot * 10 * 8, kind));
-  HIPCHK(memcpy_sync(c, c->path_off.p, off.data(), (size_t)(batch + 1) * 8, hipMemcpyHostToDevice));
-  HIPCHK(memcpy_sync(c, c->path_len.p, path_len, (size_t)batch * 4, hipMemcpyHostToDevice));
-  HIPCHK(memcpy_sync(c, c->map_id.p, mids.data(), (size_t)batch * 4, hipMemcpyHostToDevice));
-  if (boundary_vel) HIPCHK(memcpy_sync(c, c->bvel.p, boundary_vel, (size_t)batch * 20 * 8, kind));
+  HIPCHK(copy_sync(c, c->paths.as<double>(), init_paths, tot * 10, kind));
+  HIPCHK(h2d_sync(c, c->path_off.as<long long>(), off.data(), (size_t)(batch + 1)));
+  HIPCHK(h2d_sync(c, c->path_len.as<int>(), path_len, (size_t)batch));
+  HIPCHK(h2d_sync(c, c->map_id.as<int>(), mids.data(), (size_t)batch));
+  if (boundary_vel) HIPCHK(copy_sync(c, c->bvel.as<double>(), boundary_vel, (size_t)batch * 20, kind));
   else HIPCHK(hipMemsetAsync(c->bvel.p, 0, (size_t)batch * 20 * 8, c->stream));
-  if (boundary_acc) HIPCHK(memcpy_sync(c, c->bacc.p, boundary_acc, (size_t)batch * 20 * 8, hipMemcpyHostToDevice));
+  if (boundary_acc) HIPCHK(h2d_sync(c, c->bacc.as<double>(), boundary_acc, (size_t)batch * 20));
   else HIPCHK(hipMemsetAsync(c->bacc.p, 0, (size_t)batch * 20 * 8, c->stream));
   DevBatch& d = c->db;
   memset(&d, 0, sizeof(d));
@@ -78,7 +78,7 @@ static topay_status set_init_traj_impl(topay_ctx* c, int batch, const int* path_
   if ((s = run_init(c)) != TOPAY_OK) return s;
   HIPCHK(hipStreamSynchronize(c->stream));
   c->hN.assign(batch, 0);
-  HIPCHK(memcpy_sync(c, c->hN.data(), c->N.p, (size_t)batch * 4, hipMemcpyDeviceToHost));
+  HIPCHK(d2h_sync(c, c->hN.data(), c->N.as<int>(), (size_t)batch));
   int Nmax = 0;
   for (int b = 0; b < batch; b++) {
     if (c->hN[b] <= 0) c->hN[b] = 0;  // needs more than TOPAY_MAX_N pieces: reported as failed, never launched
@@ -111,12 +111,12 @@ static topay_status set_init_traj_impl(topay_ctx* c, int batch, const int* path_
     std::vector<int> ord;
     for (int k = topay_ctx::NBUCKET - 1; k >= 0; k--) ord.insert(ord.end(), c->cls[k].begin(), c->cls[k].end());
     ord.resize(batch, 0);
-    HIPCHK(memcpy_sync(c, c->order.p, ord.data(), (size_t)batch * 4, hipMemcpyHostToDevice));
+    HIPCHK(h2d_sync(c, c->order.as<int>(), ord.data(), (size_t)batch));
   }
   ENS(poff, ((size_t)batch + 1) * 8);
   ENS(noff, ((size_t)batch + 1) * 8);
-  HIPCHK(memcpy_sync(c, c->poff.p, c->h_poff.data(), ((size_t)batch + 1) * 8, hipMemcpyHostToDevice));
-  HIPCHK(memcpy_sync(c, c->noff.p, c->h_noff.data(), ((size_t)batch + 1) * 8, hipMemcpyHostToDevice));
+  HIPCHK(h2d_sync(c, c->poff.as<long long>(), c->h_poff.data(), ((size_t)batch + 1)));
+  HIPCHK(h2d_sync(c, c->noff.as<long long>(), c->h_noff.data(), ((size_t)batch + 1)));
   // every block sized by the candidates' own pieces / decision vectors (the history, 2 m n doubles per candidate, is
   // by far the largest: 0.4 MB at the benchmark's mean of 11 pieces, 7 MB at 170)
   ENS(x, NN * 8);
@@ -125,23 +125,23 @@ static topay_status set_init_traj_impl(topay_ctx* c, int batch, const int* path_
   ENS(hist_y, (size_t)m * NN * 8);
   ENS(hist_ys, (size_t)batch * m * 8);
   ENS(hist_alpha, (size_t)batch * m * 8);
-  ENS(lu, 84 * P * 8);
+  ENS(lu, kLuPerPiece * P * 8);
   ENS(success, (size_t)batch * 4);
   ENS(cost, (size_t)batch * 8);
-  ENS(stats, (size_t)batch * 8 * 4);
+  ENS(stats, (size_t)batch * kStatsLen * 4);
   ENS(xyerr, (size_t)batch * 2 * 8);
-  ENS(coef, 54 * P * 8);
+  ENS(coef, kCoefPerPiece * P * 8);
   ENS(T, P * 8);
   ENS(knots, 2 * (P + batch) * 8);
-  ENS(alm, (size_t)batch * 4 * 8);
+  ENS(alm, (size_t)batch * kAlmLen * 8);
   ENS(fout, (size_t)batch * 8);
-  ENS(sbuf, 14 * TOPAY_EP * P * 8);
-  ENS(mstash, 36 * TOPAY_EP * P * 8);
+  ENS(sbuf, kSbufPerPiece * P * 8);
+  ENS(mstash, kMstashPerPiece * P * 8);
   ENS(elapsed, (size_t)batch * 8);
   ENS(startus, (size_t)batch * 8);
   ENS(hwid, (size_t)batch * 4);
   ENS(feas_flags, (size_t)batch * 2 * 4);
-  ENS(feas_report, (size_t)batch * 38 * 8);
+  ENS(feas_report, (size_t)batch * kReportLen * 8);
   ENS(interrupted, (size_t)batch * 4);
 #undef ENS
   {
@@ -179,7 +179,7 @@ static topay_status set_init_traj_impl(topay_ctx* c, int batch, const int* path_
   HIPCHK(hipMemsetAsync(c->elapsed.p, 0, (size_t)batch * 8, c->stream));
   HIPCHK(hipMemsetAsync(c->success.p, 0, (size_t)batch * 4, c->stream));
   HIPCHK(hipMemsetAsync(c->cost.p, 0xFF, (size_t)batch * 8, c->stream));   // never-launched candidates: cost = NaN
-  HIPCHK(hipMemsetAsync(c->stats.p, 0, (size_t)batch * 32, c->stream));
+  HIPCHK(hipMemsetAsync(c->stats.p, 0, (size_t)batch * kStatsLen * 4, c->stream));
   c->have_traj = true;
   return TOPAY_OK;
 }
@@ -349,7 +349,7 @@ static topay_status upload_order(topay_ctx* c, bool shortest_first) {
     ord.insert(ord.end(), v.begin(), v.end());
   }
   ord.resize(c->B, 0);
-  HIPCHK(memcpy_sync(c, c->order.p, ord.data(), (size_t)c->B * 4, hipMemcpyHostToDevice));
+  HIPCHK(h2d_sync(c, c->order.as<int>(), ord.data(), (size_t)c->B));
   return TOPAY_OK;
 }
 
@@ -469,28 +469,29 @@ topay_status topay_synchronize(topay_ctx* c) {
       // the clock it saw, which was no smaller than the final one; one that ran to its end before the first success of
       // its call was published is stopped here.)
       const int B = c->B;
-      std::vector<int> succ(B), st((size_t)B * 8), fl((size_t)B * 2), intr(B), tau(c->n_groups);
-      HIPCHK(memcpy_sync(c, succ.data(), c->success.p, (size_t)B * 4, hipMemcpyDeviceToHost));
-      HIPCHK(memcpy_sync(c, st.data(), c->stats.p, (size_t)B * 32, hipMemcpyDeviceToHost));
-      HIPCHK(memcpy_sync(c, fl.data(), c->feas_flags.p, (size_t)B * 8, hipMemcpyDeviceToHost));
-      HIPCHK(memcpy_sync(c, intr.data(), c->interrupted.p, (size_t)B * 4, hipMemcpyDeviceToHost));
-      HIPCHK(memcpy_sync(c, tau.data(), c->group_tau.p, (size_t)c->n_groups * 4, hipMemcpyDeviceToHost));
+      std::vector<int> succ(B), st((size_t)B * kStatsLen), fl((size_t)B * 2), intr(B), tau(c->n_groups);
+      HIPCHK(d2h_sync(c, succ.data(), c->success.as<int>(), (size_t)B));
+      HIPCHK(d2h_sync(c, st.data(), c->stats.as<int>(), st.size()));
+      HIPCHK(d2h_sync(c, fl.data(), c->feas_flags.as<int>(), fl.size()));
+      HIPCHK(d2h_sync(c, intr.data(), c->interrupted.as<int>(), (size_t)B));
+      HIPCHK(d2h_sync(c, tau.data(), c->group_tau.as<int>(), (size_t)c->n_groups));
       bool changed = false;
       for (int b = 0; b < B; b++) {
         const int g = c->h_group[b];
         if (g < 0 || intr[b] || c->hN[b] == 0) continue;
-        const long long clock = (long long)(st[(size_t)b * 8 + 2] + st[(size_t)b * 8 + 5]) * c->hN[b];
+        const int* sb = &st[(size_t)b * kStatsLen];
+        const long long clock = (long long)(sb[2] + sb[5]) * c->hN[b];
         if (clock > (long long)tau[g] + c->cancel_budget) {
           intr[b] = 1; succ[b] = 0; fl[2 * b] = 0; fl[2 * b + 1] = 0;
-          st[(size_t)b * 8 + 3] = TOPAY_INTERRUPTED;
+          st[(size_t)b * kStatsLen + 3] = TOPAY_INTERRUPTED;
           changed = true;
         }
       }
       if (changed) {
-        HIPCHK(memcpy_sync(c, c->success.p, succ.data(), (size_t)B * 4, hipMemcpyHostToDevice));
-        HIPCHK(memcpy_sync(c, c->stats.p, st.data(), (size_t)B * 32, hipMemcpyHostToDevice));
-        HIPCHK(memcpy_sync(c, c->feas_flags.p, fl.data(), (size_t)B * 8, hipMemcpyHostToDevice));
-        HIPCHK(memcpy_sync(c, c->interrupted.p, intr.data(), (size_t)B * 4, hipMemcpyHostToDevice));
+        HIPCHK(h2d_sync(c, c->success.as<int>(), succ.data(), (size_t)B));
+        HIPCHK(h2d_sync(c, c->stats.as<int>(), st.data(), st.size()));
+        HIPCHK(h2d_sync(c, c->feas_flags.as<int>(), fl.data(), fl.size()));
+        HIPCHK(h2d_sync(c, c->interrupted.as<int>(), intr.data(), (size_t)B));
       }
     }
   }
@@ -543,7 +544,7 @@ topay_status topay_set_groups(topay_ctx* c, const int* group_id, int cancel_budg
   topay_status s;
   if ((s = c->group_id.ensure((size_t)c->B * 4)) != TOPAY_OK) return s;
   if ((s = c->group_tau.ensure((size_t)std::max(1, ng) * 4)) != TOPAY_OK) return s;
-  HIPCHK(memcpy_sync(c, c->group_id.p, dense.data(), (size_t)c->B * 4, hipMemcpyHostToDevice));
+  HIPCHK(h2d_sync(c, c->group_id.as<int>(), dense.data(), (size_t)c->B));
   c->db.group_id = c->group_id.as<int>();
   c->db.group_tau = c->group_tau.as<int>();
   // Launch order with cancellation: shortest candidates first inside every class.  Without it the longest go first (they
@@ -573,7 +574,7 @@ topay_status topay_get_interrupted(topay_ctx* c, int* interrupted) {
   if (!c || !c->have_traj || !interrupted) return TOPAY_ERR_NO_TRAJ;
   HIPCHK(hipSetDevice(c->device));
   if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }
-  HIPCHK(memcpy_sync(c, interrupted, c->interrupted.p, (size_t)c->B * 4, hipMemcpyDeviceToHost));
+  HIPCHK(d2h_sync(c, interrupted, c->interrupted.as<int>(), (size_t)c->B));
   return TOPAY_OK;
 }
 

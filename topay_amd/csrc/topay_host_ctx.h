@@ -319,7 +319,18 @@ static hipError_t memcpy_sync(topay_ctx* c, void* dst, const void* src, size_t n
   if (e != hipSuccess) return e;
   return hipStreamSynchronize(c->stream);
 }
-// Typed copies of `count` elements, asynchronous on the same stream: the byte count comes from the pointer type.
+// Typed copies of `count` elements on the same stream, the byte count from the pointer type: synchronous like memcpy_sync
+// (which stays for what really is a byte count: a struct, a whole buffer) ...
+template <typename T> static hipError_t copy_sync(topay_ctx* c, T* dst, const T* src, size_t count, hipMemcpyKind kind) {
+  return memcpy_sync(c, dst, src, count * sizeof(T), kind);
+}
+template <typename T> static hipError_t h2d_sync(topay_ctx* c, T* dst, const T* src, size_t count) {
+  return copy_sync(c, dst, src, count, hipMemcpyHostToDevice);
+}
+template <typename T> static hipError_t d2h_sync(topay_ctx* c, T* dst, const T* src, size_t count) {
+  return copy_sync(c, dst, src, count, hipMemcpyDeviceToHost);
+}
+// ... and asynchronous.
 template <typename T> static hipError_t h2d(topay_ctx* c, T* dst, const T* src, size_t count) {
   return hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyHostToDevice, c->stream);
 }

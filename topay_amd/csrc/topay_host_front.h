@@ -382,10 +382,10 @@ topay_status topay_topo_graph(topay_ctx* c, int instance, int cap, int* id, int*
   std::vector<int> t((size_t)created), k((size_t)created), nb((size_t)created * TOPAY_TOPO_MAX_NB);
   std::vector<double> pos((size_t)created * 2);
   if (created > 0) {
-    HIPCHK(memcpy_sync(c, t.data(), ti + lay.type + o, (size_t)created * 4, hipMemcpyDeviceToHost));
-    HIPCHK(memcpy_sync(c, k.data(), ti + lay.nnb + o, (size_t)created * 4, hipMemcpyDeviceToHost));
-    HIPCHK(memcpy_sync(c, nb.data(), ti + lay.nb + o * TOPAY_TOPO_MAX_NB, (size_t)created * TOPAY_TOPO_MAX_NB * 4, hipMemcpyDeviceToHost));
-    HIPCHK(memcpy_sync(c, pos.data(), c->tp_d.as<double>() + 2 * o, (size_t)created * 16, hipMemcpyDeviceToHost));
+    HIPCHK(d2h_sync(c, t.data(), ti + lay.type + o, (size_t)created));
+    HIPCHK(d2h_sync(c, k.data(), ti + lay.nnb + o, (size_t)created));
+    HIPCHK(d2h_sync(c, nb.data(), ti + lay.nb + o * TOPAY_TOPO_MAX_NB, (size_t)created * TOPAY_TOPO_MAX_NB));
+    HIPCHK(d2h_sync(c, pos.data(), c->tp_d.as<double>() + 2 * o, (size_t)created * 2));
   }
   int m = 0;
   for (int i = 0; i < created; i++) {
@@ -423,17 +423,17 @@ topay_status topay_topo_raw_paths(topay_ctx* c, int instance, int which, int cap
   *n_paths = n_keep;
   if (n_keep == 0) return TOPAY_OK;
   std::vector<int> keep((size_t)n_keep);
-  HIPCHK(memcpy_sync(c, keep.data(), d_keep + q * P.max_raw_path2, (size_t)n_keep * 4, hipMemcpyDeviceToHost));
+  HIPCHK(d2h_sync(c, keep.data(), d_keep + q * P.max_raw_path2, (size_t)n_keep));
   if (which == 0) {
     const int created = std::min(std::max(meta[0], 0), P.node_cap);
     std::vector<double> pos((size_t)created * 2);
-    HIPCHK(memcpy_sync(c, pos.data(), c->tp_d.as<double>() + 2 * q * P.node_cap, (size_t)created * 16, hipMemcpyDeviceToHost));
+    HIPCHK(d2h_sync(c, pos.data(), c->tp_d.as<double>() + 2 * q * P.node_cap, (size_t)created * 2));
     std::vector<int> rl((size_t)P.max_raw_path);
-    HIPCHK(memcpy_sync(c, rl.data(), d_rawlen + q * P.max_raw_path, rl.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(d2h_sync(c, rl.data(), d_rawlen + q * P.max_raw_path, rl.size()));
     std::vector<unsigned short> ids(TOPAY_TOPO_RAWLEN);
     for (int k = 0; k < n_keep && k < cap_paths; k++) {
       const int r = keep[k], len = std::min(std::max(rl[r], 0), TOPAY_TOPO_RAWLEN);
-      HIPCHK(memcpy_sync(c, ids.data(), c->tp_raw.as<unsigned short>() + (q * P.max_raw_path + r) * TOPAY_TOPO_RAWLEN, (size_t)len * 2, hipMemcpyDeviceToHost));
+      HIPCHK(d2h_sync(c, ids.data(), c->tp_raw.as<unsigned short>() + (q * P.max_raw_path + r) * TOPAY_TOPO_RAWLEN, (size_t)len));
       path_len[k] = len;
       for (int j = 0; j < len && j < cap_points; j++) {
         const int nd = std::min((int)ids[j], created - 1);
@@ -443,14 +443,13 @@ topay_status topay_topo_raw_paths(topay_ctx* c, int instance, int which, int cap
     }
   } else {
     std::vector<int> pl((size_t)n_keep);
-    HIPCHK(memcpy_sync(c, pl.data(), d_ptslen + q * c->tp_nbuf, (size_t)n_keep * 4, hipMemcpyDeviceToHost));
+    HIPCHK(d2h_sync(c, pl.data(), d_ptslen + q * c->tp_nbuf, (size_t)n_keep));
     for (int k = 0; k < n_keep && k < cap_paths; k++) {
       const int len = std::min(std::max(pl[k], 0), c->tp_pt_cap);
       path_len[k] = len;
       const int w = std::min(len, cap_points);
       if (w > 0)
-        HIPCHK(memcpy_sync(c, path_xy + (size_t)k * cap_points * 2, c->tp_pts.as<double>() + (q * c->tp_nbuf + k) * (size_t)c->tp_pt_cap * 2, (size_t)w * 16,
-                           hipMemcpyDeviceToHost));
+        HIPCHK(d2h_sync(c, path_xy + (size_t)k * cap_points * 2, c->tp_pts.as<double>() + (q * c->tp_nbuf + k) * (size_t)c->tp_pt_cap * 2, (size_t)w * 2));
     }
   }
   return TOPAY_OK;
@@ -527,11 +526,11 @@ topay_status topay_mcrrt_nodes(topay_ctx* c, int instance, int cap, int* layer, 
   const size_t m = (size_t)std::min(cap, c->mc_node_cap);
   const int* ni = c->mc_i.as<int>();
   const double* nd = c->mc_d.as<double>();
-  if (layer) HIPCHK(memcpy_sync(c, layer, ni + o, m * 4, hipMemcpyDeviceToHost));
-  if (state) HIPCHK(memcpy_sync(c, state, ni + nn + o, m * 4, hipMemcpyDeviceToHost));
-  if (parent) HIPCHK(memcpy_sync(c, parent, ni + 2 * nn + o, m * 4, hipMemcpyDeviceToHost));
-  if (cost) HIPCHK(memcpy_sync(c, cost, nd + o, m * 8, hipMemcpyDeviceToHost));
-  if (q) HIPCHK(memcpy_sync(c, q, nd + nn + 7 * o, m * 56, hipMemcpyDeviceToHost));
+  if (layer) HIPCHK(d2h_sync(c, layer, ni + o, m));
+  if (state) HIPCHK(d2h_sync(c, state, ni + nn + o, m));
+  if (parent) HIPCHK(d2h_sync(c, parent, ni + 2 * nn + o, m));
+  if (cost) HIPCHK(d2h_sync(c, cost, nd + o, m));
+  if (q) HIPCHK(d2h_sync(c, q, nd + nn + 7 * o, m * 7));
   return TOPAY_OK;
 }
 
@@ -549,17 +548,17 @@ topay_status topay_reeds_shepp(topay_ctx* c, int n, const double* from, const do
   };
   DevBuf d;
   if (topay_status s = d.carve(lay); s != TOPAY_OK) return s;
-  HIPCHK(memcpy_sync(c, d_from, from, (size_t)n * 24, hipMemcpyHostToDevice));
-  HIPCHK(memcpy_sync(c, d_to, to, (size_t)n * 24, hipMemcpyHostToDevice));
-  if (t) HIPCHK(memcpy_sync(c, d_t, t, (size_t)n * 8, hipMemcpyHostToDevice));
+  HIPCHK(h2d_sync(c, d_from, from, (size_t)n * 3));
+  HIPCHK(h2d_sync(c, d_to, to, (size_t)n * 3));
+  if (t) HIPCHK(h2d_sync(c, d_t, t, (size_t)n));
   hipLaunchKernelGGL(topay::k_reeds_shepp, dim3((n + 63) / 64), dim3(64), 0, c->stream, n, (const double*)d_from, (const double*)d_to,
                      t ? (const double*)d_t : (const double*)nullptr, rho, d_dist, d_word, d_len, d_pose);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
-  if (distance) HIPCHK(memcpy_sync(c, distance, d_dist, (size_t)n * 8, hipMemcpyDeviceToHost));
-  if (word) HIPCHK(memcpy_sync(c, word, d_word, (size_t)n * 4, hipMemcpyDeviceToHost));
-  if (lengths) HIPCHK(memcpy_sync(c, lengths, d_len, (size_t)n * 40, hipMemcpyDeviceToHost));
-  if (pose && t) HIPCHK(memcpy_sync(c, pose, d_pose, (size_t)n * 24, hipMemcpyDeviceToHost));
+  if (distance) HIPCHK(d2h_sync(c, distance, d_dist, (size_t)n));
+  if (word) HIPCHK(d2h_sync(c, word, d_word, (size_t)n));
+  if (lengths) HIPCHK(d2h_sync(c, lengths, d_len, (size_t)n * 5));
+  if (pose && t) HIPCHK(d2h_sync(c, pose, d_pose, (size_t)n * 3));
   return TOPAY_OK;
 }
 

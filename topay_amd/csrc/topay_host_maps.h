@@ -17,8 +17,8 @@ topay_status topay_set_map(topay_ctx* c, int map_id, const topay_map_desc_t* des
   topay_status s;
   if ((s = c->map2d[map_id].ensure(n2 * 8)) != TOPAY_OK) return s;
   if ((s = c->map3d[map_id].ensure(n3 * 8)) != TOPAY_OK) return s;
-  HIPCHK(memcpy_sync(c, c->map2d[map_id].p, esdf2d, n2 * 8, hipMemcpyHostToDevice));
-  HIPCHK(memcpy_sync(c, c->map3d[map_id].p, esdf3d, n3 * 8, hipMemcpyHostToDevice));
+  HIPCHK(h2d_sync(c, c->map2d[map_id].as<double>(), esdf2d, n2));
+  HIPCHK(h2d_sync(c, c->map3d[map_id].as<double>(), esdf3d, n3));
   DevMap& m = c->hmaps[map_id];
   for (int i = 0; i < 3; i++) {
     m.origin[i] = desc->origin[i]; m.dims[i] = desc->dims[i];
@@ -301,8 +301,8 @@ topay_status topay_get_map_fields(topay_ctx* c, int map_id, double* esdf2d_infla
   if (!m.esdf2d_inflate || !m.esdf2d_critical) { set_err("map slot was not built by topay_build_esdf*"); return TOPAY_ERR_NO_MAP; }
   HIPCHK(hipSetDevice(c->device));
   const size_t n2 = (size_t)m.dims[0] * m.dims[1];
-  if (esdf2d_inflate) HIPCHK(memcpy_sync(c, esdf2d_inflate, (const void*)m.esdf2d_inflate, n2 * 8, hipMemcpyDeviceToHost));
-  if (esdf2d_critical) HIPCHK(memcpy_sync(c, esdf2d_critical, (const void*)m.esdf2d_critical, n2 * 8, hipMemcpyDeviceToHost));
+  if (esdf2d_inflate) HIPCHK(d2h_sync(c, esdf2d_inflate, (const double*)m.esdf2d_inflate, n2));
+  if (esdf2d_critical) HIPCHK(d2h_sync(c, esdf2d_critical, (const double*)m.esdf2d_critical, n2));
   return TOPAY_OK;
 }
 
@@ -312,8 +312,8 @@ topay_status topay_get_map(topay_ctx* c, int map_id, double* esdf2d, double* esd
   HIPCHK(hipSetDevice(c->device));
   const DevMap& m = c->hmaps[map_id];
   const size_t n2 = (size_t)m.dims[0] * m.dims[1], n3 = n2 * m.dims[2];
-  if (esdf2d) HIPCHK(memcpy_sync(c, esdf2d, (const void*)m.esdf2d, n2 * 8, hipMemcpyDeviceToHost));
-  if (esdf3d) HIPCHK(memcpy_sync(c, esdf3d, (const void*)m.esdf3d, n3 * 8, hipMemcpyDeviceToHost));
+  if (esdf2d) HIPCHK(d2h_sync(c, esdf2d, (const double*)m.esdf2d, n2));
+  if (esdf3d) HIPCHK(d2h_sync(c, esdf3d, (const double*)m.esdf3d, n3));
   if (build_ms) *build_ms = c->last_edt_ms;
   return TOPAY_OK;
 }

@@ -269,17 +269,17 @@ static topay_status plan_try(topay_ctx* c, int t, const std::vector<int>& act, c
   hipLaunchKernelGGL(topay::k_plan_winner, dim3((Q + 63) / 64), dim3(64), 0, c->stream, c->db, Q, (const int*)d_first, (const int*)d_count, d_stage, d_win, d_wcd);
   HIPCHK(hipGetLastError());
   clk.end(id);
-  std::vector<int> win(Q), stage(B), sst((size_t)B * 8);
+  std::vector<int> win(Q), stage(B), sst((size_t)B * kStatsLen);
   std::vector<double> hw(2 * (size_t)Q);
   HIPCHK(d2h(c, win.data(), d_win, (size_t)Q));
   HIPCHK(d2h(c, stage.data(), d_stage, (size_t)B));
   HIPCHK(d2h(c, hw.data(), d_wcd, 2 * (size_t)Q));
-  HIPCHK(d2h(c, sst.data(), c->stats.as<int>(), 8 * (size_t)B));
+  HIPCHK(d2h(c, sst.data(), c->stats.as<int>(), sst.size()));
   HIPCHK(hipStreamSynchronize(c->stream));
   if (cand)
     for (int b = 0; b < B; b++) {
       int* e = cand + (((size_t)T.call[b] * 2 + t) * 8 + T.k[b]) * 4;
-      e[0] = stage[b]; e[1] = c->hN[b]; e[3] = c->hN[b] > 0 ? sst[(size_t)b * 8 + 3] : 0;
+      e[0] = stage[b]; e[1] = c->hN[b]; e[3] = c->hN[b] > 0 ? sst[(size_t)b * kStatsLen + 3] : 0;
     }
   // ---- the winners into the store: trajectories in the layout of k_gather_results, init paths after them
   std::vector<int> widx, woff{0}, foff{0};
@@ -302,7 +302,7 @@ static topay_status plan_try(topay_ctx* c, int t, const std::vector<int>& act, c
   const int W = (int)widx.size();
   if (W == 0) return TOPAY_OK;
   const size_t np = (size_t)woff.back(), P0 = c->ps_pieces, W0 = c->ps_winners, F0 = c->ps_states;
-  if ((s = grow_keep(c, c->ps_dur, (P0 + np) * 8, P0 * 8)) != TOPAY_OK || (s = grow_keep(c, c->ps_coef, (P0 + np) * 54 * 8, P0 * 54 * 8)) != TOPAY_OK ||
+  if ((s = grow_keep(c, c->ps_dur, (P0 + np) * 8, P0 * 8)) != TOPAY_OK || (s = grow_keep(c, c->ps_coef, (P0 + np) * kCoefPerPiece * 8, P0 * kCoefPerPiece * 8)) != TOPAY_OK ||
       (s = grow_keep(c, c->ps_kn, 2 * (P0 + W0 + np + W) * 8, 2 * (P0 + W0) * 8)) != TOPAY_OK ||
       (s = grow_keep(c, c->ps_front, (F0 + (size_t)foff.back()) * 80, F0 * 80)) != TOPAY_OK)
     return s;
@@ -314,7 +314,7 @@ static topay_status plan_try(topay_ctx* c, int t, const std::vector<int>& act, c
   HIPCHK(h2d(c, d_foff, foff.data(), (size_t)W + 1));
   id = clk.begin(7);
   hipLaunchKernelGGL(k_gather_results, dim3(W), dim3(64), 0, c->stream, c->db, W, (const int*)d_idx, (const int*)d_woff, c->ps_dur.as<double>() + P0,
-                     c->ps_coef.as<double>() + 54 * P0, c->ps_kn.as<double>() + 2 * (P0 + W0));
+                     c->ps_coef.as<double>() + kCoefPerPiece * P0, c->ps_kn.as<double>() + 2 * (P0 + W0));
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(topay::k_plan_gather_front, dim3(W), dim3(64), 0, c->stream, W, (const int*)d_idx, (const double*)c->paths.as<double>(),
                      (const long long*)c->path_off.as<long long>(), (const int*)d_foff, c->ps_front.as<double>() + 10 * F0);
@@ -405,11 +405,11 @@ topay_status topay_plan_get_trajs(topay_ctx* c, int n, const int* call_idx, int 
   if (np > cap_pieces) { set_err("topay_plan_get_trajs: cap_pieces too small for the selection"); return TOPAY_ERR_INVALID_ARG; }
   if (!durations && !coeffs && !knots_xy) return TOPAY_OK;
   HIPCHK(hipSetDevice(c->device));
-  const size_t kn = (size_t)2 * (np + n), dbl = (size_t)np + (size_t)np * 54 + kn;
+  const size_t kn = (size_t)2 * (np + n), dbl = (size_t)np + (size_t)np * kCoefPerPiece + kn;
   int *d_sp, *d_sk, *d_off; double *d_dur, *d_coef, *d_kn;
   auto lay = [&](Carver& k) {
     d_sp = k.take<int>((size_t)n); d_sk = k.take<int>((size_t)n); d_off = k.take<int>((size_t)n + 1);
-    d_dur = k.take<double>((size_t)np); d_coef = k.take<double>((size_t)np * 54); d_kn = k.take<double>(kn);   // (contiguous: one copy back)
+    d_dur = k.take<double>((size_t)np); d_coef = k.take<double>((size_t)np * kCoefPerPiece); d_kn = k.take<double>(kn);   // (contiguous: one copy back)
   };
   if (topay_status s = c->pb_io.carve(lay); s != TOPAY_OK) return s;
   HIPCHK(h2d(c, d_sp, sp.data(), (size_t)n));
@@ -422,10 +422,10 @@ topay_status topay_plan_get_trajs(topay_ctx* c, int n, const int* call_idx, int 
     HIPCHK(hipGetLastError());
   }
   std::vector<double> host(dbl);
-  HIPCHK(memcpy_sync(c, host.data(), d_dur, dbl * 8, hipMemcpyDeviceToHost));
+  HIPCHK(d2h_sync(c, host.data(), d_dur, dbl));
   if (durations) memcpy(durations, host.data(), (size_t)np * 8);
-  if (coeffs) memcpy(coeffs, host.data() + np, (size_t)np * 54 * 8);
-  if (knots_xy) memcpy(knots_xy, host.data() + np + (size_t)np * 54, (size_t)2 * (np + n) * 8);
+  if (coeffs) memcpy(coeffs, host.data() + np, (size_t)np * kCoefPerPiece * 8);
+  if (knots_xy) memcpy(knots_xy, host.data() + np + (size_t)np * kCoefPerPiece, kn * 8);
   return TOPAY_OK;
 }
 
@@ -438,7 +438,7 @@ topay_status topay_plan_get_front_path(topay_ctx* c, int call, int cap_states, i
   const int w = std::min(e.front_len, cap_states);
   if (w > 0 && states) {
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(memcpy_sync(c, states, c->ps_front.as<double>() + 10 * (size_t)e.front0, (size_t)w * 80, hipMemcpyDeviceToHost));
+    HIPCHK(d2h_sync(c, states, c->ps_front.as<double>() + 10 * (size_t)e.front0, (size_t)w * 10));
   }
   return TOPAY_OK;
 }

@@ -24,15 +24,15 @@ static topay_status eval_one(topay_ctx* c, int stage, int i, const double* x, co
   if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }   // inputs of a solve in flight stay untouched
   const int N = c->hN[i], nn = 10 * N - 8;
   if (N == 0) return TOPAY_ERR_TOO_MANY_PIECES;
-  HIPCHK(memcpy_sync(c, c->x.as<double>() + c->h_noff[i], x, (size_t)nn * 8, hipMemcpyHostToDevice));
-  double alm[4] = {alm_lambda ? alm_lambda[0] : c->hp.alm_init_lambda[0], alm_lambda ? alm_lambda[1] : c->hp.alm_init_lambda[1],
+  HIPCHK(h2d_sync(c, c->db.x_of(c->h_noff[i]), x, (size_t)nn));
+  double alm[kAlmLen] = {alm_lambda ? alm_lambda[0] : c->hp.alm_init_lambda[0], alm_lambda ? alm_lambda[1] : c->hp.alm_init_lambda[1],
                    alm_rho ? alm_rho[0] : c->hp.alm_init_rho[0], alm_rho ? alm_rho[1] : c->hp.alm_init_rho[1]};
-  HIPCHK(memcpy_sync(c, c->alm.as<double>() + (size_t)i * 4, alm, 32, hipMemcpyHostToDevice));
+  HIPCHK(h2d_sync(c, c->db.alm_of(i), alm, kAlmLen));
   // single-block launch through a one-entry order array placed at the end of the order buffer
   DevBuf tmp;
   topay_status s = tmp.ensure(4);
   if (s != TOPAY_OK) return s;
-  HIPCHK(memcpy_sync(c, tmp.p, &i, 4, hipMemcpyHostToDevice));
+  HIPCHK(h2d_sync(c, tmp.as<int>(), &i, 1));
   DevBatch d = c->db;
   d.order = tmp.as<int>();
   ClassDef cd = kClassTable[bucket_of(N)];   // the class (kernel, waves per trajectory) that also solves this candidate
@@ -44,9 +44,9 @@ static topay_status eval_one(topay_ctx* c, int stage, int i, const double* x, co
   hipLaunchKernelGGL(cd.eval, dim3(1), dim3(64 * cd.nw), lds, c->stream, d, (const DevMap*)c->dmaps.p, stage | (commit ? 16 : 0), 1, N);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
-  if (f) HIPCHK(memcpy_sync(c, f, c->fout.as<double>() + i, 8, hipMemcpyDeviceToHost));
-  if (g) HIPCHK(memcpy_sync(c, g, c->work.as<double>() + 4 * c->h_noff[i], (size_t)nn * 8, hipMemcpyDeviceToHost));
-  if (final_xy_error) HIPCHK(memcpy_sync(c, final_xy_error, c->xyerr.as<double>() + 2 * i, 16, hipMemcpyDeviceToHost));
+  if (f) HIPCHK(d2h_sync(c, f, c->fout.as<double>() + i, 1));
+  if (g) HIPCHK(d2h_sync(c, g, c->db.work_of(c->h_noff[i]), (size_t)nn));
+  if (final_xy_error) HIPCHK(d2h_sync(c, final_xy_error, c->db.xyerr_of(i), 2));
   return TOPAY_OK;
 }
 
@@ -62,8 +62,8 @@ topay_status topay_get_nmax(topay_ctx* c, int* nmax, int* Nmax) {
 topay_status topay_get_batch(topay_ctx* c, int* success, double* cost, int* n_pieces) {
   if (!c || !c->have_traj) return TOPAY_ERR_NO_TRAJ;
   HIPCHK(hipSetDevice(c->device));
-  if (success) HIPCHK(memcpy_sync(c, success, c->success.p, (size_t)c->B * 4, hipMemcpyDeviceToHost));
-  if (cost) HIPCHK(memcpy_sync(c, cost, c->cost.p, (size_t)c->B * 8, hipMemcpyDeviceToHost));
+  if (success) HIPCHK(d2h_sync(c, success, c->success.as<int>(), (size_t)c->B));
+  if (cost) HIPCHK(d2h_sync(c, cost, c->cost.as<double>(), (size_t)c->B));
   if (n_pieces) memcpy(n_pieces, c->hN.data(), (size_t)c->B * 4);
   return TOPAY_OK;
 }
@@ -71,9 +71,9 @@ topay_status topay_get_batch(topay_ctx* c, int* success, double* cost, int* n_pi
 topay_status topay_get_elapsed_us(topay_ctx* c, double* us, double* start_us, int* hw_id) {
   if (!c || !c->have_traj) return TOPAY_ERR_NO_TRAJ;
   HIPCHK(hipSetDevice(c->device));
-  if (us) HIPCHK(memcpy_sync(c, us, c->elapsed.p, (size_t)c->B * 8, hipMemcpyDeviceToHost));
-  if (start_us) HIPCHK(memcpy_sync(c, start_us, c->startus.p, (size_t)c->B * 8, hipMemcpyDeviceToHost));
-  if (hw_id) HIPCHK(memcpy_sync(c, hw_id, c->hwid.p, (size_t)c->B * 4, hipMemcpyDeviceToHost));
+  if (us) HIPCHK(d2h_sync(c, us, c->elapsed.as<double>(), (size_t)c->B));
+  if (start_us) HIPCHK(d2h_sync(c, start_us, c->startus.as<double>(), (size_t)c->B));
+  if (hw_id) HIPCHK(d2h_sync(c, hw_id, c->hwid.as<int>(), (size_t)c->B));
   return TOPAY_OK;
 }
 
@@ -85,7 +85,7 @@ topay_status topay_playback(topay_ctx* c, int i, int n_times, const double* time
   if (i < 0 || i >= c->B || n_times < 0 || (n_times > 0 && (!times || !states))) return TOPAY_ERR_INVALID_ARG;
   HIPCHK(hipSetDevice(c->device));
   std::vector<double> hT((size_t)std::max(1, c->hN[i]));
-  if (c->hN[i] > 0) HIPCHK(memcpy_sync(c, hT.data(), c->T.as<double>() + c->h_poff[i], (size_t)c->hN[i] * 8, hipMemcpyDeviceToHost));
+  if (c->hN[i] > 0) HIPCHK(d2h_sync(c, hT.data(), c->db.T_of(c->h_poff[i]), (size_t)c->hN[i]));
   double t = 0.0;
   for (int k = 0; k < c->hN[i]; k++) t += hT[k];
   if (!(t > 0.0 && t < 1.0e4)) t = 0.0;
@@ -107,10 +107,10 @@ topay_status topay_playback(topay_ctx* c, int i, int n_times, const double* time
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
   int ns = 0;
-  HIPCHK(memcpy_sync(c, &ns, d_nseq, 4, hipMemcpyDeviceToHost));
+  HIPCHK(d2h_sync(c, &ns, d_nseq, 1));
   if (n_seq) *n_seq = ns;
-  if (seq && ns > 0) HIPCHK(memcpy_sync(c, seq, d_seq, (size_t)std::min(ns, seq_cap) * 4 * 8, hipMemcpyDeviceToHost));
-  if (n_times) HIPCHK(memcpy_sync(c, states, d_states, (size_t)n_times * 10 * 8, hipMemcpyDeviceToHost));
+  if (seq && ns > 0) HIPCHK(d2h_sync(c, seq, d_seq, (size_t)std::min(ns, seq_cap) * 4));
+  if (n_times) HIPCHK(d2h_sync(c, states, d_states, (size_t)n_times * 10));
   return TOPAY_OK;
 }
 
@@ -157,7 +157,7 @@ topay_status topay_mesh_traj(topay_ctx* c, int i, const topay_mesh_params_t* mes
   if (i < 0 || i >= c->B || !mesh || res <= 0 || cap_states < res + 1 || !parts || !yaws || !arc_lengths || !n_states) return TOPAY_ERR_INVALID_ARG;
   HIPCHK(hipSetDevice(c->device));
   std::vector<double> hT((size_t)std::max(1, c->hN[i]));
-  if (c->hN[i] > 0) HIPCHK(memcpy_sync(c, hT.data(), c->T.as<double>() + c->h_poff[i], (size_t)c->hN[i] * 8, hipMemcpyDeviceToHost));
+  if (c->hN[i] > 0) HIPCHK(d2h_sync(c, hT.data(), c->db.T_of(c->h_poff[i]), (size_t)c->hN[i]));
   double T = 0.0;
   for (int k = 0; k < c->hN[i]; k++) T += hT[k];
   if (!(T > 0.0 && T < 1.0e4)) { *n_states = 0; return TOPAY_OK; }
@@ -188,7 +188,7 @@ topay_status topay_get_total_durations(topay_ctx* c, double* total) {
   if (!c || !c->have_traj || !total) return TOPAY_ERR_NO_TRAJ;
   HIPCHK(hipSetDevice(c->device));
   std::vector<double> hT((size_t)c->h_poff[c->B] + 1);
-  HIPCHK(memcpy_sync(c, hT.data(), c->T.p, (size_t)c->h_poff[c->B] * 8, hipMemcpyDeviceToHost));
+  HIPCHK(d2h_sync(c, hT.data(), c->T.as<double>(), (size_t)c->h_poff[c->B]));
   for (int b = 0; b < c->B; b++) {
     double t = 0.0;
     for (int i = 0; i < c->hN[b]; i++) t += hT[(size_t)c->h_poff[b] + i];  // PolyTrajectory::getTotalDuration, minco.hpp:304-313
@@ -200,14 +200,14 @@ topay_status topay_get_total_durations(topay_ctx* c, double* total) {
 topay_status topay_get_alm(topay_ctx* c, double* alm) {
   if (!c || !c->have_traj || !alm) return TOPAY_ERR_NO_TRAJ;
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(memcpy_sync(c, alm, c->alm.p, (size_t)c->B * 32, hipMemcpyDeviceToHost));
+  HIPCHK(d2h_sync(c, alm, c->alm.as<double>(), (size_t)c->B * kAlmLen));
   return TOPAY_OK;
 }
 
 topay_status topay_get_stats(topay_ctx* c, int* stats) {
   if (!c || !c->have_traj || !stats) return TOPAY_ERR_NO_TRAJ;
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(memcpy_sync(c, stats, c->stats.p, (size_t)c->B * 32, hipMemcpyDeviceToHost));
+  HIPCHK(d2h_sync(c, stats, c->stats.as<int>(), (size_t)c->B * kStatsLen));
   return TOPAY_OK;
 }
 
@@ -224,20 +224,20 @@ topay_status topay_get_result(topay_ctx* c, int i, int* success, double* cost, i
     if (n_pieces) *n_pieces = 0;
     return TOPAY_OK;
   }
-  if (success) HIPCHK(memcpy_sync(c, success, c->success.as<int>() + i, 4, hipMemcpyDeviceToHost));
-  if (cost) HIPCHK(memcpy_sync(c, cost, c->cost.as<double>() + i, 8, hipMemcpyDeviceToHost));
+  if (success) HIPCHK(d2h_sync(c, success, c->success.as<int>() + i, 1));
+  if (cost) HIPCHK(d2h_sync(c, cost, c->cost.as<double>() + i, 1));
   if (n_pieces) *n_pieces = N;
-  if (durations) HIPCHK(memcpy_sync(c, durations, c->T.as<double>() + c->h_poff[i], (size_t)N * 8, hipMemcpyDeviceToHost));
+  if (durations) HIPCHK(d2h_sync(c, durations, c->db.T_of(c->h_poff[i]), (size_t)N));
   if (coeffs) {
     std::vector<double> cm((size_t)9 * rows);
-    HIPCHK(memcpy_sync(c, cm.data(), c->coef.as<double>() + 54 * c->h_poff[i], cm.size() * 8, hipMemcpyDeviceToHost));
+    HIPCHK(d2h_sync(c, cm.data(), c->db.coef_of(c->h_poff[i]), cm.size()));
     // getTraj(): per piece the 6x9 block transposed, highest order first — minco.hpp:908-921
     for (int p = 0; p < N; p++)
       for (int d = 0; d < 9; d++)
         for (int k = 0; k < 6; k++) coeffs[((size_t)p * 9 + d) * 6 + k] = cm[(size_t)d * rows + 6 * p + 5 - k];
   }
   if (knots_xy)
-    HIPCHK(memcpy_sync(c, knots_xy, c->knots.as<double>() + 2 * (c->h_poff[i] + i), (size_t)2 * (N + 1) * 8, hipMemcpyDeviceToHost));
+    HIPCHK(d2h_sync(c, knots_xy, c->db.knots_of(c->h_poff[i], i), (size_t)2 * (N + 1)));
   return TOPAY_OK;
 }
 
@@ -259,11 +259,11 @@ topay_status topay_get_results(topay_ctx* c, int n, const int* idx, int cap_piec
   if (np > cap_pieces) { set_err("topay_get_results: cap_pieces too small for the selection"); return TOPAY_ERR_INVALID_ARG; }
   if (np == 0 || (!durations && !coeffs && !knots_xy)) return TOPAY_OK;
   // device staging: idx | piece_off | durations | coeffs | knots, one kernel, one copy back
-  const size_t kn = (size_t)2 * (np + n), dbl = (size_t)np + (size_t)np * 54 + kn;
+  const size_t kn = (size_t)2 * (np + n), dbl = (size_t)np + (size_t)np * kCoefPerPiece + kn;
   int *d_idx, *d_off; double *d_dur, *d_coef, *d_kn;
   auto lay = [&](Carver& k) {
     d_idx = k.take<int>((size_t)n); d_off = k.take<int>((size_t)n + 1);
-    d_dur = k.take<double>((size_t)np); d_coef = k.take<double>((size_t)np * 54); d_kn = k.take<double>(kn);   // (contiguous: one copy back)
+    d_dur = k.take<double>((size_t)np); d_coef = k.take<double>((size_t)np * kCoefPerPiece); d_kn = k.take<double>(kn);   // (contiguous: one copy back)
   };
   if (topay_status s = c->pb_io.carve(lay); s != TOPAY_OK) return s;
   HIPCHK(h2d(c, d_idx, idx, (size_t)n));
@@ -274,10 +274,10 @@ topay_status topay_get_results(topay_ctx* c, int n, const int* idx, int cap_piec
                      d_coef, d_kn);
   HIPCHK(hipGetLastError());
   std::vector<double> host(dbl);
-  HIPCHK(memcpy_sync(c, host.data(), d_dur, dbl * 8, hipMemcpyDeviceToHost));
+  HIPCHK(d2h_sync(c, host.data(), d_dur, dbl));
   if (durations) memcpy(durations, host.data(), (size_t)np * 8);
-  if (coeffs) memcpy(coeffs, host.data() + np, (size_t)np * 54 * 8);
-  if (knots_xy) memcpy(knots_xy, host.data() + np + (size_t)np * 54, (size_t)2 * (np + n) * 8);
+  if (coeffs) memcpy(coeffs, host.data() + np, (size_t)np * kCoefPerPiece * 8);
+  if (knots_xy) memcpy(knots_xy, host.data() + np + (size_t)np * kCoefPerPiece, kn * 8);
   return TOPAY_OK;
 }
 
@@ -290,16 +290,17 @@ topay_status topay_get_polytraj_msg(topay_ctx* c, int i, int cap_pieces, unsigne
   if (order) *order = 5;
   if (N == 0) return TOPAY_OK;
   if (N > cap_pieces) return TOPAY_ERR_INVALID_ARG;
-  std::vector<double> dur((size_t)N), cf((size_t)N * 54);
+  constexpr int CP = kCoefPerPiece;
+  std::vector<double> dur((size_t)N), cf((size_t)N * CP);
   topay_status s = topay_get_result(c, i, nullptr, nullptr, nullptr, dur.data(), cf.data(), nullptr);
   if (s != TOPAY_OK) return s;
   for (int p = 0; p < N; p++) {
     if (durations) durations[p] = (float)dur[p];
     if (coeff)
-      for (int t = 0; t < 54; t++) coeff[(size_t)p * 54 + t] = (float)cf[(size_t)p * 54 + t];
+      for (int t = 0; t < CP; t++) coeff[(size_t)p * CP + t] = (float)cf[(size_t)p * CP + t];
     if (directions) {
       // arc-length rate (dimension 1) at the middle of the piece; coefficients are highest order first
-      const double* a = &cf[(size_t)p * 54 + 6], t = 0.5 * dur[p];
+      const double* a = &cf[(size_t)p * CP + 6], t = 0.5 * dur[p];
       const double sd = ((((5.0 * a[0]) * t + 4.0 * a[1]) * t + 3.0 * a[2]) * t + 2.0 * a[3]) * t + a[4];
       directions[p] = sd < 0.0 ? -1 : 1;
     }
@@ -316,8 +317,8 @@ topay_status topay_get_x(topay_ctx* c, int i, int* n, double* x) {
   if (n) *n = nn;
   if (x) {
     // after optimize: the final iterate; before: the packed initial guess
-    if (c->solved) HIPCHK(memcpy_sync(c, x, c->x.as<double>() + c->h_noff[i], (size_t)nn * 8, hipMemcpyDeviceToHost));
-    else HIPCHK(memcpy_sync(c, x, c->x0.as<double>() + (size_t)i * (10 * TOPAY_MAX_N - 8), (size_t)nn * 8, hipMemcpyDeviceToHost));
+    if (c->solved) HIPCHK(d2h_sync(c, x, c->db.x_of(c->h_noff[i]), (size_t)nn));
+    else HIPCHK(d2h_sync(c, x, c->db.x0_of(i), (size_t)nn));
   }
   return TOPAY_OK;
 }
@@ -346,7 +347,7 @@ topay_status topay_load_solution(topay_ctx* c, int i, const double* x, const dou
     c->solved = true;
     c->gate_done = false;   // (the gate of a loaded trajectory: the separate kernel)
     const int zero = 0;     // the candidate has a trajectory now, whatever a solve before left in its flag
-    HIPCHK(memcpy_sync(c, c->interrupted.as<int>() + i, &zero, 4, hipMemcpyHostToDevice));
+    HIPCHK(h2d_sync(c, c->interrupted.as<int>() + i, &zero, 1));
   }
   return s;
 }
@@ -358,17 +359,18 @@ topay_status topay_eval_batch(topay_ctx* c, int stage, int repeats, double* f) {
   HIPCHK(hipSetDevice(c->device));
   if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }   // inputs of a solve in flight stay untouched
   // x <- x0 (strided copy), alm <- init
-  std::vector<double> x0((size_t)c->B * (10 * TOPAY_MAX_N - 8)), xs((size_t)c->h_noff[c->B] + 1, 0.0), alm((size_t)c->B * 4);
-  HIPCHK(memcpy_sync(c, x0.data(), c->x0.p, x0.size() * 8, hipMemcpyDeviceToHost));
+  std::vector<double> x0((size_t)c->B * kX0Stride), xs((size_t)c->h_noff[c->B] + 1, 0.0), alm((size_t)c->B * kAlmLen);
+  HIPCHK(d2h_sync(c, x0.data(), c->x0.as<double>(), x0.size()));
   for (int b = 0; b < c->B; b++) {
     if (c->hN[b] == 0) continue;
     const int nn = 10 * c->hN[b] - 8;
-    memcpy(&xs[(size_t)c->h_noff[b]], &x0[(size_t)b * (10 * TOPAY_MAX_N - 8)], (size_t)nn * 8);
-    alm[4 * b] = c->hp.alm_init_lambda[0]; alm[4 * b + 1] = c->hp.alm_init_lambda[1];
-    alm[4 * b + 2] = c->hp.alm_init_rho[0]; alm[4 * b + 3] = c->hp.alm_init_rho[1];
+    memcpy(&xs[(size_t)c->h_noff[b]], &x0[(size_t)b * kX0Stride], (size_t)nn * 8);
+    double* ab = &alm[(size_t)kAlmLen * b];
+    ab[0] = c->hp.alm_init_lambda[0]; ab[1] = c->hp.alm_init_lambda[1];
+    ab[2] = c->hp.alm_init_rho[0]; ab[3] = c->hp.alm_init_rho[1];
   }
-  HIPCHK(memcpy_sync(c, c->x.p, xs.data(), (size_t)c->h_noff[c->B] * 8, hipMemcpyHostToDevice));
-  HIPCHK(memcpy_sync(c, c->alm.p, alm.data(), alm.size() * 8, hipMemcpyHostToDevice));
+  HIPCHK(h2d_sync(c, c->x.as<double>(), xs.data(), (size_t)c->h_noff[c->B]));
+  HIPCHK(h2d_sync(c, c->alm.as<double>(), alm.data(), alm.size()));
   HIPCHK(hipEventRecord(c->ev0, c->stream));
   topay_status s = launch_classes<true>(c, false, stage, repeats);
   if (s != TOPAY_OK) return s;
@@ -377,7 +379,7 @@ topay_status topay_eval_batch(topay_ctx* c, int stage, int repeats, double* f) {
   float ms = 0.f;
   HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
   c->last_ms = ms;
-  if (f) HIPCHK(memcpy_sync(c, f, c->fout.p, (size_t)c->B * 8, hipMemcpyDeviceToHost));
+  if (f) HIPCHK(d2h_sync(c, f, c->fout.as<double>(), (size_t)c->B));
   return TOPAY_OK;
 }
 
@@ -391,17 +393,17 @@ topay_status topay_feasibility_report(topay_ctx* c, int* feasible, int* strict, 
   const int B = c->B;
   if (c->gate_done) {   // the solving waves have gated their own trajectories: verdicts and extremes are resident
     std::vector<int> fl((size_t)B * 2);
-    HIPCHK(memcpy_sync(c, fl.data(), c->feas_flags.p, fl.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(d2h_sync(c, fl.data(), c->feas_flags.as<int>(), fl.size()));
     for (int b = 0; b < B; b++) {
       if (feasible) feasible[b] = fl[2 * b];
       if (strict) strict[b] = fl[2 * b + 1];
     }
-    if (report) HIPCHK(memcpy_sync(c, report, c->feas_report.p, (size_t)B * 38 * 8, hipMemcpyDeviceToHost));
+    if (report) HIPCHK(d2h_sync(c, report, c->feas_report.as<double>(), (size_t)B * kReportLen));
     return TOPAY_OK;
   }
   // scratch is sized from the longest returned trajectory
   std::vector<double> hT((size_t)c->h_poff[B] + 1);
-  HIPCHK(memcpy_sync(c, hT.data(), c->T.p, (size_t)c->h_poff[B] * 8, hipMemcpyDeviceToHost));
+  HIPCHK(d2h_sync(c, hT.data(), c->T.as<double>(), (size_t)c->h_poff[B]));
   double tmax = 0.0;
   for (int b = 0; b < B; b++) {
     double t = 0.0;
@@ -412,7 +414,7 @@ topay_status topay_feasibility_report(topay_ctx* c, int* feasible, int* strict, 
   topay_status s;
   if ((s = c->feas_cseq.ensure((size_t)B * 2 * (cap_panels + 1) * 8)) != TOPAY_OK) return s;
   if ((s = c->feas_tk.ensure((size_t)B * cap_samples * 8)) != TOPAY_OK) return s;
-  if ((s = c->feas_report.ensure((size_t)B * 38 * 8)) != TOPAY_OK) return s;
+  if ((s = c->feas_report.ensure((size_t)B * kReportLen * 8)) != TOPAY_OK) return s;
   if ((s = c->feas_flags.ensure((size_t)B * 2 * 4)) != TOPAY_OK) return s;
   topay_status ps = push_params(c);
   if (ps != TOPAY_OK) return ps;
@@ -421,20 +423,20 @@ topay_status topay_feasibility_report(topay_ctx* c, int* feasible, int* strict, 
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
   std::vector<int> fl((size_t)B * 2), intr(B);
-  HIPCHK(memcpy_sync(c, fl.data(), c->feas_flags.p, fl.size() * 4, hipMemcpyDeviceToHost));
+  HIPCHK(d2h_sync(c, fl.data(), c->feas_flags.as<int>(), fl.size()));
   // an interrupted candidate has no trajectory (its result block holds the spline of the evaluation it was stopped in):
   // its verdicts stay 0 / 0, as the in-solve path and the cancellation post-pass of topay_synchronize write them
-  HIPCHK(memcpy_sync(c, intr.data(), c->interrupted.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+  HIPCHK(d2h_sync(c, intr.data(), c->interrupted.as<int>(), (size_t)B));
   bool changed = false;
   for (int b = 0; b < B; b++)
     if (intr[b] && (fl[2 * b] || fl[2 * b + 1])) { fl[2 * b] = 0; fl[2 * b + 1] = 0; changed = true; }
-  if (changed) HIPCHK(memcpy_sync(c, c->feas_flags.p, fl.data(), fl.size() * 4, hipMemcpyHostToDevice));
+  if (changed) HIPCHK(h2d_sync(c, c->feas_flags.as<int>(), fl.data(), fl.size()));
   c->gate_done = true;   // resident until the next solve, load or re-initialisation (each resets it)
   for (int b = 0; b < B; b++) {
     if (feasible) feasible[b] = fl[2 * b];
     if (strict) strict[b] = fl[2 * b + 1];
   }
-  if (report) HIPCHK(memcpy_sync(c, report, c->feas_report.p, (size_t)B * 38 * 8, hipMemcpyDeviceToHost));
+  if (report) HIPCHK(d2h_sync(c, report, c->feas_report.as<double>(), (size_t)B * kReportLen));
   return TOPAY_OK;
 }
 
@@ -457,7 +459,7 @@ topay_status topay_set_trace(topay_ctx* c, int cap) {
 topay_status topay_get_trace(topay_ctx* c, int i, double* out) {
   if (!c || !c->have_traj || c->trace_cap <= 0 || i < 0 || i >= c->B) return TOPAY_ERR_INVALID_ARG;
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(memcpy_sync(c, out, c->trace.as<double>() + (size_t)i * c->trace_cap, (size_t)c->trace_cap * 8, hipMemcpyDeviceToHost));
+  HIPCHK(d2h_sync(c, out, c->trace.as<double>() + (size_t)i * c->trace_cap, (size_t)c->trace_cap));
   return TOPAY_OK;
 }
 
@@ -470,12 +472,12 @@ topay_status topay_test_math(topay_ctx* c, int n, const double* a, const double*
   if ((s = da.ensure((size_t)n * 8)) != TOPAY_OK || (s = dbb.ensure((size_t)n * 8)) != TOPAY_OK ||
       (s = dout.ensure((size_t)n * 32)) != TOPAY_OK)
     return s;
-  HIPCHK(memcpy_sync(c, da.p, a, (size_t)n * 8, hipMemcpyHostToDevice));
-  HIPCHK(memcpy_sync(c, dbb.p, b, (size_t)n * 8, hipMemcpyHostToDevice));
+  HIPCHK(h2d_sync(c, da.as<double>(), a, (size_t)n));
+  HIPCHK(h2d_sync(c, dbb.as<double>(), b, (size_t)n));
   hipLaunchKernelGGL(k_math, dim3((n + 63) / 64), dim3(64), 0, c->stream, da.as<double>(), dbb.as<double>(), dout.as<double>(), n);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
-  HIPCHK(memcpy_sync(c, out4n, dout.p, (size_t)n * 32, hipMemcpyDeviceToHost));
+  HIPCHK(d2h_sync(c, out4n, dout.as<double>(), (size_t)n * 4));
   return TOPAY_OK;
 }
 

@@ -33,10 +33,11 @@ __global__ void k_init(DevBatch Bt, const double* paths, const long long* path_o
                        const double* bvel, const double* bacc, double* scratch, int scratch_stride, int maxN, int stride_n) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= Bt.B) return;
+  // (init_xy and x0 by the strides the host passes -- TOPAY_MAX_N and kX0Stride, those of init_xy_of / x0_of: with the views
+  // this image's compiler gives this kernel other code)
   init_one(g_P, paths + path_off[b] * 10, path_len[b], bvel + (size_t)b * 20, bacc + (size_t)b * 20,
-           scratch + (size_t)b * scratch_stride, maxN, Bt.N + b, Bt.s1_past + b, Bt.head + (size_t)b * 27,
-           Bt.tail + (size_t)b * 27, Bt.start_xy + 2 * b, Bt.goal_xy + 2 * b, Bt.init_xy + (size_t)b * 2 * maxN,
-           Bt.x0 + (size_t)b * stride_n);
+           scratch + (size_t)b * scratch_stride, maxN, Bt.N + b, Bt.s1_past + b, Bt.head_of(b), Bt.tail_of(b),
+           Bt.start_xy + 2 * b, Bt.goal_xy + 2 * b, Bt.init_xy + (size_t)b * 2 * maxN, Bt.x0 + (size_t)b * stride_n);
 }
 
 // Where candidate b's variable-length blocks start: every per-candidate array is packed by the candidate's own size
@@ -52,9 +53,9 @@ __host__ __device__ __forceinline__ int eval_lds_doubles(int Nmax_lds) {
   return lds_doubles_mw(Nmax_lds, NW);
 }
 
-template <int RMAX, int NW>
+// The candidate's blocks (DevBatch views) and the evaluation's LDS blocks into the context of its workgroup of NW waves
+template <int NW>
 __device__ __forceinline__ void load_ctx(EvalCtx& C, const DevBatch& Bt, int b, int Nmax_lds) {
-  constexpr int NT = 64 * NW;
   C.tid = threadIdx.x;
   C.lane = threadIdx.x & 63;
   C.wave = threadIdx.x >> 6;
@@ -64,15 +65,17 @@ __device__ __forceinline__ void load_ctx(EvalCtx& C, const DevBatch& Bt, int b, 
   C.red = nullptr; C.adj = nullptr; C.cl_in_lds = 1;
   carve_mw(C, TOPAY_LDS_PTR, Nmax_lds, NW);
   fill_power_table(C.pw, C.lane);
-  C.hd = (glb_cdp)(Bt.head + (size_t)b * 27);
-  C.tl = (glb_cdp)(Bt.tail + (size_t)b * 27);
+  // (spelled out, like the FeasIO of solve_one: through head_of / tail_of this image's compiler gives the solve kernels another
+  // schedule; worth another try with the next compiler)
+  C.hd = (glb_cdp)(Bt.head + (size_t)b * kHeadLen);
+  C.tl = (glb_cdp)(Bt.tail + (size_t)b * kHeadLen);
   const long long po = uniform_i64(Bt.poff[b]);
-  C.lu = (glb_dp)(Bt.lu + 84 * po);
+  C.lu = (glb_dp)Bt.lu_of(po);
   C.sb_stride = TOPAY_EP * C.N;
-  C.sbuf = (glb_dp)(Bt.sbuf + 14 * TOPAY_EP * po);
-  C.mstash = (glb_dp)(Bt.mstash + 36 * TOPAY_EP * po);
-  C.coefg = (glb_dp)(Bt.coef + 54 * po);
-  C.init_xy = (glb_cdp)(Bt.init_xy + (size_t)b * 2 * TOPAY_MAX_N);
+  C.sbuf = (glb_dp)Bt.sbuf_of(po);
+  C.mstash = (glb_dp)Bt.mstash_of(po);
+  C.coefg = (glb_dp)Bt.coef_of(po);
+  C.init_xy = (glb_cdp)Bt.init_xy_of(b);
   C.sx = Bt.start_xy[2 * b]; C.sy = Bt.start_xy[2 * b + 1];
   C.ex = Bt.goal_xy[2 * b];  C.ey = Bt.goal_xy[2 * b + 1];
   C.fxe0 = 0.0; C.fxe1 = 0.0;
@@ -93,11 +96,11 @@ __device__ __forceinline__ void store_result(const EvalCtx& C, const DevBatch& B
   const long long po = uniform_i64(Bt.poff[b]);
   // (after a gradient phase the coefficients already sit in the result block, C.cL holds the adjoint)
   if (C.cl_in_lds) {
-    double* coef = Bt.coef + 54 * po;
+    double* coef = Bt.coef_of(po);
     for (int t = C.tid; t < 9 * rows; t += NT) coef[t] = C.cL[t];
   }
   for (int t = C.tid; t < N; t += NT) Bt.T[po + t] = C.Tp[t];
-  double* kn = Bt.knots + 2 * (po + b);
+  double* kn = Bt.knots_of(po, b);
   if (C.tid == 0) { kn[0] = C.sx; kn[1] = C.sy; }
   for (int t = C.tid; t < 2 * N; t += NT) kn[2 + t] = C.pcs[2 * N + 2 + t];
 }
@@ -109,12 +112,13 @@ __device__ __forceinline__ void eval_body(const DevBatch& Bt, const DevMap* maps
   const bool commit = (stage & 16) != 0;
   stage &= 15;
   EvalCtx C;
-  load_ctx<RMAX, NW>(C, Bt, b, Nmax_lds);
+  load_ctx<NW>(C, Bt, b, Nmax_lds);
   const TOPAY_GLB DevMap* mp = (const TOPAY_GLB DevMap*)(maps + __builtin_amdgcn_readfirstlane(Bt.map_id[b]));
   const long long no = uniform_i64(Bt.noff[b]);
-  C.x = (glb_cdp)(Bt.x + no);
-  C.g = (glb_dp)(Bt.work + 4 * no);
-  C.lam0 = Bt.alm[4 * b]; C.lam1 = Bt.alm[4 * b + 1]; C.rho0 = Bt.alm[4 * b + 2]; C.rho1 = Bt.alm[4 * b + 3];
+  C.x = (glb_cdp)Bt.x_of(no);
+  C.g = (glb_dp)Bt.work_of(no);
+  const double* alm = Bt.alm_of(b);
+  C.lam0 = alm[0]; C.lam1 = alm[1]; C.rho0 = alm[2]; C.rho1 = alm[3];
   __syncthreads();
   double f = 0.0;
   // (negative repeats: cost only -- the gate then answers "gradient not needed", as for a rejected line-search trial)
@@ -130,14 +134,29 @@ __device__ __forceinline__ void eval_body(const DevBatch& Bt, const DevMap* maps
   }
   if (C.tid == 0) {
     Bt.fout[b] = f;
-    Bt.xyerr[2 * b] = C.fxe0;
-    Bt.xyerr[2 * b + 1] = C.fxe1;
+    Bt.xyerr_of(b)[0] = C.fxe0;
+    Bt.xyerr_of(b)[1] = C.fxe1;
   }
   if (commit) {   // topay_load_solution: the spline of this x becomes the candidate's result, as after a solve that ended here
     __syncthreads();
     store_result<NW>(C, Bt, b);
     if (C.tid == 0) { Bt.cost[b] = f; Bt.success[b] = 1; }
   }
+}
+
+// The trajectory a gate or a playback of candidate b reads: its result blocks and start pose; scratch and outputs null,
+// for the caller to set.
+__device__ __forceinline__ FeasIO feas_io_of(const DevBatch& Bt, int b, long long po) {
+  FeasIO F;
+  F.coef = Bt.coef_of(po);
+  F.T = Bt.T_of(po);
+  F.N = Bt.N[b];
+  F.x0 = Bt.start_xy[2 * b]; F.y0 = Bt.start_xy[2 * b + 1];
+  F.th0 = Bt.head_of(b)[0];
+  F.cseq = nullptr; F.tk = nullptr;
+  F.cap_panels = 0; F.cap_samples = 0;
+  F.report = nullptr; F.feasible = nullptr; F.truncated = nullptr;
+  return F;
 }
 
 // The gate inside the solve kernel is a call: inlined, its 9 000 instructions and their live ranges became part of the
@@ -161,23 +180,23 @@ __device__ __forceinline__ void solve_one(const DevBatch& Bt, const DevMap* maps
 #endif
   }
   EvalCtx C;
-  load_ctx<RMAX_E, NWE>(C, Bt, b, Nmax_lds);
+  load_ctx<NWE>(C, Bt, b, Nmax_lds);
   const TOPAY_GLB DevMap* mp = (const TOPAY_GLB DevMap*)(maps + __builtin_amdgcn_readfirstlane(Bt.map_id[b]));
   lds_dp pf = TOPAY_LDS_PTR + eval_lds_doubles<NWE>(Nmax_lds);  // [8] past costs, then [40] solver state parked across an evaluation (+ the command block of the helper-wave kernels)
   const long long no = uniform_i64(Bt.noff[b]);
   const int n = C.n;
   SolveIO S;
-  S.x = (glb_dp)(Bt.x + no);
-  S.g = (glb_dp)(Bt.work + 4 * no);
-  S.xp = (glb_dp)(Bt.work + 4 * no + n);
-  S.gp = (glb_dp)(Bt.work + 4 * no + 2 * (long long)n);
-  S.d = (glb_dp)(Bt.work + 4 * no + 3 * (long long)n);
-  S.hist_s = (glb_dp)(Bt.hist_s + (long long)Bt.hist_m * no);
-  S.hist_y = (glb_dp)(Bt.hist_y + (long long)Bt.hist_m * no);
-  S.hist_ys = (glb_dp)(Bt.hist_ys + (size_t)b * Bt.hist_m);
-  S.hist_al = (glb_dp)(Bt.hist_alpha + (size_t)b * Bt.hist_m);
+  S.x = (glb_dp)Bt.x_of(no);
+  S.g = (glb_dp)Bt.work_of(no);
+  S.xp = (glb_dp)(Bt.work_of(no) + n);
+  S.gp = (glb_dp)(Bt.work_of(no) + 2 * (long long)n);
+  S.d = (glb_dp)(Bt.work_of(no) + 3 * (long long)n);
+  S.hist_s = (glb_dp)Bt.hist_s_of(no);
+  S.hist_y = (glb_dp)Bt.hist_y_of(no);
+  S.hist_ys = (glb_dp)Bt.hist_ys_of(b);
+  S.hist_al = (glb_dp)Bt.hist_alpha_of(b);
   S.nstride = n;
-  S.stats = (glb_ip)(Bt.stats + (size_t)b * 8);
+  S.stats = (glb_ip)Bt.stats_of(b);
   S.trace = Bt.trace ? (glb_dp)(Bt.trace + (size_t)b * Bt.trace_cap) : (glb_dp)nullptr;
   S.trace_cap = Bt.trace_cap;
   const int grp = Bt.group_id ? __builtin_amdgcn_readfirstlane(Bt.group_id[b]) : -1;
@@ -186,7 +205,7 @@ __device__ __forceinline__ void solve_one(const DevBatch& Bt, const DevMap* maps
   S.cancel_budget = Bt.cancel_budget;
   // x <- x0
   {
-    const double* x0 = Bt.x0 + (size_t)b * (10 * TOPAY_MAX_N - 8);
+    const double* x0 = Bt.x0_of(b);
     for (int e = C.tid; e < C.n; e += NT) S.x[e] = x0[e];
   }
   int success = 0, interrupted = 0;
@@ -207,23 +226,25 @@ __device__ __forceinline__ void solve_one(const DevBatch& Bt, const DevMap* maps
     // printConstraintsSituations of the returned trajectory (planner.cpp:878-880) by wave 0, from the result blocks just
     // written; panels and sample times go to the candidate's L-BFGS history blocks, which are dead now
     __syncthreads();
-    int* fl = Bt.feas_flags + 2 * b;
+    int* fl = Bt.flags_of(b);
     if (interrupted) {
       if (C.tid == 0) { fl[0] = 0; fl[1] = 0; }
     } else if (threadIdx.x < 64) {
       const long long po = uniform_i64(Bt.poff[b]);
       const long long hist_doubles = (long long)Bt.hist_m * C.n;
+      // (field by field, not feas_io_of: N and the start are the context's, and with this image's compiler the builder changes
+      // the solve kernels' schedule)
       FeasIO F;
-      F.coef = Bt.coef + 54 * po;
-      F.T = Bt.T + po;
+      F.coef = Bt.coef_of(po);
+      F.T = Bt.T_of(po);
       F.N = C.N;
       F.x0 = C.sx; F.y0 = C.sy;
-      F.th0 = Bt.head[(size_t)b * 27];
-      F.cseq = Bt.hist_s + (long long)Bt.hist_m * no;
-      F.tk = Bt.hist_y + (long long)Bt.hist_m * no;
+      F.th0 = Bt.head_of(b)[0];
+      F.cseq = Bt.hist_s_of(no);
+      F.tk = Bt.hist_y_of(no);
       F.cap_panels = hist_doubles / 2 - 1;
       F.cap_samples = hist_doubles;
-      F.report = Bt.feas_report + (size_t)b * 38;
+      F.report = Bt.report_of(b);
       F.feasible = fl;
       F.truncated = Bt.gate_truncated;
       feasibility_gate_in_solve<OCC>(F, mp);
@@ -242,9 +263,9 @@ __device__ __forceinline__ void solve_one(const DevBatch& Bt, const DevMap* maps
     if (Bt.interrupted) Bt.interrupted[b] = interrupted;
     Bt.success[b] = success;
     Bt.cost[b] = cost;
-    Bt.xyerr[2 * b] = C.fxe0;
-    Bt.xyerr[2 * b + 1] = C.fxe1;
-    Bt.alm[4 * b] = C.lam0; Bt.alm[4 * b + 1] = C.lam1; Bt.alm[4 * b + 2] = C.rho0; Bt.alm[4 * b + 3] = C.rho1;
+    Bt.xyerr_of(b)[0] = C.fxe0;
+    Bt.xyerr_of(b)[1] = C.fxe1;
+    Bt.alm_of(b)[0] = C.lam0; Bt.alm_of(b)[1] = C.lam1; Bt.alm_of(b)[2] = C.rho0; Bt.alm_of(b)[3] = C.rho1;
     Bt.elapsed_us[b] = (double)(wall_clock64() - t_begin) * 0.01;
     Bt.start_us[b] = (double)t_begin * 0.01;
 #ifndef TOPAY_CPU_EMU
@@ -297,12 +318,12 @@ __device__ __forceinline__ void drain_queues(const DevBatch& B, const DevMap* ma
       if (cancelled && pos < count) {   // interrupted before its first evaluation: no trajectory, success 0, verdicts 0 / 0
         if (threadIdx.x == 0) {
           const int b = B.order[off + pos];
-          int* st = B.stats + (size_t)b * 8;
-          for (int q = 0; q < 8; q++) st[q] = 0;
+          int* st = B.stats_of(b);
+          for (int q = 0; q < kStatsLen; q++) st[q] = 0;
           st[3] = TOPAY_INTERRUPTED;
           if (B.interrupted) B.interrupted[b] = 1;
           B.success[b] = 0;
-          if (B.gate_in_solve) { B.feas_flags[2 * b] = 0; B.feas_flags[2 * b + 1] = 0; }
+          if (B.gate_in_solve) { B.flags_of(b)[0] = 0; B.flags_of(b)[1] = 0; }
         }
         continue;
       }
@@ -320,6 +341,8 @@ __device__ __forceinline__ void drain_queues(const DevBatch& B, const DevMap* ma
 // length); a resident workgroup that fetches its next candidate itself leaves no slot idle and starts candidates
 // strictly in queue order.  Which workgroup solves which candidate is timing-dependent, the result of a candidate is
 // not (nothing is shared between candidates).
+// (solve_body and eval_lds_doubles above are one-line wrappers that stay: with this image's compiler the solve kernels' code
+// changes without either; worth another try with the next compiler)
 template <int RMAX, int OCC, int NWE = 1, int RMAX_E = RMAX>
 __device__ __forceinline__ void solve_body(const DevBatch& Bt, const DevMap* maps, int Nmax_lds) {
   drain_queues<RMAX, OCC, NWE, RMAX_E>(Bt, maps, Nmax_lds, Bt.queue_class);   // the batch is the kernel argument (scalar loads, no copy)
@@ -378,18 +401,12 @@ __global__ void __launch_bounds__(64, 2) k_feasible(DevBatch Bt, const DevMap* m
     if (threadIdx.x == 0) { flags[2 * b] = 0; flags[2 * b + 1] = 0; }
     return;
   }
-  FeasIO F;
-  F.coef = Bt.coef + 54 * Bt.poff[b];
-  F.T = Bt.T + Bt.poff[b];
-  F.N = N;
-  F.x0 = Bt.start_xy[2 * b]; F.y0 = Bt.start_xy[2 * b + 1];
-  F.th0 = Bt.head[(size_t)b * 27];
+  FeasIO F = feas_io_of(Bt, b, Bt.poff[b]);
   F.cseq = cseq + (size_t)b * 2 * (cap_panels + 1);
   F.tk = tk + (size_t)b * cap_samples;
   F.cap_panels = cap_panels; F.cap_samples = cap_samples;
-  F.report = report + (size_t)b * 38;
+  F.report = report + (size_t)b * kReportLen;
   F.feasible = flags + 2 * b;
-  F.truncated = nullptr;
   const TOPAY_GLB DevMap* mp = (const TOPAY_GLB DevMap*)(maps + __builtin_amdgcn_readfirstlane(Bt.map_id[b]));
   feasibility_gate(F, mp);
 }
@@ -411,18 +428,9 @@ __global__ void __launch_bounds__(64) k_playback(DevBatch Bt, int b, double* cse
     if (threadIdx.x == 0) *nseq_out = 0;
     return;
   }
-  FeasIO F;
-  F.coef = Bt.coef + 54 * Bt.poff[b];
-  F.T = Bt.T + Bt.poff[b];
-  F.N = N;
-  F.x0 = Bt.start_xy[2 * b]; F.y0 = Bt.start_xy[2 * b + 1];
-  F.th0 = Bt.head[(size_t)b * 27];
+  FeasIO F = feas_io_of(Bt, b, Bt.poff[b]);
   F.cseq = cseq;
-  F.tk = nullptr;
-  F.cap_panels = cap_panels; F.cap_samples = 0;
-  F.report = nullptr;
-  F.feasible = nullptr;
-  F.truncated = nullptr;
+  F.cap_panels = cap_panels;
   playback(F, nq, times, states, seq_out, nseq_out);
 }
 
@@ -435,13 +443,15 @@ __global__ void k_gather_results(DevBatch Bt, int n, const int* idx, const int* 
   const int N = piece_off[k + 1] - piece_off[k];
   if (N <= 0) return;
   const int rows = 6 * N, p0 = piece_off[k];
-  const double* cm = Bt.coef + 54 * Bt.poff[b];   // [9][rows], element d * rows + 6 p + k = coefficient of t^k
-  for (int t = threadIdx.x; t < N * 54; t += blockDim.x) {
-    const int p = t / 54, r = t - 54 * p, d = r / 6, kk = r - 6 * d;
-    coeffs[(size_t)p0 * 54 + t] = cm[(size_t)d * rows + 6 * p + 5 - kk];   // per piece 9 x 6, highest order first
+  const long long po = Bt.poff[b];
+  const double* cm = Bt.coef_of(po);   // [9][rows], element d * rows + 6 p + k = coefficient of t^k
+  constexpr int CP = kCoefPerPiece;
+  for (int t = threadIdx.x; t < N * CP; t += blockDim.x) {
+    const int p = t / CP, r = t - CP * p, d = r / 6, kk = r - 6 * d;
+    coeffs[(size_t)p0 * CP + t] = cm[(size_t)d * rows + 6 * p + 5 - kk];   // per piece 9 x 6, highest order first
   }
-  for (int t = threadIdx.x; t < N; t += blockDim.x) durations[p0 + t] = Bt.T[Bt.poff[b] + t];
-  for (int t = threadIdx.x; t < 2 * (N + 1); t += blockDim.x) knots[2 * (size_t)(p0 + k) + t] = Bt.knots[2 * (Bt.poff[b] + b) + t];
+  for (int t = threadIdx.x; t < N; t += blockDim.x) durations[p0 + t] = Bt.T_of(po)[t];
+  for (int t = threadIdx.x; t < 2 * (N + 1); t += blockDim.x) knots[2 * (size_t)(p0 + k) + t] = Bt.knots_of(po, b)[t];
 }
 
 // GridMap::isWholeBodyCollision for a batch of states

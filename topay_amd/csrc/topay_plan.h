@@ -123,10 +123,10 @@ __global__ void k_plan_winner(DevBatch Bt, int n_calls, const int* first, const 
     double dur = 0.0;
     if (N <= 0) st = PLAN_TOO_MANY_PIECES;
     else {
-      for (int i = 0; i < N; i++) dur += Bt.T[Bt.poff[b] + i];
+      for (int i = 0; i < N; i++) dur += Bt.T_of(Bt.poff[b])[i];
       if (Bt.interrupted[b]) st = PLAN_INTERRUPTED;
       else if (!Bt.success[b]) st = PLAN_SOLVER_FAILED;
-      else if (!Bt.feas_flags[2 * b]) st = PLAN_GATE_FAILED;
+      else if (!Bt.flags_of(b)[0]) st = PLAN_GATE_FAILED;
       else st = PLAN_COUNTS;
     }
     stage[b] = st;
@@ -156,7 +156,7 @@ __global__ void k_plan_store_gather(int n, const int* src_piece, const int* src_
   const int N = piece_off[k + 1] - piece_off[k];
   if (N <= 0) return;
   const int p0 = piece_off[k], sp = src_piece[k], sk = src_knot[k];
-  for (int t = threadIdx.x; t < N * 54; t += blockDim.x) coeffs[(size_t)p0 * 54 + t] = s_coef[(size_t)sp * 54 + t];
+  for (int t = threadIdx.x; t < N * kCoefPerPiece; t += blockDim.x) coeffs[(size_t)p0 * kCoefPerPiece + t] = s_coef[(size_t)sp * kCoefPerPiece + t];
   for (int t = threadIdx.x; t < N; t += blockDim.x) durations[p0 + t] = s_dur[sp + t];
   for (int t = threadIdx.x; t < 2 * (N + 1); t += blockDim.x) knots[2 * (size_t)(p0 + k) + t] = s_kn[2 * (size_t)sk + t];
 }

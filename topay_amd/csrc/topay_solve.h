@@ -815,7 +815,7 @@ __device__ __forceinline__ void init_one(const DevParams& P, const double* path,
   init_xy[2 * ninner] = goal_xy[0];
   init_xy[2 * ninner + 1] = goal_xy[1];
   // boundary PVA — moma_traj_opt.cpp:281-297
-  for (int q = 0; q < 27; q++) { head[q] = 0.0; tail[q] = 0.0; }
+  for (int q = 0; q < kHeadLen; q++) { head[q] = 0.0; tail[q] = 0.0; }
   const double* n0 = nodes;
   const double* nl = nodes + (size_t)(path_num - 1) * ND;
   head[0 * 9 + 0] = n0[2];

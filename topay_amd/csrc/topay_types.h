@@ -99,6 +99,19 @@ struct DevParams {
   double joint_vel_limit2[7], joint_acc_limit2[7];
 };
 
+// Element counts of the batch's blocks, stated once: per candidate (fixed-size blocks) and per piece (packed blocks).  The
+// DevBatch views below and the host's allocations and copies are written in these.
+constexpr int kHeadLen = 27;                        // head / tail: 9 x 3 col-major boundary PVA
+constexpr int kReportLen = 38;                      // feas_report (topay_feas.h)
+constexpr int kStatsLen = 8;                        // stats
+constexpr int kAlmLen = 4;                          // alm: lambda0,1 rho0,1
+constexpr int kCoefPerPiece = 54;                   // coef: 6 rows x 9 dimensions (also a piece of the packed getTraj() output)
+constexpr int kLuPerPiece = 84;                     // lu: 14 (band + reciprocal diagonal) x 6 rows
+constexpr int kSbufPerPiece = 14 * TOPAY_EP;        // sbuf: 14 parked gradient rows of the piece's even samples
+constexpr int kMstashPerPiece = 36 * TOPAY_EP;      // mstash: 36 pair forces per even sample
+constexpr int kX0Stride = 10 * TOPAY_MAX_N - 8;     // x0: strided by the longest decision vector (written before N is known)
+constexpr int kInitXyStride = 2 * TOPAY_MAX_N;      // init_xy
+
 // Per-batch device arrays.  Fixed-size blocks are indexed by the candidate; the variable-length ones (everything sized
 // by the candidate's pieces N or its decision vector n = 10 N - 8) are packed by the candidate's own size, at the
 // offsets poff[b] = pieces of the candidates before b and noff[b] = decision-vector elements before b -- not strided by
@@ -111,12 +124,12 @@ struct DevBatch {
   int* N;             // [B] pieces
   int* s1_past;       // [B]
   int* map_id;        // [B]
-  double* head;       // [B][27]  9x3 col-major start PVA
-  double* tail;       // [B][27]
+  double* head;       // [B][kHeadLen]  9x3 col-major start PVA
+  double* tail;       // [B][kHeadLen]
   double* start_xy;   // [B][2]
   double* goal_xy;    // [B][2]
-  double* init_xy;    // [B][TOPAY_MAX_N][2]
-  double* x0;         // [B][10 TOPAY_MAX_N - 8]  packed initial decision vector (written before N is known)
+  double* init_xy;    // [B][kInitXyStride]  TOPAY_MAX_N points
+  double* x0;         // [B][kX0Stride]  packed initial decision vector (written before N is known)
   // solver state
   double* x;          // [noff]  n per candidate
   double* work;       // [4 noff]  g, xp, gp, d (n each) per candidate
@@ -124,19 +137,19 @@ struct DevBatch {
   double* hist_y;     // [m noff]
   double* hist_ys;    // [B][m]
   double* hist_alpha; // [B][m]
-  double* lu;         // [84 poff]  LU stash (band + reciprocal diagonal), 14 x 6N per candidate
+  double* lu;         // [kLuPerPiece poff]  LU stash (band + reciprocal diagonal), 14 x 6N per candidate
   // outputs
   int* success;       // [B]
   double* cost;       // [B]
-  int* stats;         // [B][8]
+  int* stats;         // [B][kStatsLen]
   double* xyerr;      // [B][2]
-  double* coef;       // [54 poff]  6N x 9 col-major per candidate
+  double* coef;       // [kCoefPerPiece poff]  6N x 9 col-major per candidate
   double* T;          // [poff]
   double* knots;      // [2 (poff + b)]  N + 1 knots per candidate
-  double* alm;        // [B][4] lambda0,1 rho0,1 (eval hook input / solver output)
+  double* alm;        // [B][kAlmLen] lambda0,1 rho0,1 (eval hook input / solver output)
   double* fout;       // [B] eval hook output
-  double* sbuf;       // [182 poff]  [14][13 N] per-sample gradient rows parked between the cost and the gradient phase
-  double* mstash;     // [468 poff]  [13 N][36] forces of self-colliding sphere pairs of a sample (rarely touched, topay_eval.h)
+  double* sbuf;       // [kSbufPerPiece poff]  [14][TOPAY_EP N] per-sample gradient rows parked between the cost and the gradient phase
+  double* mstash;     // [kMstashPerPiece poff]  [TOPAY_EP N][36] forces of self-colliding sphere pairs of a sample (rarely touched, topay_eval.h)
   double* start_us;   // [B] start of the solve on the device's constant clock (scheduling diagnostics)
   // persistent launches: one queue per N-class = positions [queue_off[k], queue_off[k] + queue_count[k]) of `order`, handed
   // out through the device counters queue_next[k]; a workgroup of class queue_class drains its own queue, then the
@@ -150,7 +163,7 @@ struct DevBatch {
   int gate_in_solve;   // always 1: the field and its tests stay until a change that may alter the solve kernels' code (it moves every later kernel argument)
   int* gate_truncated; // one counter in pinned host memory: candidates whose history block was too short for the gate's scratch
   int* feas_flags;    // [B][2]
-  double* feas_report;// [B][38]
+  double* feas_report;// [B][kReportLen]
   // Cancellation (planner.cpp:943-952: the candidates of one planning call that are still running 100 ms after the first
   // success are interrupted).  group_id[b] = planning call of candidate b (-1: none); group_tau[g] = smallest work clock
   // (piece-evaluations, the unit of alm_work_budget) at which a candidate of g finished successfully AND passed the gate;
@@ -168,4 +181,29 @@ struct DevBatch {
   const int* order;   // [B] block -> trajectory map
   double* trace;      // optional [B][trace_cap] f of every evaluation (debug / parity tooling), may be null
   int trace_cap;
+
+  // Candidate views: where candidate b's block starts.  The packed blocks take the candidate's offsets po = poff[b] / no = noff[b]
+  // from the caller (a kernel holds them wave-uniform in scalar registers, the host in h_poff / h_noff): no view loads them.
+  // The work block holds g, xp, gp, d at +0, +n, +2n, +3n.
+  __host__ __device__ __forceinline__ double* head_of(int b) const { return head + (size_t)b * kHeadLen; }
+  __host__ __device__ __forceinline__ double* tail_of(int b) const { return tail + (size_t)b * kHeadLen; }
+  __host__ __device__ __forceinline__ double* init_xy_of(int b) const { return init_xy + (size_t)b * kInitXyStride; }
+  __host__ __device__ __forceinline__ double* x0_of(int b) const { return x0 + (size_t)b * kX0Stride; }
+  __host__ __device__ __forceinline__ int* stats_of(int b) const { return stats + (size_t)b * kStatsLen; }
+  __host__ __device__ __forceinline__ double* alm_of(int b) const { return alm + kAlmLen * b; }
+  __host__ __device__ __forceinline__ double* xyerr_of(int b) const { return xyerr + 2 * b; }
+  __host__ __device__ __forceinline__ int* flags_of(int b) const { return feas_flags + 2 * b; }
+  __host__ __device__ __forceinline__ double* report_of(int b) const { return feas_report + (size_t)b * kReportLen; }
+  __host__ __device__ __forceinline__ double* hist_ys_of(int b) const { return hist_ys + (size_t)b * hist_m; }
+  __host__ __device__ __forceinline__ double* hist_alpha_of(int b) const { return hist_alpha + (size_t)b * hist_m; }
+  __host__ __device__ __forceinline__ double* coef_of(long long po) const { return coef + kCoefPerPiece * po; }
+  __host__ __device__ __forceinline__ double* T_of(long long po) const { return T + po; }
+  __host__ __device__ __forceinline__ double* knots_of(long long po, int b) const { return knots + 2 * (po + b); }
+  __host__ __device__ __forceinline__ double* lu_of(long long po) const { return lu + kLuPerPiece * po; }
+  __host__ __device__ __forceinline__ double* sbuf_of(long long po) const { return sbuf + kSbufPerPiece * po; }
+  __host__ __device__ __forceinline__ double* mstash_of(long long po) const { return mstash + kMstashPerPiece * po; }
+  __host__ __device__ __forceinline__ double* x_of(long long no) const { return x + no; }
+  __host__ __device__ __forceinline__ double* work_of(long long no) const { return work + 4 * no; }
+  __host__ __device__ __forceinline__ double* hist_s_of(long long no) const { return hist_s + (long long)hist_m * no; }
+  __host__ __device__ __forceinline__ double* hist_y_of(long long no) const { return hist_y + (long long)hist_m * no; }
 };
