@@ -196,6 +196,83 @@ topay_status topay_build_esdf_fields(topay_ctx* ctx, int n_maps, int first_map_i
                                      const signed char* occ2d, const signed char* occ2d_critical, const signed char* occ3d);
 topay_status topay_get_map_fields(topay_ctx* ctx, int map_id, double* esdf2d_inflate, double* esdf2d_critical);
 
+/* ---- Benchmark episodes on the device: worlds, occupancy, scenarios -------------------------------------------------------
+ * The first half of a turn of the reference's benchmark loop (Planner::benchmarkCallback, planner.cpp:491-548): the random
+ * world (random_map_generator.cpp: "tables" 207-325, "cuboids" 342-443), its occupancy grids (GridMap::regenerateDesk /
+ * regenerateMap, grid_map.cpp:716-798), updateESDF, and the rejection sampling of start, goal and the two arm
+ * configurations.  The reference seeds all of it from std::random_device; here every generator is a mt19937_64 with an explicit
+ * seed and the three draws of the CPU harness (harness/workload.hpp), which is the checker: equal seeds give equal bytes.
+ *
+ * topay_world_params_t: the generator's parameters (params/map_tables.yaml, map_cuboids.yaml).  obs_num are used as given:
+ * a caller that wants the harness's World::build scales them with the area, obs_num * size_xy^2 / 400, rounded
+ * (topay_amd.api.world_params does).  The map is GridMap::init's: min = -size / 2 (z from 0), dims = ceil(size / resolution).
+ * Caps (TOPAY_ERR_INVALID_ARG above): a map holds at most 2048 accepted obstacle boxes, obs_num[0] + obs_num[1] + 2 keep-outs;
+ * desk_arrangement_range is 1 <= [0] <= [1] <= 8 (a group of at most 8 x 8 desks: the primitive list of a map is sized for it). */
+typedef struct {
+  int kind;            /* 0 tables, 1 cuboids */
+  int obs_num[2];      /* desks, boxes (40, 80) / standing, floating cuboids (80, 80) at 20 x 20 m */
+  double size_xy, size_z, resolution, cloud_resolution;   /* 20, 1.6, 0.1, 0.05 */
+  double wall_size_range[2], wall_height_range[2], float_size_range[2], float_height_range[2],
+         desk_length_range[2], desk_width_range[2], desk_height_range[2];
+  int desk_arrangement_range[2];
+  int reserved;
+} topay_world_params_t;
+topay_status topay_world_default_params(int kind, topay_world_params_t* p);
+
+/* World::build(kind, seed[i], ..., keepouts, nthreads = -1) for n maps followed by the construction of the five fields: slots
+ * first_map_id .. first_map_id + n - 1 then hold what topay_build_esdf_fields gives for the harness's occupancy grids, bit for bit.
+ *   seed         [n]
+ *   keepouts_xy  [n][2][2]: centres of the two 1 x 1 x 1 m keep-out boxes of the tables world (start, goal; grid_map.cpp:766-770);
+ *                NULL = none; ignored by the cuboids world
+ *   status       [n], may be NULL: 1 built; -1 the generator's guard of 2 000 000 tries ended a loop early (the world is built
+ *                with the obstacles placed so far, as the harness builds it)
+ * The cloud is never materialised: every box is axis aligned, so a box marks (x, y) cells times a set of z cells.  Maps with at
+ * most 32 layers whose column masks fit the LDS of a compute unit are rasterised there and written with 16-byte stores (path 1);
+ * any other map by byte stores into cleared grids (path 2).  Both give the same bytes.
+ * topay_get_occupancy copies the grids of a slot of the last topay_generate_worlds / _episodes back (any pointer may be NULL;
+ * TOPAY_ERR_NO_MAP for a slot that call did not fill, or that has been refilled by another entry since). */
+topay_status topay_generate_worlds(topay_ctx* ctx, int n, int first_map_id, const topay_world_params_t* params,
+                                   const unsigned long long* seed, const double* keepouts_xy, int* status);
+topay_status topay_get_occupancy(topay_ctx* ctx, int map_id, signed char* occ2d, signed char* occ2d_critical, signed char* occ3d);
+
+/* World::sampleStartGoalXY for n seeds on a size_xy map (host only: the keep-outs of a tables world are needed before the world
+ * exists): goal, then start, each (x, y) in [-size_xy / 2 + 2, size_xy / 2 - 2] and theta in [-pi, pi), accepted when
+ * 3 <= distance <= 8.  start3 / goal3: [n][3].  TOPAY_ERR_INVALID_ARG for a map too small to hold such a pair. */
+topay_status topay_sample_start_goal_xy(int n, const unsigned long long* seed, double size_xy, double* start3, double* goal3);
+/* World::sampleArm for n states on resident maps: joints U[-max, max] until GridMap::isWholeBodyCollision is false, at most
+ * max_tries times (<= 0: 2000, the harness's stand-in for the reference's 1 s clock).  states [n][10]: in x, y, theta; out the
+ * joints of the last try.  ok [n]: 1 / 0; tries [n] (may be NULL).  map_ids NULL = slot 0. */
+topay_status topay_sample_arm(topay_ctx* ctx, int n, const int* map_ids, const unsigned long long* seed, int max_tries,
+                              double* states, int* ok, int* tries);
+/* World::sampleScenario for n seeds on resident maps (the cuboids flow): start / goal pairs as above whose ends are 0.5 m clear in
+ * the 2-D field, then the goal arm, then the start arm, up to 10000 attempts.  start, goal [n][10]; ok [n]. */
+topay_status topay_sample_scenarios(topay_ctx* ctx, int n, const int* map_ids, const unsigned long long* seed, double* start,
+                                    double* goal, int* ok);
+/* One attempt of an episode per seed: the map into slot first_map_id + i, start and goal into start / goal [n][10].
+ *   kind 0 (the tables flow of the harness's wl_tables_batch_create, without its init-path stand-in): with sd = seed * 1000 +
+ *          attempt, start and goal (x, y, theta) from sd, the world from sd with keep-outs at both, the goal arm from
+ *          seed * 7919 + 2 * attempt, the start arm from seed * 7919 + 2 * attempt + 1 (64-bit wrap-around arithmetic);
+ *   kind 1: the world from seed, topay_sample_scenarios with the same seed.
+ *   attempt  [n] or NULL = 0;  status [n]: 1 ok, 0 an arm or the scenario could not be sampled.
+ * Nothing is retried inside: a caller repeats a failed episode on its own slot with attempt + 1. */
+topay_status topay_generate_episodes(topay_ctx* ctx, int n, int first_map_id, const topay_world_params_t* params,
+                                     const unsigned long long* seed, const int* attempt, double* start, double* goal, int* status);
+
+/* Diagnostics of the last topay_generate_worlds / _episodes of a context (read only):
+ *   topay_world_last_path  which rasteriser path ran, 1 or 2;
+ *   topay_world_stage_ms   device time by stage from events: generation, rasterisation, fields, and the sampler's launch
+ *                          (0 after topay_generate_worlds), in ms. */
+topay_status topay_world_last_path(topay_ctx* ctx, int* path);
+topay_status topay_world_stage_ms(topay_ctx* ctx, double ms[4]);
+/* TEST HOOKS -- for the test suite only, not part of the product interface.  The two setters stay in force on the context until
+ * they are set back to 0:
+ *   topay_world_test_path       2 forces rasteriser path 2 whatever the map; 0 = the rule;
+ *   topay_world_test_max_tries  tries per arm of topay_generate_episodes' tables flow; 0 = the harness's 2000;
+ *   topay_test_mt64             runs on the device: outputs skip .. skip + n - 1 of mt19937_64(seed). */
+topay_status topay_world_test_path(topay_ctx* ctx, int path);
+topay_status topay_world_test_max_tries(topay_ctx* ctx, int max_tries);
+topay_status topay_test_mt64(unsigned long long seed, int skip, int n, unsigned long long* out);
+
 /* == optimizeTraj lines 146-357 for every batch member.
  *   path_len[b]      number of 10-d states of candidate b
  *   init_paths       ragged, sum(path_len) x 10, row-major (x, y, theta, q1..q7)

@@ -90,6 +90,20 @@ PLAN_STAGES = ["absent", "search_failed", "too_many_pieces", "solver_failed", "g
 PLAN_STAGE_MS_KEYS = ["roadmap", "jps", "dense", "search", "init", "solve", "gate_winner", "store"]
 
 
+class WorldParams(C.Structure):
+    """topay_world_params_t (include/topay.h): the world generator's parameters (params/map_tables.yaml, map_cuboids.yaml)."""
+    _fields_ = [("kind", C.c_int), ("obs_num", C.c_int * 2), ("size_xy", C.c_double), ("size_z", C.c_double), ("resolution", C.c_double),
+                ("cloud_resolution", C.c_double), ("wall_size_range", C.c_double * 2), ("wall_height_range", C.c_double * 2),
+                ("float_size_range", C.c_double * 2), ("float_height_range", C.c_double * 2), ("desk_length_range", C.c_double * 2),
+                ("desk_width_range", C.c_double * 2), ("desk_height_range", C.c_double * 2), ("desk_arrangement_range", C.c_int * 2),
+                ("reserved", C.c_int)]
+
+
+c_u64p = C.POINTER(C.c_ulonglong)
+c_i8p = C.POINTER(C.c_int8)
+WORLD_STAGE_MS_KEYS = ["generation", "rasterisation", "fields", "sampling"]
+
+
 class Record(C.Structure):
     """topay_record_t: the 32-byte per-scenario record of the multi-GPU exchange."""
     _fields_ = [("scenario_id", C.c_int), ("best_candidate", C.c_int), ("status", C.c_int), ("n_pieces", C.c_int),
@@ -171,6 +185,19 @@ def load(path=None):
     L.topay_build_esdf_fields.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(MapDesc), C.POINTER(C.c_int8), C.POINTER(C.c_int8),
                                           C.POINTER(C.c_int8)]
     L.topay_get_map_fields.argtypes = [C.c_void_p, C.c_int, c_dp, c_dp]
+    if hasattr(L, "topay_generate_worlds"):   # (older builds of the library under tools/libs, A/B runs)
+        L.topay_world_default_params.argtypes = [C.c_int, C.POINTER(WorldParams)]
+        L.topay_generate_worlds.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(WorldParams), c_u64p, c_dp, c_ip]
+        L.topay_get_occupancy.argtypes = [C.c_void_p, C.c_int, c_i8p, c_i8p, c_i8p]
+        L.topay_world_last_path.argtypes = [C.c_void_p, c_ip]
+        L.topay_world_test_path.argtypes = [C.c_void_p, C.c_int]
+        L.topay_world_test_max_tries.argtypes = [C.c_void_p, C.c_int]
+        L.topay_world_stage_ms.argtypes = [C.c_void_p, c_dp]
+        L.topay_sample_start_goal_xy.argtypes = [C.c_int, c_u64p, C.c_double, c_dp, c_dp]
+        L.topay_sample_arm.argtypes = [C.c_void_p, C.c_int, c_ip, c_u64p, C.c_int, c_dp, c_ip, c_ip]
+        L.topay_sample_scenarios.argtypes = [C.c_void_p, C.c_int, c_ip, c_u64p, c_dp, c_dp, c_ip]
+        L.topay_generate_episodes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(WorldParams), c_u64p, c_ip, c_dp, c_dp, c_ip]
+        L.topay_test_mt64.argtypes = [C.c_ulonglong, C.c_int, C.c_int, c_u64p]
     L.topay_get_total_durations.argtypes = [C.c_void_p, c_dp]
     L.topay_check_feasible.argtypes = [C.c_void_p, c_ip]
     L.topay_feasibility_report.argtypes = [C.c_void_p, c_ip, c_ip, c_dp]
@@ -210,6 +237,52 @@ def default_params(lib=None):
     p = Params()
     _chk(L, L.topay_default_params(C.byref(p)))
     return p
+
+
+def _u64(a):
+    """Seeds as 64-bit words (Python integers of any size wrap around like the harness's uint64_t arithmetic)."""
+    if isinstance(a, np.ndarray):
+        a = a.tolist()                        # (a list of mixed magnitudes would become float64 in numpy: convert item by item)
+    if not isinstance(a, (list, tuple)):
+        a = [a]
+    return np.array([int(x) & 0xFFFFFFFFFFFFFFFF for x in a], dtype=np.uint64)
+
+
+def world_params(kind, size_xy=20.0, size_z=1.6, resolution=0.1, cloud_resolution=0.05, lib=None, **kw):
+    """WorldParams of the tables (0) / cuboids (1) world with the obstacle counts scaled by the area as World::build does
+    (workload.hpp:689-691): round(40 | 80 x size_xy^2 / 400), round(80 x ...).  kw: any other field, set last."""
+    L = lib or load()
+    p = WorldParams()
+    _chk(L, L.topay_world_default_params(int(kind), C.byref(p)))
+    p.size_xy, p.size_z, p.resolution, p.cloud_resolution = float(size_xy), float(size_z), float(resolution), float(cloud_resolution)
+    area_scale = (p.size_xy * p.size_xy) / (20.0 * 20.0)
+    for k in range(2):
+        v = p.obs_num[k] * area_scale
+        p.obs_num[k] = int(np.floor(v + 0.5)) if v >= 0 else -int(np.floor(-v + 0.5))   # lround: halves away from zero
+    for k, v in kw.items():
+        if isinstance(v, (list, tuple, np.ndarray)):
+            for i, x in enumerate(v):
+                getattr(p, k)[i] = x
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def sample_start_goal_xy(seeds, size_xy=20.0, lib=None):
+    """World::sampleStartGoalXY for every seed (host only): (start [n, 3], goal [n, 3])."""
+    L = lib or load()
+    sd = _u64(seeds)
+    s3, g3 = np.zeros((len(sd), 3)), np.zeros((len(sd), 3))
+    _chk(L, L.topay_sample_start_goal_xy(len(sd), sd.ctypes.data_as(c_u64p), float(size_xy), _dp(s3), _dp(g3)))
+    return s3, g3
+
+
+def test_mt64(seed, skip, n, lib=None):
+    """Outputs skip .. skip + n - 1 of mt19937_64(seed), generated on the device (test hook)."""
+    L = lib or load()
+    out = np.zeros(n, dtype=np.uint64)
+    _chk(L, L.topay_test_mt64(int(seed) & 0xFFFFFFFFFFFFFFFF, int(skip), int(n), out.ctypes.data_as(c_u64p)))
+    return out
 
 
 def params_from_yaml(source, base=None, lib=None):
@@ -560,6 +633,102 @@ class MomaTrajOptBatch:
         ms = C.c_double(0)
         _chk(self.L, self.L.topay_get_map(self.h, map_id, _dp(e2), _dp(e3), C.byref(ms)))
         return e2, e3, ms.value
+
+    # -- the first half of a benchmark episode (planner.cpp:491-548) on the device
+    def _world_dims(self, prm, first_map_id, n):
+        dims = tuple(int(np.ceil(v / prm.resolution)) for v in (prm.size_xy, prm.size_xy, prm.size_z))
+        for k in range(n):
+            self._map_dims[first_map_id + k] = dims
+
+    def generate_worlds(self, prm, seeds, keepouts=None, first_map_id=0):
+        """World::build for every seed into slots first_map_id ... (topay_generate_worlds), fields included.  keepouts: [n, 2, 2]
+        (tables: start and goal xy) or None.  Returns the status array (1 built, -1 the generator's guard ended a loop)."""
+        sd = _u64(seeds)
+        n = len(sd)
+        ko = None if keepouts is None else np.ascontiguousarray(keepouts, dtype=np.float64).reshape(n, 4)
+        st = np.zeros(n, dtype=np.int32)
+        _chk(self.L, self.L.topay_generate_worlds(self.h, n, int(first_map_id), C.byref(prm), sd.ctypes.data_as(c_u64p), _dp(ko), _ip(st)))
+        self._world_dims(prm, first_map_id, n)
+        return st
+
+    def get_occupancy(self, map_id=0):
+        """(occ2d, occ2d_critical, occ3d) of a slot of the last generate_worlds / generate_episodes."""
+        if map_id not in self._map_dims:
+            raise TopayError(f"topay status -3: slot {map_id} holds no map")
+        nx, ny, nz = self._map_dims[map_id]
+        o2, oc, o3 = np.zeros(nx * ny, dtype=np.int8), np.zeros(nx * ny, dtype=np.int8), np.zeros(nx * ny * nz, dtype=np.int8)
+        _chk(self.L, self.L.topay_get_occupancy(self.h, int(map_id), o2.ctypes.data_as(c_i8p), oc.ctypes.data_as(c_i8p), o3.ctypes.data_as(c_i8p)))
+        return o2, oc, o3
+
+    def world_last_path(self):
+        """Rasteriser path of the last generate_worlds / generate_episodes: 1 masks in LDS, 2 byte stores."""
+        v = C.c_int(0)
+        _chk(self.L, self.L.topay_world_last_path(self.h, C.byref(v)))
+        return v.value
+
+    def world_test_path(self, path):
+        """Test hook: 2 = byte stores whatever the map, 0 = the rule."""
+        _chk(self.L, self.L.topay_world_test_path(self.h, int(path)))
+
+    def world_test_max_tries(self, max_tries):
+        """Test hook: tries per arm of generate_episodes' tables flow (0 = 2000)."""
+        _chk(self.L, self.L.topay_world_test_max_tries(self.h, int(max_tries)))
+
+    def world_stage_ms(self):
+        """Device time of the last generate_worlds / generate_episodes by stage (WORLD_STAGE_MS_KEYS), milliseconds."""
+        ms = np.zeros(4)
+        _chk(self.L, self.L.topay_world_stage_ms(self.h, _dp(ms)))
+        return dict(zip(WORLD_STAGE_MS_KEYS, ms.tolist()))
+
+    def sample_arm(self, states, seeds, map_ids=None, max_tries=0):
+        """World::sampleArm for [n, 10] states (x, y, theta given) -> (states with joints, ok, tries)."""
+        st = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 10).copy()
+        n = len(st)
+        sd = _u64(seeds)
+        mid = None if map_ids is None else np.ascontiguousarray(map_ids, dtype=np.int32)
+        ok, tr = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        _chk(self.L, self.L.topay_sample_arm(self.h, n, _ip(mid), sd.ctypes.data_as(c_u64p), int(max_tries), _dp(st), _ip(ok), _ip(tr)))
+        return st, ok.astype(bool), tr
+
+    def sample_scenarios(self, seeds, map_ids=None):
+        """World::sampleScenario for every seed -> (start [n, 10], goal [n, 10], ok)."""
+        sd = _u64(seeds)
+        n = len(sd)
+        mid = None if map_ids is None else np.ascontiguousarray(map_ids, dtype=np.int32)
+        s, g, ok = np.zeros((n, 10)), np.zeros((n, 10)), np.zeros(n, dtype=np.int32)
+        _chk(self.L, self.L.topay_sample_scenarios(self.h, n, _ip(mid), sd.ctypes.data_as(c_u64p), _dp(s), _dp(g), _ip(ok)))
+        return s, g, ok.astype(bool)
+
+    def generate_episodes(self, prm, seeds, first_map_id=0, max_attempts=1, attempts=None):
+        """One episode per seed into slots first_map_id ... (topay_generate_episodes): map, start, goal.  A failed episode is
+        repeated on its own slot with attempt + 1, up to max_attempts attempts (the retry the library leaves to its caller).
+        attempts: the first attempt of every episode (default 0).  Returns (start [n, 10], goal [n, 10], status [n], attempt [n] --
+        the attempt that gave the episode, or the last one tried).
+
+        A retry round calls the library on the failed slots only, and every call replaces the grids that get_occupancy reads:
+        after a retry, get_occupancy serves the slots of the last call alone (TopayError NO_MAP for an episode that succeeded
+        in an earlier round; the fields of every slot stay resident).  Each distinct run of retried slots also keeps a field
+        arena of its own until its slots are rebuilt in one call or the context is destroyed."""
+        sd = _u64(seeds)
+        n = len(sd)
+        att = np.zeros(n, dtype=np.int32) if attempts is None else np.ascontiguousarray(attempts, dtype=np.int32).copy()
+        start, goal, status = np.zeros((n, 10)), np.zeros((n, 10)), np.zeros(n, dtype=np.int32)
+        todo = np.arange(n)
+        for rnd in range(max(1, int(max_attempts))):
+            runs = np.split(todo, np.nonzero(np.diff(todo) != 1)[0] + 1)    # consecutive slots go in one call
+            for run in runs:
+                k = len(run)
+                s, g, st = np.zeros((k, 10)), np.zeros((k, 10)), np.zeros(k, dtype=np.int32)
+                sdr, atr = np.ascontiguousarray(sd[run]), np.ascontiguousarray(att[run])
+                _chk(self.L, self.L.topay_generate_episodes(self.h, k, int(first_map_id + run[0]), C.byref(prm), sdr.ctypes.data_as(c_u64p), _ip(atr),
+                                                            _dp(s), _dp(g), _ip(st)))
+                start[run], goal[run], status[run] = s, g, st
+            self._world_dims(prm, first_map_id, n)
+            todo = np.nonzero(status != 1)[0]
+            if len(todo) == 0 or rnd + 1 == max(1, int(max_attempts)):
+                break
+            att[todo] += 1
+        return start, goal, status, att
 
     def playback(self, i, times):
         """MomaTraj playback of candidate i: (states[len(times), 10], car_seq[n, 4])."""

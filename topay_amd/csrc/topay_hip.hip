@@ -28,6 +28,7 @@
 #include "topay_yaml.h"
 
 #include "topay_kernels.h"
+#include "topay_world.h"
 
 // host side, in this order: each header uses what the ones before it define
 #include "topay_host_ctx.h"
@@ -37,3 +38,4 @@
 #include "topay_host_front.h"
 #include "topay_host_dist.h"
 #include "topay_host_plan.h"
+#include "topay_host_world.h"

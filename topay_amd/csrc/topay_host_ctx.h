@@ -215,8 +215,16 @@ struct topay_ctx {
   DevBuf paths, path_off, path_len, bvel, bacc, scratch;
   DevBuf N, s1_past, map_id, head, tail, start_xy, goal_xy, init_xy, x0;
   DevBuf x, work, hist_s, hist_y, hist_ys, hist_alpha, lu;
-  DevBuf success, cost, stats, xyerr, coef, T, knots, alm, fout, order, trace, elapsed, startus, hwid, sbuf, mstash, feas_cseq, feas_tk, feas_report, feas_flags, edt_occ, edt_tmp1, edt_tmp2, edt_v, edt_z, edt_out2, pb_io;
+  DevBuf success, cost, stats, xyerr, coef, T, knots, alm, fout, order, trace, elapsed, startus, hwid, sbuf, mstash, feas_cseq, feas_tk, feas_report, feas_flags, edt_occ, edt_thr, edt_tmp1, edt_tmp2, edt_v, edt_z, edt_out2, pb_io;
   float last_edt_ms = 0.f;
+  // topay_generate_worlds / topay_generate_episodes (topay_host_world.h): the occupancy grids of the last call stay for
+  // topay_get_occupancy (slots [world_first, world_first + world_n) of dimensions world_dims), its primitive lists and its
+  // inputs / outputs; the rasteriser path it took (1: masks in LDS, 2: byte stores) and its device time by stage
+  DevBuf world_occ, world_prims, world_io;
+  int world_first = 0, world_n = 0, world_dims[3] = {0, 0, 0}, world_path = 0;
+  int world_force_path = 0, world_max_tries = 0;   // test hooks: 2 = byte stores whatever the map; tries per arm of an episode (0: 2000)
+  hipEvent_t world_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // stage bounds 0..3, the sampler's launch 4, 5
+  double world_ms[4] = {0, 0, 0, 0};
   int trace_cap = 0;
   DevBatch db;
   bool have_traj = false, solved = false;
@@ -434,6 +442,14 @@ static void drop_shared_slots(topay_ctx* c, int first, int n) {
   }
 }
 
+// slots [first, first + n) are refilled by something else than the world generator: its occupancy grids no longer describe them
+static void world_forget(topay_ctx* c, int first, int n) {
+  if (c->world_n > 0 && first < c->world_first + c->world_n && c->world_first < first + n) {
+    c->world_n = 0;
+    c->world_occ.release();
+  }
+}
+
 static int bucket_of(int N) {
   for (int k = 0; k < topay_ctx::NBUCKET; k++)
     if (N <= kBucketMaxN[k]) return k;
@@ -565,6 +581,8 @@ void topay_destroy(topay_ctx* c) {
   }
   (void)hipSetDevice(c->device);
   for (hipEvent_t e : c->pl_events) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->world_ev)
+    if (e) (void)hipEventDestroy(e);
   for (int k = 0; k < topay_ctx::NBUCKET; k++) {
     if (c->bevent[k]) (void)hipEventDestroy(c->bevent[k]);
     if (c->bstream[k] && c->bstream[k] != c->stream) (void)hipStreamDestroy(c->bstream[k]);

@@ -2,6 +2,15 @@
 
 #pragma once
 
+// what every entry that fills a slot asks of a map's dimensions
+static topay_status map_dims_check(const topay_map_desc_t* desc) {
+  const size_t n2 = (size_t)desc->dims[0] * desc->dims[1], n3 = n2 * desc->dims[2];
+  if (n2 == 0 || n3 == 0) return TOPAY_ERR_INVALID_ARG;
+  if (n3 >= (1ull << 32)) { set_err("map of 2^32 cells or more (the lookups index a field with 32 bits)"); return TOPAY_ERR_UNSUPPORTED; }
+  if (desc->dims[2] < 2) { set_err("3-D field with a single layer (the lookups fetch z-neighbours in pairs)"); return TOPAY_ERR_UNSUPPORTED; }
+  return TOPAY_OK;
+}
+
 extern "C" {
 
 topay_status topay_set_map(topay_ctx* c, int map_id, const topay_map_desc_t* desc, const double* esdf2d, const double* esdf3d) {
@@ -9,11 +18,10 @@ topay_status topay_set_map(topay_ctx* c, int map_id, const topay_map_desc_t* des
   HIPCHK(hipSetDevice(c->device));
   if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }   // inputs of a solve in flight stay untouched
   const size_t n2 = (size_t)desc->dims[0] * desc->dims[1], n3 = n2 * desc->dims[2];
-  if (n2 == 0 || n3 == 0) return TOPAY_ERR_INVALID_ARG;
-  if (n3 >= (1ull << 32)) { set_err("map of 2^32 cells or more (the lookups index a field with 32 bits)"); return TOPAY_ERR_UNSUPPORTED; }
-  if (desc->dims[2] < 2) { set_err("3-D field with a single layer (the lookups fetch z-neighbours in pairs)"); return TOPAY_ERR_UNSUPPORTED; }
+  if (topay_status ds = map_dims_check(desc)) return ds;
   invalidate_sharers(c, map_id, 1);
   drop_shared_slots(c, map_id, 1);
+  world_forget(c, map_id, 1);
   topay_status s;
   if ((s = c->map2d[map_id].ensure(n2 * 8)) != TOPAY_OK) return s;
   if ((s = c->map3d[map_id].ensure(n3 * 8)) != TOPAY_OK) return s;
@@ -49,6 +57,7 @@ topay_status topay_share_maps(topay_ctx* c, topay_ctx* owner, int first_map_id, 
     if (!owner->have_map[m]) return TOPAY_ERR_NO_MAP;
   invalidate_sharers(c, first_map_id, n_maps);   // (contexts that shared c's own copies of these slots)
   drop_shared_slots(c, first_map_id, n_maps);
+  world_forget(c, first_map_id, n_maps);
   for (int m = first_map_id; m < first_map_id + n_maps; m++) {
     c->map2d[m].release(); c->map3d[m].release(); c->map2d_inf[m].release(); c->map2d_crit[m].release();   // own copies of these slots, if any
     c->hmaps[m] = owner->hmaps[m];
@@ -73,30 +82,21 @@ topay_status topay_share_maps(topay_ctx* c, topay_ctx* owner, int first_map_id, 
   return TOPAY_OK;
 }
 
-// ESDF construction on the device (GridMap::updateESDF, grid_map.cpp:125-521) from the occupancy grids the
-// reference fills from its point cloud (grid_map.cpp:733-747): occ2d[x*ny + y] (points below the chassis height),
-// occ3d[x*ny*nz + y*nz + z].  The map slots then hold the result exactly as topay_set_map would.  A batch of maps
-// of equal dimensions (the benchmark loop: one map per scenario) is built by the same launches, blockIdx.y = map:
-// a single 200 x 200 x 16 map has too few lines to fill the device.
-topay_status topay_build_esdf_fields(topay_ctx* c, int n_maps, int first_map_id, const topay_map_desc_t* desc,
-                                     const signed char* occ2d, const signed char* occ2d_critical, const signed char* occ3d) {
-  if (!c || !desc || !occ2d || !occ3d || n_maps <= 0 || first_map_id < 0 || first_map_id + n_maps > TOPAY_MAX_MAPS)
-    return TOPAY_ERR_INVALID_ARG;
-  HIPCHK(hipSetDevice(c->device));
-  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }   // inputs of a solve in flight stay untouched
+// ESDF construction on the device (GridMap::updateESDF, grid_map.cpp:125-521) from occupancy grids that already lie in device
+// memory: d_occ3 [n_maps][nx*ny*nz], d_occ2 [n_maps][nx*ny] (points below the chassis height), d_occ2c [n_maps][nx*ny] (the
+// critical grid; written here as the projection of d_occ3 when project_critical).  The body of topay_build_esdf_fields, which
+// uploads the grids first, and of topay_generate_worlds (topay_host_world.h), whose rasteriser wrote them.  The grids are read
+// only (d_occ2c apart) and stay the caller's.
+static topay_status build_fields_from_device(topay_ctx* c, int n_maps, int first_map_id, const topay_map_desc_t* desc, signed char* d_occ3,
+                                             signed char* d_occ2, signed char* d_occ2c, bool project_critical) {
   const int nx = desc->dims[0], ny = desc->dims[1], nz = desc->dims[2];
   const size_t n2 = (size_t)nx * ny, n3 = n2 * nz, M = (size_t)n_maps;
-  if (n2 == 0 || n3 == 0) return TOPAY_ERR_INVALID_ARG;
-  if (n3 >= (1ull << 32)) { set_err("map of 2^32 cells or more (the lookups index a field with 32 bits)"); return TOPAY_ERR_UNSUPPORTED; }
-  if (desc->dims[2] < 2) { set_err("3-D field with a single layer (the lookups fetch z-neighbours in pairs)"); return TOPAY_ERR_UNSUPPORTED; }
+  if (topay_status ds = map_dims_check(desc)) return ds;
   invalidate_sharers(c, first_map_id, n_maps);
   drop_shared_slots(c, first_map_id, n_maps);
   topay_status s;
-  signed char *d_occ3, *d_occ2, *d_occ2c, *d_occ2t;   // 3-D, 2-D, 2-D critical, 2-D scratch
-  auto lay_occ = [&](Carver& k) {
-    d_occ3 = k.take<signed char>(M * n3); d_occ2 = k.take<signed char>(M * n2); d_occ2c = k.take<signed char>(M * n2); d_occ2t = k.take<signed char>(M * n2);
-  };
-  if ((s = c->edt_occ.carve(lay_occ)) != TOPAY_OK) return s;
+  if ((s = c->edt_thr.ensure(M * n2)) != TOPAY_OK) return s;
+  signed char* d_occ2t = c->edt_thr.as<signed char>();   // 2-D scratch: the thresholded fields
   if ((s = c->edt_tmp1.ensure(M * n3 * 8)) != TOPAY_OK) return s;
   if ((s = c->edt_tmp2.ensure(M * n3 * 8)) != TOPAY_OK) return s;
   // results: e3 | e2 | e2 inflate | e2 critical in a new arena (they stay there); the plain critical field is scratch
@@ -133,9 +133,6 @@ topay_status topay_build_esdf_fields(topay_ctx* c, int n_maps, int first_map_id,
   const size_t ws_elems = std::max(std::max((size_t)nx * ny * (nz + 2), (size_t)nx * nz * (ny + 2)), (size_t)ny * nz * (nx + 2));
   if ((s = c->edt_v.ensure(M * ws_elems * 4)) != TOPAY_OK) return s;
   if ((s = c->edt_z.ensure(M * ws_elems * 8)) != TOPAY_OK) return s;
-  HIPCHK(h2d(c, d_occ3, occ3d, M * n3));
-  HIPCHK(h2d(c, d_occ2, occ2d, M * n2));
-  if (occ2d_critical) HIPCHK(h2d(c, d_occ2c, occ2d_critical, M * n2));
   HIPCHK(hipEventRecord(c->ev0, c->stream));
   double* t1 = c->edt_tmp1.as<double>();
   double* t2 = c->edt_tmp2.as<double>();
@@ -245,7 +242,7 @@ topay_status topay_build_esdf_fields(topay_ctx* c, int n_maps, int first_map_id,
   if ((s = field2d(d_occ2, e2)) != TOPAY_OK) return s;              // esdf_buffer_2d
   threshold(e2, d_occ2t);
   if ((s = field2d(d_occ2t, e2i)) != TOPAY_OK) return s;            // esdf_buffer_2d_inflate (355-423)
-  if (!occ2d_critical) {
+  if (project_critical) {
     const long long n = (long long)(M * n2);
     hipLaunchKernelGGL(k_edt_project, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const signed char*)d_occ3, d_occ2c,
                        (long long)n2, nz, (long long)M);
@@ -280,8 +277,33 @@ topay_status topay_build_esdf_fields(topay_ctx* c, int n_maps, int first_map_id,
   c->last_edt_ms = ms;
   // the construction's workspace (occupancy, two intermediate volumes, the envelope stacks, the staged results: about
   // five times the maps themselves) is not needed once the fields sit in their map slots
-  c->edt_occ.release(); c->edt_tmp1.release(); c->edt_tmp2.release(); c->edt_v.release(); c->edt_z.release(); c->edt_out2.release();
+  c->edt_thr.release(); c->edt_tmp1.release(); c->edt_tmp2.release(); c->edt_v.release(); c->edt_z.release(); c->edt_out2.release();
   return TOPAY_OK;
+}
+
+// ESDF construction on the device from the occupancy grids the reference fills from its point cloud (grid_map.cpp:733-747):
+// occ2d[x*ny + y] (points below the chassis height), occ3d[x*ny*nz + y*nz + z].  The map slots then hold the result exactly as
+// topay_set_map would.  A batch of maps of equal dimensions (the benchmark loop: one map per scenario) is built by the same
+// launches, blockIdx.y = map: a single 200 x 200 x 16 map has too few lines to fill the device.
+topay_status topay_build_esdf_fields(topay_ctx* c, int n_maps, int first_map_id, const topay_map_desc_t* desc,
+                                     const signed char* occ2d, const signed char* occ2d_critical, const signed char* occ3d) {
+  if (!c || !desc || !occ2d || !occ3d || n_maps <= 0 || first_map_id < 0 || first_map_id + n_maps > TOPAY_MAX_MAPS)
+    return TOPAY_ERR_INVALID_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }   // inputs of a solve in flight stay untouched
+  const size_t n2 = (size_t)desc->dims[0] * desc->dims[1], n3 = n2 * desc->dims[2], M = (size_t)n_maps;
+  if (topay_status ds = map_dims_check(desc)) return ds;
+  world_forget(c, first_map_id, n_maps);
+  topay_status s;
+  signed char *d_occ3, *d_occ2, *d_occ2c;   // 3-D, 2-D, 2-D critical
+  auto lay_occ = [&](Carver& k) { d_occ3 = k.take<signed char>(M * n3); d_occ2 = k.take<signed char>(M * n2); d_occ2c = k.take<signed char>(M * n2); };
+  if ((s = c->edt_occ.carve(lay_occ)) != TOPAY_OK) return s;
+  HIPCHK(h2d(c, d_occ3, occ3d, M * n3));
+  HIPCHK(h2d(c, d_occ2, occ2d, M * n2));
+  if (occ2d_critical) HIPCHK(h2d(c, d_occ2c, occ2d_critical, M * n2));
+  s = build_fields_from_device(c, n_maps, first_map_id, desc, d_occ3, d_occ2, d_occ2c, occ2d_critical == nullptr);
+  c->edt_occ.release();
+  return s;
 }
 
 topay_status topay_build_esdf_batch(topay_ctx* c, int n_maps, int first_map_id, const topay_map_desc_t* desc,
