@@ -1,4 +1,4 @@
-"""Several wavefronts per trajectory (topay_amd/csrc/topay_eval_mw.h): the workgroup of 2 or 4 waves that solves the long
+"""Several wavefronts per trajectory (eval_cost_grad<..., NW> in topay_amd/csrc/topay_eval.h): the workgroup of 2 or 4 waves that solves the long
 candidates (launch classes N <= 42 / 64 / 170).
 
   * An evaluation is order-identical whatever the number of waves: for every N <= 64 the 2- and 4-wave kernels must

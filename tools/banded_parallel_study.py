@@ -2,7 +2,7 @@
 item 5: "measure a parallel banded solve ... in the emulator first -- per-evaluation parity vs oracle must stay <= 1e-11 ... If cyclic
 reduction loses accuracy on the T^5-scaled rows, say so with the numbers and stop.")
 
-CPU study, numpy only.  The 6N x 6N system of MinJerkOpt<9>::generate (minco.hpp:838-900; the device's minco_generate_mw fills the same
+CPU study, numpy only.  The 6N x 6N system of MinJerkOpt<9>::generate (minco.hpp:838-900; the device's minco_generate fills the same
 band) is solved three ways for random piece durations and boundary / inner-point data of the benchmark's magnitudes:
   ref   the reference's banded LU WITHOUT pivoting, in its elimination order (banded_system.hpp:66-118), float64 -- what the oracle and
         the device do, bit for bit up to fused multiply-adds;

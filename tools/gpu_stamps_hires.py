@@ -3,7 +3,7 @@
     TOPAY_LIB=tools/libs/libtopay_stamps.so python3 tools/gpu_stamps_hires.py [scenarios] [size_m]
 
 The diagnostics build (-DTOPAY_STAMPS, tools/ab_lib.sh stamps -DTOPAY_STAMPS) reads the shader clock before and after an
-s_waitcnt vmcnt(n) placed where the eight gathers of the sphere being finished are first needed (topay_eval.h): the latency a
+s_waitcnt vmcnt(n) placed where the eight gathers of the sphere being finished are first needed (topay_mani.h): the latency a
 wave is actually exposed to, everything the look-ahead and the other resident wave do not cover.  Whole solves of
 scenarios x 8 candidates (128 -> one wave per SIMD, 512 -> two); the same on the cached maps is tools/gpu_stamps.py.
 The world and the init paths are those of tools/k1_gather.py hires (field built on the device, straight 3-8 m segments).

@@ -1,548 +1,47 @@
-// One-wavefront-per-trajectory cost + analytic gradient of TopAY's (s,theta) NLP.
+// Cost + analytic gradient of TopAY's (s, theta) NLP for one trajectory: eval_cost_grad<STAGE, RMAX, NW, OCC>, the one
+// evaluation there is, run by the trajectory's workgroup of NW = 1, 2 or 4 waves (the SIMDs of one compute unit) with
+// the LDS of eval_lds_plan (topay_eval_ctx.h).
 //
-// Follows (all under /root/reference/src):
+// Follows (paths under the reference's src/):
 //   planner/src/moma_traj_opt.cpp:817-955   first/secondStageCostCallback
 //   planner/src/moma_traj_opt.cpp:957-1198  calFirstStagePenalGrad
 //   planner/src/moma_traj_opt.cpp:1200-1829 calSecondStagePenalGrad
-//   planner/include/utils/minco.hpp:824-1069, banded_system.hpp:66-145
-//   simulator/fake_moma/include/fake_moma/moma_param.h:203-337, map/include/map/grid_map.h:364-509
+//   planner/include/utils/minco.hpp:824-1069, banded_system.hpp:66-145            (topay_minco.h)
+//   simulator/fake_moma/include/fake_moma/moma_param.h:203-337                    (topay_mani.h)
+//   map/include/map/grid_map.h:364-509                                            (topay_esdf.h)
 //
-// Work decomposition inside the wave (64 lanes, one workgroup = one wave):
-//   * "row lanes":    lane <-> row of the 6N x 6N MINCO system (2 rows per lane when 6N > 64).
-//                     They own the gradient w.r.t. the coefficient rows (gdC) in registers.
-//   * "sample lanes": lane <-> even ("full") Simpson sample e = 13*piece + m, 64 per pass.
-//                     Each also handles the odd sample that follows it.
-//   * banded LU / substitutions: the 6x7 (resp. 6x9) update block of one pivot across lanes, in LDS.
-// XY positions are a wave prefix scan of Simpson panel integrals; the XY-gradient "chain"
-// (moma_traj_opt.cpp:1313-1314,1667-1668,1812-1822) is the matching suffix scan, done in a second
-// sweep.  Per-sample gradient rows travel sample-lane -> row-lane through a small LDS pass buffer.
+// Work decomposition inside the workgroup (NT = 64 NW threads):
+//   * "row threads":    thread tid owns the rows tid + NT r, r < RMAX, of the 6N x 6N MINCO system and, in registers
+//                       (RMAX x 9 doubles, not in LDS), the gradient with respect to those coefficient rows.
+//   * "sample lanes":   lane <-> even ("full") Simpson sample e = 13 * piece + m, 64 per pass, one pass per wave and
+//                       round.  Each also handles the odd sample that follows it.
+//   * banded LU / substitutions: the serial part, on wave 0 (topay_minco.h); the factors are stashed in the candidate's
+//                       LU block in HBM and stream back through two small LDS windows.
+// XY positions are a prefix scan of Simpson panel integrals; the XY-gradient "chain" (moma_traj_opt.cpp:1313-1314,
+// 1667-1668, 1812-1822) is the matching suffix scan, done in a second sweep.  Per-sample gradient rows are parked in HBM
+// between the cost and the gradient phase (GradGate: a rejected line-search trial never needs them) and travel sample lane
+// -> row thread through one small LDS pass buffer per wave.  The adjoint solve runs in the LDS block of the coefficients,
+// which move to the candidate's result block in HBM first (the dJ/dT correction reads them from there).
+//
+// The arithmetic of an evaluation is ORDER-IDENTICAL for every NW:
+//   * XY prefix / chain suffix: scan inside a pass by the wave that owns it, pass totals added sequentially in pass
+//     order (one wave's running carry);
+//   * per-lane penalty cost: per-round hand-over of the pass costs through LDS, added in pass order;
+//   * row accumulation: every row thread walks the samples of its piece in ascending order, pass by pass;
+//   * sums over pieces: the pieces sit on wave 0's lanes for N <= 64, the other waves add exact zeros.
+// So for N <= 64 an evaluation returns the same bits on one, two and four waves (asserted on the GPU:
+// tests/test_multiwave.py); the L-BFGS vector arithmetic around it is divided differently (topay_solve.h) and is
+// restated per (EPL, NW) in the oracle's device-order mode.
 #pragma once
 
-#include <hip/hip_runtime.h>
-
+#include "topay_esdf.h"
+#include "topay_eval_ctx.h"
+#include "topay_mani.h"
 #include "topay_math.h"
-#include "topay_types.h"
-
-#ifndef TOPAY_CPU_EMU
-#define HIP_DYN_SHARED_DECL extern __shared__ double topay_lds[];
-#endif
-
-// Optimizer/robot parameters live in constant memory: every access is a scalar load the compiler can re-issue at
-// the point of use instead of keeping hundreds of SGPRs of kernel arguments alive across the whole solve.
-__constant__ DevParams g_P;
-// The parameter block through ONE base address per function, held in a scalar register pair: the compiler otherwise forms the
-// address of every field it reads from the program counter anew (s_getpc_b64 + 64-bit add: three scalar instructions ahead of
-// each of the 133 parameter loads of the manipulator block -- a wave issues one instruction per four cycles whatever its kind).
-// The empty asm hides where the pointer comes from, so the fields become immediate offsets from it.
-typedef const TOPAY_CST DevParams& dev_params_ref;
-__device__ __forceinline__ dev_params_ref dev_params() {
-#ifndef TOPAY_CPU_EMU
-  const TOPAY_CST DevParams* p = (const TOPAY_CST DevParams*)&g_P;
-  asm("" : "+s"(p));
-  return *p;
-#else
-  return g_P;
-#endif
-}
-
-// Optional scheduling fences between the independent sub-blocks of the manipulator block (off: a leftover of rounds 1-2;
-// every kernel is built for 256 registers since round 4 and the block's sphere loop carries its own fence, TOPAY_OCC2_FENCE).
-#ifdef TOPAY_USE_SCHED_FENCE
-#define TOPAY_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-#else
-#define TOPAY_SCHED_FENCE() do { } while (0)
-#endif
-
-// The compiler must treat the value as changed (no instruction is emitted): stops common-subexpression reuse across a
-// rarely taken path, which would otherwise be paid for with registers on the common one.
-#ifndef TOPAY_CPU_EMU
-#define TOPAY_OPAQUE(x) asm volatile("" : "+v"(x))
-#define TOPAY_OPAQUE_I(x) asm volatile("" : "+v"(x))
-#else
-#define TOPAY_OPAQUE(x) do { } while (0)
-#define TOPAY_OPAQUE_I(x) do { } while (0)
-#endif
-
-// On the functions that call the non-inlined device functions.  Those callees use the whole register file, and the
-// compiler lets such a function skip the saving of callee-saved registers (the caller then saves exactly what it keeps across
-// the call) only if no call of it carries LLVM's `tail` marker -- which the optimiser adds to every call that is handed no
-// pointer into the caller's stack frame.  Round 5 took the stack out of the manipulator block's interface, the marker
-// appeared, and the block began to save and restore all 112 callee-saved VGPRs on every call (388 scratch instructions).
-// With this attribute the marker is not added.
-#ifndef TOPAY_CPU_EMU
-#define TOPAY_CALLS_BIG_FUNCTIONS __attribute__((disable_tail_calls))
-#else
-#define TOPAY_CALLS_BIG_FUNCTIONS
-#endif
-
-// A wave-uniform `true` the compiler cannot see through (one s_cmp + s_cbranch): starts a new basic block on purpose.
-__device__ __forceinline__ bool topay_opaque_true() {
-#ifndef TOPAY_CPU_EMU
-  int one = 1;
-  asm volatile("" : "+s"(one));
-  return one != 0;
-#else
-  return true;
-#endif
-}
-
-#ifndef TOPAY_ESDF_LOOKAHEAD
-#define TOPAY_ESDF_LOOKAHEAD 2
-#endif
-#ifndef TOPAY_OCC2_FENCE
-#define TOPAY_OCC2_FENCE 1
-#endif
-#ifndef TOPAY_ESDF_LOOKAHEAD_OCC2
-#define TOPAY_ESDF_LOOKAHEAD_OCC2 1
-#endif
+#include "topay_minco.h"
+#include "topay_wave.h"
 
 namespace topay {
-
-// ---------------------------------------------------------------------------------------------
-// wave helpers (collectives: call only from wave-uniform control flow)
-// ---------------------------------------------------------------------------------------------
-// One fixed summation tree for every wave reduction: xor-butterfly with offsets 1,2,4,8 inside each 16-lane row
-// (DPP quad_perm / row_half_mirror / row_mirror; additions commute, so all lanes of a row end up with identical
-// bits), then (r0+r1)+(r2+r3) over the four rows via readlane.  Every lane receives the same bits, which keeps
-// wave-uniform control flow uniform.
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-#ifndef TOPAY_CPU_EMU
-  // (mov_dpp: no "old" operand -- with update_dpp(lo, lo, ...) the compiler copies the source into the destination first,
-  // two more 32-bit moves per level of every reduction: 8 of the 39 vector instructions per history pair of the two-loop recursion)
-  lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xF, 0xF, false);
-  hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xF, 0xF, false);
-#else
-  lo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xF, 0xF, false);
-  hi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xF, 0xF, false);
-#endif
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-  return __hiloint2double(hi, lo);
-}
-// rows of 16 lanes outside ROWMASK receive 0.0 (the caller adds the result)
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ double dpp_f64_rows(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, ROWMASK, 0xF, false);
-  hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, ROWMASK, 0xF, false);
-  return __hiloint2double(hi, lo);
-}
-// 64-lane sum: a butterfly inside every row of 16 (every lane of row k then holds r_k), then across the rows:
-// (r0 + r1) + (r2 + r3), in lane 63.  The sum is 20 instructions of VALU issue -- f64 has no DPP operand form, every
-// level is two 32-bit DPP moves and an add -- and that, not the latency of the chain, is what a reduction costs
-// (docs/EXPERIMENTS.md); the cross-row levels replace four lane reads and three adds of rounds 1-2, same bits (the
-// operands of every addition are the same, in the other order).
-__device__ __forceinline__ double wave_sum(double v) {
-  v += dpp_f64<0xB1>(v);   // quad_perm [1,0,3,2]   : lane ^ 1
-  v += dpp_f64<0x4E>(v);   // quad_perm [2,3,0,1]   : lane ^ 2
-  v += dpp_f64<0x141>(v);  // row_half_mirror       : quad q <-> quad q^1
-  v += dpp_f64<0x140>(v);  // row_mirror            : half h <-> half h^1
-#ifndef TOPAY_CPU_EMU
-  // Only lane 63 is read below: the rows a broadcast does not reach may hold anything, so the moves need no zeroed
-  // destination (two more 32-bit moves per level with the row masks of the emulator's form; lane 63's operands are the same).
-  v += dpp_f64<0x142>(v);             // row_bcast15: row k += lane 15 of row k - 1               -> lane 63: r3 + r2, lane 31: r1 + r0
-  v += dpp_f64<0x143>(v);             // row_bcast31: rows 2, 3 += lane 31                        -> lane 63: (r3 + r2) + (r1 + r0)
-#else
-  v += dpp_f64_rows<0x142, 0xA>(v);   // row_bcast15: rows 1 and 3 += lane 15 of the row before  -> r1 + r0, r3 + r2
-  v += dpp_f64_rows<0x143, 0xC>(v);   // row_bcast31: rows 2 and 3 += lane 31                    -> (r3 + r2) + (r1 + r0)
-#endif
-  return readlane_f64(v, 63);
-}
-__device__ __forceinline__ double wave_max(double v) {
-  double o;
-  o = dpp_f64<0xB1>(v); v = o > v ? o : v;
-  o = dpp_f64<0x4E>(v); v = o > v ? o : v;
-  o = dpp_f64<0x141>(v); v = o > v ? o : v;
-  o = dpp_f64<0x140>(v); v = o > v ? o : v;
-  const double r0 = readlane_f64(v, 0), r1 = readlane_f64(v, 16), r2 = readlane_f64(v, 32), r3 = readlane_f64(v, 48);
-  const double a = r0 > r1 ? r0 : r1, b = r2 > r3 ? r2 : r3;
-  return a > b ? a : b;
-}
-// LDS hand-off between lanes of the one wave of this workgroup: LDS operations of a wave complete in issue
-// order, so only compiler reordering has to be prevented (no s_barrier, no vmcnt drain).
-__device__ __forceinline__ void lds_sync() {
-#ifdef TOPAY_FULL_SYNC
-  __syncthreads();
-  return;
-#endif
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-}
-// Hand-off through GLOBAL memory between the lanes of one wave (stores by some lanes, loads by others): the stores are
-// complete (vmcnt) before any lane goes on, without a workgroup barrier -- usable by one wave of a several-waves workgroup.
-__device__ __forceinline__ void wave_global_sync() {
-#ifndef TOPAY_CPU_EMU
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-#else
-  __builtin_amdgcn_wave_barrier();
-#endif
-}
-// The lane's number formed anew (two instructions, no operand): used after a call of the manipulator block, so that the
-// number -- and everything derived from it -- need not be carried across the call in a register the callee clobbers.
-__device__ __forceinline__ int fresh_lane_id(int known) {
-#ifndef TOPAY_CPU_EMU
-  int l;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-  (void)known;
-  return l;
-#else
-  return known;
-#endif
-}
-// inclusive prefix sum over lanes
-__device__ __forceinline__ double wave_incl_scan(double v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    double o = __shfl_up(v, off);
-    if (lane >= off) v += o;
-  }
-  return v;
-}
-// inclusive suffix sum over lanes
-__device__ __forceinline__ double wave_incl_rscan(double v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    double o = __shfl_down(v, off);
-    if (lane + off < 64) v += o;
-  }
-  return v;
-}
-
-// ---------------------------------------------------------------------------------------------
-// scalar pieces — moma_traj_opt.h:745-830
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double expC2(double tau) {
-  return tau > 0.0 ? ((0.5 * tau + 1.0) * tau + 1.0) : 1.0 / ((0.5 * tau - 1.0) * tau + 1.0);
-}
-__device__ __forceinline__ double logC2(double T) {
-  return T > 1.0 ? (sqrt(2.0 * T - 1.0) - 1.0) : (1.0 - sqrt(2.0 / T - 1.0));
-}
-__device__ __forceinline__ double dTdTau(double tau) {
-  if (tau > 0) return tau + 1.0;
-  double den = (0.5 * tau - 1.0) * tau + 1.0;
-  return (1.0 - tau) / (den * den);
-}
-__device__ __forceinline__ double sigmoidC2(double vq, double max_q) {
-  double e = expC2(vq);
-  return 2.0 * max_q * e / (1.0 + e) - max_q;
-}
-__device__ __forceinline__ double invSigmoidC2(double q, double max_q) {
-  double b = 0.5 * (max_q + q) / max_q;
-  return logC2(b / (1 - b));
-}
-__device__ __forceinline__ double dQdVq(double vq, double max_q) {
-  double e1 = expC2(vq) + 1.0;
-  return 2.0 * max_q * dTdTau(vq) / (e1 * e1);
-}
-// smoothL1Penalty, only meaningful for x > 0 — moma_traj_opt.h:810-830 (constants precomputed in DevParams)
-__device__ __forceinline__ void smoothL1(dev_params_ref P, double x, double mu, double& f, double& df) {
-  if (x < mu) {
-    f = (P.sl_f4c * x + P.sl_f3c) * x * x * x;
-    df = (P.sl_d3c * x + P.sl_d2c) * x * x;
-  } else {
-    f = x - P.sl_half;
-    df = 1.0;
-  }
-}
-// 1/K as a constant factor: the reference divides by int_K in every penalty term (e.g. moma_traj_opt.cpp:1315); a
-// multiplication by the rounded reciprocal differs by at most one ulp and saves an IEEE division per term.
-#define TOPAY_INV_K (1.0 / TOPAY_K)
-
-// ---------------------------------------------------------------------------------------------
-// ESDF interpolation — grid_map.h:364-441 (2-D), 443-509 (3-D); out of map => d = 0, grad = 0
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-// Clamped cell index pair (i, i+1) -> (lo, hi) as grid_map.h:727-733 does, without ever forming i + 1 on an
-// unclamped i: a saturated float->int conversion (points far outside the map) would overflow, and the compiler
-// may assume it does not.
-__device__ __forceinline__ void clamp_pair(int i, int top, int& lo, int& hi) {
-  const int ic = i < -1 ? -1 : (i > top ? top : i);
-  lo = ic < 0 ? 0 : ic;
-  hi = ic + 1 > top ? top : ic + 1;
-}
-
-// Wave-uniform copy of a map descriptor, forced into scalar registers.
-__device__ __forceinline__ double uniform_f64(double v) {
-  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
-  return __hiloint2double(hi, lo);
-}
-// Wave-uniform pointers forced into scalar registers: a value the compiler cannot prove uniform (loaded from the context
-// block in private memory) lives in a vector register, and everything in vector registers that is live across the call of
-// the manipulator block is saved to and restored from scratch memory around it, once per sample pass.
-template <typename T>
-__device__ __forceinline__ T* uniform_gptr(T* p) {
-  const unsigned long long v = (unsigned long long)p;
-  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(v & 0xffffffffu)), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32));
-  return (T*)(((unsigned long long)hi << 32) | lo);
-}
-#ifndef TOPAY_CPU_EMU
-template <typename T>
-__device__ __forceinline__ TOPAY_GLB T* uniform_ptr(TOPAY_GLB T* p) {
-  const unsigned long long v = (unsigned long long)p;
-  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(v & 0xffffffffu)), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32));
-  return (TOPAY_GLB T*)(((unsigned long long)hi << 32) | lo);
-}
-template <typename T>
-__device__ __forceinline__ TOPAY_LDS T* uniform_ptr(TOPAY_LDS T* p) {
-  return (TOPAY_LDS T*)(size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)p);
-}
-#else
-template <typename T>
-__device__ __forceinline__ T* uniform_ptr(T* p) { return p; }
-#endif
-
-__device__ __forceinline__ DevMap load_map(const TOPAY_GLB DevMap* mp) {
-  DevMap m;
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-    m.origin[a] = uniform_f64(mp->origin[a]);
-    m.min_b[a] = uniform_f64(mp->min_b[a]);
-    m.max_b[a] = uniform_f64(mp->max_b[a]);
-    m.dims[a] = __builtin_amdgcn_readfirstlane(mp->dims[a]);
-  }
-  m.res = uniform_f64(mp->res);
-  m.res_inv = uniform_f64(mp->res_inv);
-  m.pad = 0;
-  {
-    const unsigned long long p2 = (unsigned long long)mp->esdf2d, p3 = (unsigned long long)mp->esdf3d;
-    const unsigned lo2 = __builtin_amdgcn_readfirstlane((int)(p2 & 0xffffffffu)), hi2 = __builtin_amdgcn_readfirstlane((int)(p2 >> 32));
-    const unsigned lo3 = __builtin_amdgcn_readfirstlane((int)(p3 & 0xffffffffu)), hi3 = __builtin_amdgcn_readfirstlane((int)(p3 >> 32));
-    m.esdf2d = (glb_cdp)(((unsigned long long)hi2 << 32) | lo2);
-    m.esdf3d = (glb_cdp)(((unsigned long long)hi3 << 32) | lo3);
-  }
-  return m;
-}
-
-__device__ __forceinline__ void esdf2d_query(const DevMap& M, double px, double py, double& dist, double& gx, double& gy) {
-  bool in = !(px < M.min_b[0] + 1e-4 || py < M.min_b[1] + 1e-4 || px > M.max_b[0] - 1e-4 || py > M.max_b[1] - 1e-4);
-  dist = 0.0; gx = 0.0; gy = 0.0;
-  if (in) {
-    const double r = M.res, ri = M.res_inv;
-    int ix = (int)floor((px - 0.5 * r - M.origin[0]) * ri);
-    int iy = (int)floor((py - 0.5 * r - M.origin[1]) * ri);
-    double dx = (px - ((ix + 0.5) * r + M.origin[0])) * ri;
-    double dy = (py - ((iy + 0.5) * r + M.origin[1])) * ri;
-    const int ny = M.dims[1];
-    int x0, x1, y0, y1;
-    clamp_pair(ix, M.dims[0] - 1, x0, x1);
-    clamp_pair(iy, ny - 1, y0, y1);
-    glb_cdp e = M.esdf2d;
-    double v00 = e[(size_t)x0 * ny + y0], v01 = e[(size_t)x0 * ny + y1];
-    double v10 = e[(size_t)x1 * ny + y0], v11 = e[(size_t)x1 * ny + y1];
-    double v0 = v00 * (1 - dx) + v10 * dx;
-    double v1 = v01 * (1 - dx) + v11 * dx;
-    dist = v0 * (1 - dy) + v1 * dy;
-    gy = (v1 - v0) * ri;
-    double g0 = (1 - dy) * (v10 - v00);
-    g0 += dy * (v11 - v01);
-    gx = g0 * ri;
-  }
-}
-
-__device__ __forceinline__ void esdf3d_query(const DevMap& M, double px, double py, double pz, double& dist, double& gx,
-                                             double& gy, double& gz) {
-  bool in = !(px < M.min_b[0] + 1e-4 || py < M.min_b[1] + 1e-4 || pz < M.min_b[2] + 1e-4 ||
-              px > M.max_b[0] - 1e-4 || py > M.max_b[1] - 1e-4 || pz > M.max_b[2] - 1e-4);
-  // branch-free: the gathers are issued unconditionally at clamped indices (so that the scheduler can start them
-  // early and overlap several spheres) and the result is discarded for points outside the map (d = 0, grad = 0)
-  {
-    const double r = M.res, ri = M.res_inv;
-    int ix = (int)floor((px - 0.5 * r - M.origin[0]) * ri);
-    int iy = (int)floor((py - 0.5 * r - M.origin[1]) * ri);
-    int iz = (int)floor((pz - 0.5 * r - M.origin[2]) * ri);
-    double dx = (px - ((ix + 0.5) * r + M.origin[0])) * ri;
-    double dy = (py - ((iy + 0.5) * r + M.origin[1])) * ri;
-    double dz = (pz - ((iz + 0.5) * r + M.origin[2])) * ri;
-    const int ny = M.dims[1], nz = M.dims[2];
-    int x0, x1, y0, y1, z0, z1;
-    clamp_pair(ix, M.dims[0] - 1, x0, x1);
-    clamp_pair(iy, ny - 1, y0, y1);
-    clamp_pair(iz, nz - 1, z0, z1);
-    glb_cdp e = M.esdf3d;
-    size_t b00 = ((size_t)x0 * ny + y0) * nz, b01 = ((size_t)x0 * ny + y1) * nz;
-    size_t b10 = ((size_t)x1 * ny + y0) * nz, b11 = ((size_t)x1 * ny + y1) * nz;
-    double v000 = e[b00 + z0], v001 = e[b00 + z1], v010 = e[b01 + z0], v011 = e[b01 + z1];
-    double v100 = e[b10 + z0], v101 = e[b10 + z1], v110 = e[b11 + z0], v111 = e[b11 + z1];
-    const double ex = 1 - dx, ey = 1 - dy, ez = 1.0 - dz;
-    double v00 = fma(v100, dx, v000 * ex);
-    double v01 = fma(v101, dx, v001 * ex);
-    double v10 = fma(v110, dx, v010 * ex);
-    double v11 = fma(v111, dx, v011 * ex);
-    double v0 = fma(v10, dy, v00 * ey);
-    double v1 = fma(v11, dy, v01 * ey);
-    dist = fma(v1, dz, v0 * ez);
-    gz = (v1 - v0) * ri;
-    gy = fma(v11 - v01, dz, (v10 - v00) * ez) * ri;
-    double g0 = ez * ey * (v100 - v000);
-    g0 = fma(ez * dy, v110 - v010, g0);
-    g0 = fma(dz * ey, v101 - v001, g0);
-    g0 = fma(dz * dy, v111 - v011, g0);
-    gx = g0 * ri;
-  }
-  dist = in ? dist : 0.0; gx = in ? gx : 0.0; gy = in ? gy : 0.0; gz = in ? gz : 0.0;
-}
-
-// The same lookup split in two so that the gathers of the next sphere can be in flight while the penalties of the
-// current one (divergent branches the scheduler will not move loads across) are evaluated.
-//
-// Four 16-byte gathers instead of eight 8-byte ones (round 5).  The two z-neighbours of a corner pair are adjacent doubles of
-// the field (x-major, z fastest), so one load fetches both: the pair starts at zb = min(z0, nz - 2) and the clamped indices z0,
-// z1 (equal at either face of the map) pick their element of it -- the same eight values into the same arithmetic, half the
-// vector-memory instructions.  A gather costs the compute unit's L1 one tag lookup per lane whatever its width, and eight waves
-// of a compute unit share that L1: 96 -> 48 such instructions per call of the manipulator block.  (The loads are 8-byte
-// aligned; a pair that straddles a cache line costs two lookups, one case in eight or sixteen.  nz >= 2 is checked when a map
-// is set: with a single layer the pair would reach past the field.)
-typedef double esdf_pair __attribute__((vector_size(16), aligned(8)));
-struct Esdf3dReq {
-  esdf_pair p00, p01, p10, p11;   // (z pair) of the rows (x0, y0), (x0, y1), (x1, y0), (x1, y1)
-  double dx, dy, dz;
-  bool in, z0hi, z1hi;            // z0 / z1 is the pair's second element
-};
-__device__ __forceinline__ void esdf3d_issue(const DevMap& M, double px, double py, double pz, Esdf3dReq& q) {
-  q.in = !(px < M.min_b[0] + 1e-4 || py < M.min_b[1] + 1e-4 || pz < M.min_b[2] + 1e-4 ||
-           px > M.max_b[0] - 1e-4 || py > M.max_b[1] - 1e-4 || pz > M.max_b[2] - 1e-4);
-  const double r = M.res, ri = M.res_inv;
-  int ix = (int)floor((px - 0.5 * r - M.origin[0]) * ri);
-  int iy = (int)floor((py - 0.5 * r - M.origin[1]) * ri);
-  int iz = (int)floor((pz - 0.5 * r - M.origin[2]) * ri);
-  q.dx = (px - ((ix + 0.5) * r + M.origin[0])) * ri;
-  q.dy = (py - ((iy + 0.5) * r + M.origin[1])) * ri;
-  q.dz = (pz - ((iz + 0.5) * r + M.origin[2])) * ri;
-  const int ny = M.dims[1], nz = M.dims[2];
-  int x0, x1, y0, y1, z0, z1;
-  clamp_pair(ix, M.dims[0] - 1, x0, x1);
-  clamp_pair(iy, ny - 1, y0, y1);
-  clamp_pair(iz, nz - 1, z0, z1);
-  glb_cdp e = M.esdf3d;
-  // One linear index with a multiply (integer multiplies run at a quarter of the vector rate), the other rows by adding the
-  // strides of the axes along which the clamped neighbour differs (x1 - x0, y1 - y0 are 0 or 1).  A field has fewer than
-  // 2^32 cells (checked when the map is set), so the indices are 32-bit.
-  const int zb = z0 < nz - 2 ? z0 : nz - 2;
-  q.z0hi = z0 != zb;
-  q.z1hi = z1 != zb;
-  const unsigned i00 = ((unsigned)x0 * (unsigned)ny + (unsigned)y0) * (unsigned)nz + (unsigned)zb;
-  const unsigned sx = x1 != x0 ? (unsigned)(ny * nz) : 0u, sy = y1 != y0 ? (unsigned)nz : 0u;
-  const unsigned i01 = i00 + sy, i10 = i00 + sx;
-  const unsigned i11 = i10 + sy;
-#ifndef TOPAY_CPU_EMU
-  typedef const TOPAY_GLB esdf_pair* pair_ptr;
-  q.p00 = *(pair_ptr)(e + (size_t)i00);
-  q.p01 = *(pair_ptr)(e + (size_t)i01);
-  q.p10 = *(pair_ptr)(e + (size_t)i10);
-  q.p11 = *(pair_ptr)(e + (size_t)i11);
-#else
-  q.p00[0] = e[(size_t)i00]; q.p00[1] = e[(size_t)i00 + 1];
-  q.p01[0] = e[(size_t)i01]; q.p01[1] = e[(size_t)i01 + 1];
-  q.p10[0] = e[(size_t)i10]; q.p10[1] = e[(size_t)i10 + 1];
-  q.p11[0] = e[(size_t)i11]; q.p11[1] = e[(size_t)i11 + 1];
-#endif
-}
-__device__ __forceinline__ void esdf3d_finish(const DevMap& M, const Esdf3dReq& q, double& dist, double& gx, double& gy,
-                                              double& gz) {
-  const double ri = M.res_inv;
-  const double dx = q.dx, dy = q.dy, dz = q.dz;
-  const double ex = 1 - dx, ey = 1 - dy, ez = 1.0 - dz;
-  const double v000 = q.z0hi ? q.p00[1] : q.p00[0], v001 = q.z1hi ? q.p00[1] : q.p00[0];
-  const double v010 = q.z0hi ? q.p01[1] : q.p01[0], v011 = q.z1hi ? q.p01[1] : q.p01[0];
-  const double v100 = q.z0hi ? q.p10[1] : q.p10[0], v101 = q.z1hi ? q.p10[1] : q.p10[0];
-  const double v110 = q.z0hi ? q.p11[1] : q.p11[0], v111 = q.z1hi ? q.p11[1] : q.p11[0];
-  double v00 = fma(v100, dx, v000 * ex);
-  double v01 = fma(v101, dx, v001 * ex);
-  double v10 = fma(v110, dx, v010 * ex);
-  double v11 = fma(v111, dx, v011 * ex);
-  double v0 = fma(v10, dy, v00 * ey);
-  double v1 = fma(v11, dy, v01 * ey);
-  dist = fma(v1, dz, v0 * ez);
-  gz = (v1 - v0) * ri;
-  gy = fma(v11 - v01, dz, (v10 - v00) * ez) * ri;
-  double g0 = ez * ey * (v100 - v000);
-  g0 = fma(ez * dy, v110 - v010, g0);
-  g0 = fma(dz * ey, v101 - v001, g0);
-  g0 = fma(dz * dy, v111 - v011, g0);
-  gx = g0 * ri;
-  dist = q.in ? dist : 0.0; gx = q.in ? gx : 0.0; gy = q.in ? gy : 0.0; gz = q.in ? gz : 0.0;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Wave-level evaluation context: LDS carve-up + per-trajectory global pointers
-// ---------------------------------------------------------------------------------------------
-struct EvalCtx {
-  int lane, N, rows, n;
-  // several waves per trajectory (topay_eval_mw.h): thread index in the workgroup, wave index, small cross-wave scratch
-  int tid, wave;
-  lds_dp red;    // [8] partial sums of a workgroup reduction (two phases) | [64] pass totals | [2][NW][64] per-round costs | [NW] masks
-  lds_dp adj;    // [9][rows] right-hand sides / solution of the adjoint solve (the coefficients' block: == cL)
-  glb_dp coefg;  // HBM copy of the coefficients (the candidate's result block), read by the dJ/dT correction
-  int cl_in_lds; // the coefficients of the last evaluation are still in C.cL (0 after a gradient phase -- they are in coefg)
-  // LDS
-  lds_dp cL;     // [9][rows]  MINCO coefficients, column d contiguous (the reference's col-major c)
-  lds_dp Tp;     // [5][N]     T, T^2..T^5
-  glb_cdp hd, tl; // HBM [27] each: head / tail PVA, 9x3 col-major (read once per evaluation by the right-hand side)
-  int npass_lds;  // passes the pass-total block of the LDS plan is sized for
-  lds_dp gdT;    // [N]        penalty dJ/dT accumulator
-  lds_dp pcs;    // [4*(N+1)]  per-piece scratch: stage-1 tracking gradient (2N) | piece-end XY (2(N+1))
-  lds_dp gC;     // [9][rows]  penalty dJ/dC accumulator, element (row, d) owned by the row lane of `row`
-  glb_dp sbuf;   // HBM [14][sb_stride]: per-sample gradient rows parked between the cost and the gradient phase
-  int sb_stride;
-  glb_dp mstash; // HBM [sb_stride][36]: forces of self-colliding sphere pairs of a sample (manipulator_block; rarely touched)
-  lds_dp pw;     // [26][6]    integer powers jj^k of the Simpson sample index (constant for the whole solve)
-  lds_dp X;      // union region: band + reciprocal diagonal (14*rows) | sample buffers (26N + 960)
-  // global
-  glb_cdp x;
-  glb_dp g;
-  glb_dp lu;          // [14*rows] stash
-  glb_cdp init_xy;
-  double sx, sy, ex, ey;           // start xy, goal xy
-  double lam0, lam1, rho0, rho1;   // ALM state
-  double fxe0, fxe1;               // final_xy_error of this evaluation (stage 2)
-  // diagnostic build only (TOPAY_STAMPS): per-phase shader-clock accumulators, [16] per trajectory
-  TOPAY_GLB long long* stamps;
-  long long t_last;
-};
-
-// jj^k for jj = 0..25 (sample index within a piece; 25 is read but always multiplied by zero), k = 0..5: the local time of sample jj is jj * hs, so the
-// monomial basis of coefficient row k factors as (jj^k) * hs^k and the row lanes only need the three hs-powers
-// of their row (basis_k(k, hs)) once per pass instead of a power chain per sample.
-__device__ __forceinline__ void fill_power_table(lds_dp pw, int lane) {
-  for (int t = lane; t < 156; t += 64) {
-    const int jj = t / 6, k = t - 6 * jj;
-    double v = 1.0;
-    for (int u = 0; u < k; u++) v *= (double)jj;
-    pw[t] = v;
-  }
-}
-
-#define BAND(i, j) band[((i) - (j) + 6) * rows + (j)]
-
-// Phase stamps for the diagnostic build (-DTOPAY_STAMPS): never compiled into the product library.
-#ifdef TOPAY_STAMPS
-#define STAMP(C, k)                                                    \
-  do {                                                                 \
-    const long long now_ = (long long)__builtin_amdgcn_s_memtime();    \
-    if ((C).stamps && (C).lane == 0) (C).stamps[k] += now_ - (C).t_last; \
-    (C).t_last = (long long)__builtin_amdgcn_s_memtime();              \
-  } while (0)
-#else
-#define STAMP(C, k) do { } while (0)
-#endif
-// sub-interval stamp that does not reset the phase clock
-#ifdef TOPAY_STAMPS
-#define SUBSTAMP_BEGIN(C) const long long sub_t0_ = (long long)__builtin_amdgcn_s_memtime()
-#define SUBSTAMP_END(C, k)                                                                                   \
-  do {                                                                                                       \
-    if ((C).stamps && (C).lane == 0) (C).stamps[k] += (long long)__builtin_amdgcn_s_memtime() - sub_t0_;      \
-  } while (0)
-#else
-#define SUBSTAMP_BEGIN(C) do { } while (0)
-#define SUBSTAMP_END(C, k) do { } while (0)
-#endif
 
 // Decides, once the cost of an evaluation is known, whether its gradient will be used.  In the reference's line search
 // (lbfgs.hpp:318-340) a trial that fails the sufficient-decrease test is discarded without its gradient ever being
@@ -566,131 +65,6 @@ struct GradGate {
     return !(f > thr);                                                             // else: needs g . d
   }
 };
-
-// Banded triangular sweeps with one lane per right-hand side (banded_system.hpp:96-118 and 123-145).
-// The reference's substitutions are column sweeps: step j finalises x(j) and updates the six following (or
-// preceding) entries of the same right-hand side.  The nine right-hand sides are independent, so lane d < 9 owns
-// column d of the 6N x 9 block and carries the six pending entries in registers: a step is six independent
-// multiply-subtracts with no LDS round trip and no barrier (the cross-lane version needed both, ~300 cycles per
-// step).  Arithmetic and its order per entry are unchanged (mul, then sub, j ascending / descending).
-//   MODE 0  L   x = b   (generate, forward):  b(i) -= A(i,j) b(j),            i = j+1..j+6
-//   MODE 1  U   x = b   (generate, backward): b(i) -= A(i,j) (b(j)/A(j,j)),   i = j-1..j-6 ; stores b(j)/A(j,j)
-//   MODE 2  U^T x = b   (adjoint, forward):   b(i) -= A(j,i) (b(j)/A(j,j)),   i = j+1..j+6 ; stores b(j)/A(j,j)
-//   MODE 3  L^T x = b   (adjoint, backward):  b(i) -= A(j,i) b(j),            i = j-1..j-6
-// rows = 6N is a multiple of 6: blocks of six steps with compile-time register indices.
-//
-// The factors are NOT resident in LDS (round 4): the band (84 N doubles) beside the right-hand sides (54 N) was the
-// peak of the LDS plan and decided how many trajectories share a compute unit.  They stream from the candidate's LU
-// block in HBM ([14][rows]: 13 diagonals, then the reciprocal diagonal; written once per evaluation by the
-// factorisation) through two windows of 7 rows x 30 columns in LDS: a chunk is 24 steps (four blocks), all 64 lanes
-// of the wave request the next chunk's window, the nine owner lanes sweep the current one, the requested values are
-// written to the other window.  Window row r holds diagonal D0 + r (D0 = 7: the lower factor, modes 0 and 3; D0 = 0:
-// the upper factor, modes 1 and 2), row 6 the reciprocal diagonal; window column = matrix column - clo.  Which value
-// feeds which multiply-subtract is unchanged.
-#define TOPAY_SWEEP_CHUNK 24
-#define TOPAY_SWEEP_WCOLS 30
-#define TOPAY_SWEEP_WIN (7 * TOPAY_SWEEP_WCOLS)   // doubles per window; the sweeps use two
-template <int MODE>
-__device__ __forceinline__ void band_sweep(lds_dp v, bool owner, glb_cdp lu, lds_dp win, int rows, int lane) {
-  constexpr bool FWD = (MODE == 0 || MODE == 2);
-  constexpr bool SCALE = (MODE == 1 || MODE == 2);
-  constexpr int D0 = (MODE == 0 || MODE == 3) ? 7 : 0;
-  constexpr int CH = TOPAY_SWEEP_CHUNK, WC = TOPAY_SWEEP_WCOLS, WIN = TOPAY_SWEEP_WIN;
-  constexpr int NEL = (SCALE ? 7 : 6) * WC;      // window elements in use
-  constexpr int NQ = (NEL + 63) / 64;            // per lane
-  double w[6];
-  double x = 0.0;
-#pragma unroll
-  for (int t = 0; t < 6; t++) w[t] = 0.0;
-  if (owner) {
-    if (FWD) {
-      x = v[0];
-#pragma unroll
-      for (int t = 0; t < 6; t++) w[t] = v[1 + t];
-    } else {
-      x = v[rows - 1];
-#pragma unroll
-      for (int t = 0; t < 6; t++) w[t] = v[rows - 2 - t];
-    }
-  }
-  const int nchunk = (rows + CH - 1) / CH;
-  // first matrix column of chunk k's window
-  auto chunk_clo = [&](int k) { return FWD ? CH * k : rows - 1 - CH * k - (WC - 1); };
-  auto request = [&](int k, double (&q)[NQ]) {
-    const int clo = chunk_clo(k);
-#pragma unroll
-    for (int u = 0; u < NQ; u++) {
-      const int e = lane + 64 * u;
-      const int r = e / WC, cc = e - r * WC;
-      int c = clo + cc;
-      c = c < 0 ? 0 : (c > rows - 1 ? rows - 1 : c);   // columns outside the matrix only ever feed rows that do not exist
-      const int d = (r < 6 ? D0 + r : 13);
-      q[u] = lu[(d < 14 ? d : 13) * rows + c];         // (e >= NEL: a valid address, the value is dropped)
-    }
-  };
-  auto deposit = [&](int k, const double (&q)[NQ]) {
-    lds_dp wb = win + (k & 1) * WIN;
-#pragma unroll
-    for (int u = 0; u < NQ; u++) {
-      const int e = lane + 64 * u;
-      if (e < NEL) wb[e] = q[u];
-    }
-  };
-  double q[NQ];
-  request(0, q);
-  deposit(0, q);
-  lds_sync();
-  for (int k = 0; k < nchunk; k++) {
-    const bool more = k + 1 < nchunk;
-    if (more) request(k + 1, q);
-    if (owner) {
-      lds_cdp wb = win + (k & 1) * WIN;
-      const int clo = chunk_clo(k);
-#pragma unroll 1
-      for (int b0 = CH * k; b0 < CH * (k + 1) && b0 < rows; b0 += 6) {
-        // everything the block reads from LDS, issued up front: 36 coefficients, 6 scales, 6 incoming entries
-        double cf[6][6], sc[6], nw[6];
-#pragma unroll
-        for (int u = 0; u < 6; u++) {
-          const int j = FWD ? b0 + u : rows - 1 - (b0 + u);
-#pragma unroll
-          for (int t = 1; t <= 6; t++) {
-            int idx;
-            if (MODE == 0) idx = (t - 1) * WC + (j - clo);            // A(j+t, j)
-            else if (MODE == 1) idx = (6 - t) * WC + (j - clo);       // A(j-t, j)
-            else if (MODE == 2) idx = (6 - t) * WC + (j + t - clo);   // A(j, j+t)
-            else idx = (t - 1) * WC + (j - t - clo);                  // A(j, j-t)
-            // Unconditional reads.  Where row i = j +- t falls outside the matrix the value is a never-written zero of
-            // the band (modes 0, 1) or an unrelated entry (modes 2, 3) and only ever feeds window slots of rows that
-            // do not exist and are never stored.
-            cf[u][t - 1] = wb[idx];
-          }
-          if (SCALE) sc[u] = wb[6 * WC + (j - clo)];
-          int in = FWD ? j + 7 : j - 7;
-          in = in < 0 ? 0 : (in > rows - 1 ? rows - 1 : in);
-          nw[u] = v[in];
-        }
-        double xo[6];
-#pragma unroll
-        for (int u = 0; u < 6; u++) {
-          const double xs = SCALE ? x * sc[u] : x;
-          xo[u] = xs;
-#pragma unroll
-          for (int t = 0; t < 6; t++) w[(u + t) % 6] -= cf[u][t] * xs;
-          x = w[u % 6];
-          w[u % 6] = nw[u];
-        }
-#pragma unroll
-        for (int u = 0; u < 6; u++) {
-          const int j = FWD ? b0 + u : rows - 1 - (b0 + u);
-          v[j] = xo[u];
-        }
-      }
-    }
-    if (more) deposit(k + 1, q);
-    lds_sync();
-  }
-}
 
 // polynomial basis of local time s: b0 = s^k, b1, b2, b3 derivatives — moma_traj_opt.cpp:1263-1270
 struct Basis {
@@ -733,376 +107,6 @@ __device__ __forceinline__ void xy_integrand(lds_cdp cL, int rows, int i, double
   det_sincos(th, &sn, &cn);
   fx = sd * cn;
   fy = sd * sn;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Stage-2 manipulator block of one even sample: FK (moma_param.h:203-247), 12 ESDF lookups
-// (moma_traj_opt.cpp:1477-1520), self collision (1521-1612), Jacobian-transpose (moma_param.h:249-337),
-// joint position limits (1616-1666).
-//
-// World sphere centre  P_k = p0 + A * rho_k,  A = Rz(theta) * relative_R,  p0 = (x, y, h) + Rz(theta) * relative_t,
-// where rho_k comes from the joint chain run in the arm-local frame (pure rotations).  relative_R is the
-// reference's 0.7071068 literal matrix, i.e. not exactly orthonormal, so the joint torques are formed in the local
-// frame from g' = A^T g:  tau_i = u_i . sum (rho - o_{i+1}) x g'  — the exact derivative of the reference's matrix
-// products for any A, unlike the world-frame axis x r form.  Yaw and x, y are taken in the world frame (Rz exact).
-// pos = (x, y, theta, q1..q7).  Returns cost and the "/K" gdT part; moma_grad[10] = d/d(x, y, theta, q).
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void joint_rotate(double* R, int i, double c_, double s_) {
-  if (i % 2 == 0) {  // R <- R * Rz(q): mixes columns 0,1
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-      const double r0 = R[a * 3 + 0], r1 = R[a * 3 + 1];
-      R[a * 3 + 0] = fma(r0, c_, r1 * s_);
-      R[a * 3 + 1] = fma(r1, c_, -(r0 * s_));
-    }
-  } else {  // R <- R * Ry(q): mixes columns 0,2
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-      const double r0 = R[a * 3 + 0], r2 = R[a * 3 + 2];
-      R[a * 3 + 0] = fma(r0, c_, -(r2 * s_));
-      R[a * 3 + 2] = fma(r0, s_, r2 * c_);
-    }
-  }
-}
-
-// Interface (round 5).  Nothing of the block's inputs or outputs travels through the stack any more:
-//   * in: the sample (piece i, even sample index j, local half step, step) and its XY position -- the pose (theta, q1..q7)
-//     is evaluated HERE from the coefficients in LDS (round 4 passed the ten pose values by value: 16 of the 32 argument
-//     dwords went through scratch memory because the hidden return-value pointer took the 33rd register);
-//   * out: five doubles in registers (an aggregate of at most 16 dwords is returned in VGPRs): d/dx, d/dy, d/dtheta, cost and
-//     the "/K" dJ/dT part; the seven joint entries of moma_grad go to the lane's column of seven rows of the wave's LDS pass
-//     buffer (mg_lds[q * 64], q = 0..6: the buffer is idle during the sample passes), each as soon as its torque is known --
-//     what the 12-double return value in scratch memory did for the register pressure of the block's last part, without the
-//     scratch memory.
-// e = the sample's index in the candidate's self-collision block, -1 for a padding lane (results dropped, no HBM write).
-struct ManiOut {
-  double gx, gy, gth;
-  double cost, gdT;
-};
-#ifdef TOPAY_ASM_MARKS   // (probe builds: comment lines in the assembly that delimit the sections of the block)
-#define MMARK(k) asm volatile("; TOPAY_MARK " #k)
-#else
-#define MMARK(k) do { } while (0)
-#endif
-#ifdef TOPAY_STAMPS
-__device__ long long g_mani_stamps[8];
-#define MSTAMP(k)                                                                                   \
-  do {                                                                                              \
-    const long long now_ = (long long)__builtin_amdgcn_s_memtime();                                 \
-    if (blockIdx.x == 0 && threadIdx.x == 0) g_mani_stamps[k] += now_ - mt_;                        \
-    mt_ = now_;                                                                                     \
-  } while (0)
-#else
-#define MSTAMP(k) do { } while (0)
-#endif
-// Register plan (round 4).  OCC = waves per SIMD the caller's kernel is built for: 1 -> 512 registers per lane, 2 -> 256.
-// The block used to hold the 12 sphere centres AND 12 force accumulators (144 VGPRs) because the rare self-collision
-// pairs add to the forces of two spheres at once, ahead of the per-sphere terms.  Now a sphere's force is born in the
-// iteration of the sphere loop that consumes its centre (the arm-local force takes the centre's registers), and the pair
-// contributions -- needed by fewer than one sample in a thousand -- are accumulated in an HBM block by the lanes that
-// have any, in the pair order of before, and read back at the top of the sphere's iteration: same operands, same order,
-// same bits as the 144-register version.  LA = spheres whose ESDF gathers are issued ahead (2 with one wave per SIMD;
-// 1 with two, where the other wave covers the latency and the request registers are what is scarce).
-template <int OCC>
-__device__ __noinline__ ManiOut manipulator_block(const TOPAY_GLB DevMap* mp, lds_cdp cL, int rows, int pi, int pj, double half, double step,
-                                                  double posx, double posy, int e, glb_dp mstash, lds_dp mg_lds) {
-  dev_params_ref P = dev_params();
-  const DevMap M = load_map(mp);
-  const bool in_act = e >= 0;
-  const double invK = topay_hold_f64(TOPAY_INV_K), ten = topay_hold_f64(10.0);
-  const glb_dp in_stash = mstash + 36 * (in_act ? e : 0);
-  // pose of the sample: order-0 polynomials of theta and the seven joints (the arc length is not part of the pose), in the
-  // arithmetic of poly4 / make_basis
-  double pos[10];
-  pos[0] = posx; pos[1] = posy;
-  double sth, cth;
-  {
-    const double s1 = pj * half;
-    const double s2 = s1 * s1, s3 = s2 * s1, s4 = s2 * s2, s5 = s3 * s2;
-#pragma unroll
-    for (int d = 0; d < 9; d++) {
-      if (d == 1) continue;
-      lds_cdp c = cL + d * rows + 6 * pi;
-      pos[d == 0 ? 2 : d + 1] = fma(c[5], s5, fma(c[4], s4, fma(c[3], s3, fma(c[2], s2, fma(c[1], s1, c[0])))));
-    }
-  }
-  const double omg = (pj == 0 || pj == 2 * TOPAY_K) ? 0.5 : 1.0;
-  ManiOut out;
-  double cost, gdTk;
-  const double mu = P.relu_mu;
-  const double w = omg * step;
-#ifdef TOPAY_STAMPS
-  long long mt_ = (long long)__builtin_amdgcn_s_memtime();
-#endif
-  double sq[7], cq[7];
-  {
-    // yaw and the seven joints, step by step across the eight angles (det_sincos_n: the constants of a step are formed once)
-    double ang[8], sn8[8], cs8[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) ang[i] = pos[2 + i];
-    det_sincos_n<8>(ang, sn8, cs8);
-    sth = sn8[0]; cth = cs8[0];
-#pragma unroll
-    for (int i = 0; i < 7; i++) { sq[i] = sn8[1 + i]; cq[i] = cs8[1 + i]; }
-  }
-  MSTAMP(0);  // 8 sincos
-  MMARK(0);
-  double A[9];
-  {
-    const double Rz[9] = {cth, -sth, 0.0, sth, cth, 0.0, 0.0, 0.0, 1.0};
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-#pragma unroll
-      for (int b = 0; b < 3; b++)
-        A[a * 3 + b] = Rz[a * 3 + 0] * P.relR[0 * 3 + b] + Rz[a * 3 + 1] * P.relR[1 * 3 + b] + Rz[a * 3 + 2] * P.relR[2 * 3 + b];
-  }
-  const double p0x = pos[0] + (cth * P.relT[0] - sth * P.relT[1]);
-  const double p0y = pos[1] + (sth * P.relT[0] + cth * P.relT[1]);
-  const double p0z = P.p0z;
-  // walk 1: world sphere centres (the arm-local rho_k are not kept; the torque walks below regenerate them)
-  // spheres per link: link0:{0,1} 1:{2} 2:{3,4} 3:{5} 4:{6,7} 5:{8} 6:{9,10} 7:{11}
-  double Px[TOPAY_NSPH], Py[TOPAY_NSPH], Pz[TOPAY_NSPH];
-  {
-    double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
-    double q0 = 0.0, q1 = 0.0, q2 = 0.0;
-    int sidx = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-      const int cnt = (i % 2 == 0) ? 2 : 1;
-#pragma unroll
-      for (int c = 0; c < cnt; c++) {
-        const double lx = fma(R[2], P.sph_off[sidx], q0), ly = fma(R[5], P.sph_off[sidx], q1), lz = fma(R[8], P.sph_off[sidx], q2);
-        Px[sidx] = p0x + fma(A[2], lz, fma(A[1], ly, A[0] * lx));
-        Py[sidx] = p0y + fma(A[5], lz, fma(A[4], ly, A[3] * lx));
-        Pz[sidx] = p0z + fma(A[8], lz, fma(A[7], ly, A[6] * lx));
-        sidx++;
-      }
-      q0 = fma(R[2], P.colli_length[i], q0);
-      q1 = fma(R[5], P.colli_length[i], q1);
-      q2 = fma(R[8], P.colli_length[i], q2);
-      if (i == 7) break;
-      joint_rotate(R, i, cq[i], sq[i]);
-      TOPAY_SCHED_FENCE();
-    }
-  }
-  MSTAMP(1);  // walk 1
-  MMARK(1);
-  // The joints' cosines wait in the lane's LDS column (the seven words that take the torques at the end) while the sphere
-  // loop needs the registers: walk 2a reads them from there, walk 2b reads word i before torque i is written to it.  (They
-  // and the sines used to be spilled to scratch memory across the loop by the compiler: 14 of the block's 25 spilled values.)
-#pragma unroll
-  for (int i = 0; i < 7; i++) mg_lds[i * 64] = cq[i];
-  cost = 0.0;
-  gdTk = 0.0;
-  const double wMC = P.s2_mani_colli_weight, wSC = P.s2_self_colli_weight;
-  // sphere pairs: collision_matrix == -1 <=> non-adjacent spheres (moma_param.h:128-143: at the zero pose
-  // only self and neighbouring spheres overlap) — moma_traj_opt.cpp:1566-1611
-  // The clearances of all 55 pairs are independent straight-line arithmetic; only a lane that sees a positive one walks
-  // the penalty path, which recomputes the same expressions and keeps the forces of the two spheres in its column of the
-  // HBM block (read-modify-write, pair order).
-  bool anypair;
-  {
-    double worst[TOPAY_NSPH - 2];
-    double wall = -1.0;
-#pragma unroll
-    for (int a = 0; a < TOPAY_NSPH - 2; a++) {
-      worst[a] = -1.0;
-#pragma unroll
-      for (int b = a + 2; b < TOPAY_NSPH; b++) {
-        const double dx = Px[a] - Px[b], dy = Py[a] - Py[b], dz = Pz[a] - Pz[b];
-        const double dist = P.pair_rr2[a * TOPAY_NSPH + b] - fma(dz, dz, fma(dy, dy, dx * dx));
-        worst[a] = fmax(worst[a], dist);
-      }
-      wall = fmax(wall, worst[a]);
-    }
-    anypair = in_act && wall > 0;
-    if (anypair) {
-      // (the centres are made opaque here: otherwise the compiler keeps the 165 coordinate differences of the screening
-      // above alive for this path -- in scratch memory -- instead of recomputing the few it needs)
-#pragma unroll
-      for (int k = 0; k < TOPAY_NSPH; k++) { TOPAY_OPAQUE(Px[k]); TOPAY_OPAQUE(Py[k]); TOPAY_OPAQUE(Pz[k]); }
-      const glb_dp sg = in_stash;
-#pragma unroll
-      for (int v = 0; v < 3 * TOPAY_NSPH; v++) sg[v] = 0.0;
-#pragma unroll
-      for (int a = 0; a < TOPAY_NSPH - 2; a++) {
-        if (worst[a] > 0) {
-#pragma unroll
-          for (int b = a + 2; b < TOPAY_NSPH; b++) {
-            const double dx = Px[a] - Px[b], dy = Py[a] - Py[b], dz = Pz[a] - Pz[b];
-            const double dist = P.pair_rr2[a * TOPAY_NSPH + b] - fma(dz, dz, fma(dy, dy, dx * dx));
-            if (dist > 0) {
-              double pe, pd;
-              smoothL1(P, dist, mu, pe, pd);
-              const double sc = -w * wSC * pd * 2.0;
-              sg[3 * a + 0] = fma(sc, dx, sg[3 * a + 0]);
-              sg[3 * a + 1] = fma(sc, dy, sg[3 * a + 1]);
-              sg[3 * a + 2] = fma(sc, dz, sg[3 * a + 2]);
-              sg[3 * b + 0] = fma(-sc, dx, sg[3 * b + 0]);
-              sg[3 * b + 1] = fma(-sc, dy, sg[3 * b + 1]);
-              sg[3 * b + 2] = fma(-sc, dz, sg[3 * b + 2]);
-              gdTk += omg * wSC * (pe * invK);
-              cost += w * wSC * pe;
-            }
-          }
-        }
-      }
-    }
-  }
-  MSTAMP(2);  // sphere pairs
-  MMARK(2);
-  // chassis top (spheres with index > 2, 1525-1539) and environment collision (1477-1520)
-  double bFx = 0.0, bFy = 0.0, bMz = 0.0;  // base: x, y, yaw (everything rotates about the vertical axis through (x, y))
-  constexpr int LA = OCC >= 2 ? TOPAY_ESDF_LOOKAHEAD_OCC2 : TOPAY_ESDF_LOOKAHEAD;  // spheres whose gathers are issued ahead
-  Esdf3dReq rq[LA + 1];
-  double Lx[TOPAY_NSPH], Ly[TOPAY_NSPH], Lz[TOPAY_NSPH];   // arm-local forces g' = A^T g
-#pragma unroll
-  for (int k = 0; k < LA; k++) esdf3d_issue(M, Px[k], Py[k], Pz[k], rq[k]);
-#pragma unroll
-  for (int k = 0; k < TOPAY_NSPH; k++) {
-    if (k + LA < TOPAY_NSPH) esdf3d_issue(M, Px[k + LA], Py[k + LA], Pz[k + LA], rq[(k + LA) % (LA + 1)]);
-    double Gx = 0.0, Gy = 0.0, Gz = 0.0;
-    if (anypair) {
-      const glb_cdp sg = in_stash;
-      Gx = sg[3 * k + 0]; Gy = sg[3 * k + 1]; Gz = sg[3 * k + 2];
-    }
-    if (k >= 3) {
-      const double height = P.sph_top[k] - Pz[k];
-      if (height > 0) {
-        double pe, pd;
-        smoothL1(P, height, mu, pe, pd);
-        Gz += -w * wSC * pd;
-        gdTk += omg * wSC * (pe * invK);
-        cost += w * wSC * pe;
-      }
-    }
-    double d, gx, gy, gz;
-#ifdef TOPAY_STAMPS
-    {
-      // exposed latency of this sphere's four pair gathers: cycles until they have returned (the 4 min(LA, spheres left)
-      // issued after them may stay in flight), measured where the first of them is needed
-      const long long w0_ = (long long)__builtin_amdgcn_s_memtime();
-      constexpr int FULL = 4 * LA;   // (four pair gathers per sphere) s_waitcnt vmcnt(n): expcnt / lgkmcnt fields left at their maxima
-      const int left = TOPAY_NSPH - 1 - k;
-      if (left >= LA) __builtin_amdgcn_s_waitcnt(0x0f70 | (FULL & 15) | ((FULL >> 4) << 14));
-      else if (left == 1) __builtin_amdgcn_s_waitcnt(0x0f70 | 4);
-      else __builtin_amdgcn_s_waitcnt(0x0f70);
-      const long long w1_ = (long long)__builtin_amdgcn_s_memtime();
-      if (blockIdx.x == 0 && threadIdx.x == 0) { g_mani_stamps[6] += w1_ - w0_; g_mani_stamps[7] += 1; }
-    }
-#endif
-    esdf3d_finish(M, rq[k % (LA + 1)], d, gx, gy, gz);
-    const double viola = P.sph_viol[k] - d * ten;
-    if (viola > 0) {
-      double pe, pd;
-      smoothL1(P, viola, mu, pe, pd);
-      const double sc = -w * wMC * pd;
-      Gx += sc * gx * ten; Gy += sc * gy * ten; Gz += sc * gz * ten;
-      gdTk += omg * wMC * (pe * invK);
-      cost += w * wMC * pe;
-    }
-    bFx += Gx;
-    bFy += Gy;
-    bMz = fma(Px[k] - pos[0], Gy, fma(-(Py[k] - pos[1]), Gx, bMz));
-    // g' = A^T g (arm-local frame); the world position is no longer needed
-    Lx[k] = fma(A[6], Gz, fma(A[3], Gy, A[0] * Gx));
-    Ly[k] = fma(A[7], Gz, fma(A[4], Gy, A[1] * Gx));
-    Lz[k] = fma(A[8], Gz, fma(A[5], Gy, A[2] * Gx));
-    if (OCC >= 2 && TOPAY_OCC2_FENCE) __builtin_amdgcn_sched_barrier(0);
-    TOPAY_SCHED_FENCE();
-  }
-  MSTAMP(3);  // ESDF loop
-  MMARK(3);
-  // joints: tau_i = u_i . (Mo_beyond - o_{i+1} x F_beyond) with F, Mo = sums of g' and rho x g'.
-  // walk 2a accumulates the totals, walk 2b peels off the links at or below each joint.
-  double Fx = 0, Fy = 0, Fz = 0, Mx = 0, My = 0, Mz = 0;
-  {
-    double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
-    double q0 = 0.0, q1 = 0.0, q2 = 0.0;
-    int sidx = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-      const int cnt = (i % 2 == 0) ? 2 : 1;
-#pragma unroll
-      for (int c = 0; c < cnt; c++) {
-        const double lx = fma(R[2], P.sph_off[sidx], q0), ly = fma(R[5], P.sph_off[sidx], q1), lz = fma(R[8], P.sph_off[sidx], q2);
-        Fx += Lx[sidx]; Fy += Ly[sidx]; Fz += Lz[sidx];
-        Mx = fma(ly, Lz[sidx], fma(-lz, Ly[sidx], Mx));
-        My = fma(lz, Lx[sidx], fma(-lx, Lz[sidx], My));
-        Mz = fma(lx, Ly[sidx], fma(-ly, Lx[sidx], Mz));
-        sidx++;
-      }
-      q0 = fma(R[2], P.colli_length[i], q0);
-      q1 = fma(R[5], P.colli_length[i], q1);
-      q2 = fma(R[8], P.colli_length[i], q2);
-      if (i == 7) break;
-      joint_rotate(R, i, mg_lds[i * 64], sq[i]);
-      TOPAY_SCHED_FENCE();
-    }
-  }
-  {
-    double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
-    double o0 = 0.0, o1 = 0.0, o2 = 0.0;
-    int sidx = 0;
-#pragma unroll
-    for (int i = 0; i < 7; i++) {
-      const int cnt = (i % 2 == 0) ? 2 : 1;
-#pragma unroll
-      for (int c = 0; c < cnt; c++) {  // remove link i's spheres from the "beyond" sums
-        const double lx = fma(R[2], P.sph_off[sidx], o0), ly = fma(R[5], P.sph_off[sidx], o1), lz = fma(R[8], P.sph_off[sidx], o2);
-        Fx -= Lx[sidx]; Fy -= Ly[sidx]; Fz -= Lz[sidx];
-        Mx = fma(-ly, Lz[sidx], fma(lz, Ly[sidx], Mx));
-        My = fma(-lz, Lx[sidx], fma(lx, Lz[sidx], My));
-        Mz = fma(-lx, Ly[sidx], fma(ly, Lx[sidx], Mz));
-        sidx++;
-      }
-      o0 = fma(R[2], P.colli_length[i], o0);
-      o1 = fma(R[5], P.colli_length[i], o1);
-      o2 = fma(R[8], P.colli_length[i], o2);
-      const double cqi_ = mg_lds[i * 64];   // (read before the torque takes the word)
-      // joint i turns frame i about its local z (even i) or y (odd i) axis through o_{i+1}
-      const int ac = (i % 2 == 0) ? 2 : 1;
-      const double ax = R[0 * 3 + ac], ay = R[1 * 3 + ac], az = R[2 * 3 + ac];
-      const double tx = Mx - fma(o1, Fz, -(o2 * Fy));
-      const double ty = My - fma(o2, Fx, -(o0 * Fz));
-      const double tz = Mz - fma(o0, Fy, -(o1 * Fx));
-      mg_lds[i * 64] = fma(az, tz, fma(ay, ty, ax * tx));
-      joint_rotate(R, i, cqi_, sq[i]);
-      TOPAY_SCHED_FENCE();
-    }
-  }
-  MSTAMP(4);  // walks 2a/2b
-  MMARK(4);
-  // joint position limits — moma_traj_opt.cpp:1616-1666 (symmetric joint_pos_limit_max, reference quirk); the rare
-  // contribution to a joint's entry is a read-modify-write of the lane's own LDS word
-  const double wJP = P.s2_mani_pos_weight;
-#pragma unroll
-  for (int ji = 0; ji < 7; ji++) {
-    double v = pos[ji + 3] - P.joint_pos_limit_max[ji];
-    if (v > 0) {
-      double pe, pd;
-      smoothL1(P, v, mu, pe, pd);
-      mg_lds[ji * 64] += w * wJP * pd;
-      gdTk += omg * wJP * (pe * invK);
-      cost += w * wJP * pe;
-    }
-    v = -P.joint_pos_limit_max[ji] - pos[ji + 3];
-    if (v > 0) {
-      double pe, pd;
-      smoothL1(P, v, mu, pe, pd);
-      mg_lds[ji * 64] -= w * wJP * pd;
-      gdTk += omg * wJP * (pe * invK);
-      cost += w * wJP * pe;
-    }
-  }
-  MSTAMP(5);  // joint limits
-  MMARK(5);
-  out.gx = bFx;
-  out.gy = bFy;
-  out.gth = bMz;
-  out.cost = cost;
-  out.gdT = gdTk;
-  return out;
 }
 
 // kinodynamic penalties shared by both stages — moma_traj_opt.cpp:1059-1115 / 1334-1462.
@@ -1180,7 +184,6 @@ __device__ __forceinline__ void basis_k(int k, double s, double& b0, double& b1,
 // Body of one even Simpson sample (i, j) of sweep 1: kinodynamic penalties, and in stage 2 the chassis ESDF query, the
 // manipulator block and the joint velocity / acceleration limits.  Outputs the per-sample gradient rows gB[12]
 // (theta orders 0-2, s orders 1-2, joints order 0), the sample's dJ/dT part, its positional gradient and its cost.
-// Shared by the one-wave and the several-waves evaluation: same arithmetic, same bits.
 //
 // Stage 2 is two functions around the call of the block, sample_mani() and sample_rest(): the caller forms the sample's
 // geometry (piece, sample index, step, position) from the lane number before the call and AGAIN after it -- everything a
@@ -1261,7 +264,6 @@ __device__ __forceinline__ void sample_rest(dev_params_ref P, lds_cdp cL, int ro
       const double mgq = mg_lds[q * 64];   // the block's d/dq_q, from the lane's column of the pass buffer
       gB[5 + q] = mgq;                     // gradBeta row 0 of the joints (1671)
       qacc += mgq * a1;
-      TOPAY_SCHED_FENCE();
     }
     cst = cst + mo_.cost;
     gdTs = gdTs + mo_.gdT;
@@ -1271,6 +273,855 @@ __device__ __forceinline__ void sample_rest(dev_params_ref P, lds_cdp cL, int ro
     gdTs += mo_.gth * th1 * real_alpha;   // (1670)
     gdTs += qacc * real_alpha;            // (1672)
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The evaluation, NW waves.  RMAX = system rows per thread (rows <= 64 NW RMAX), N <= 64 NW.
+// ---------------------------------------------------------------------------------------------
+template <int STAGE, int RMAX, int NW, int OCC = 1>
+__device__ __noinline__ TOPAY_CALLS_BIG_FUNCTIONS double eval_cost_grad(EvalCtx& C, const TOPAY_GLB DevMap* mp, const GradGate gate) {
+  constexpr int NT = 64 * NW;
+  // (wave-uniform context fields into scalar registers: what stays in vector registers is saved and restored around every
+  // call of the manipulator block)
+  const lds_dp c_Tp = uniform_ptr(C.Tp);
+  const lds_dp c_X = uniform_ptr(C.X);
+  const double c_ex = uniform_f64(C.ex);
+  const double c_ey = uniform_f64(C.ey);
+  const glb_dp c_g = uniform_ptr(C.g);
+  const lds_dp c_gdT = uniform_ptr(C.gdT);
+  const glb_cdp c_init_xy = uniform_ptr(C.init_xy);
+  const double c_lam0 = uniform_f64(C.lam0);
+  const double c_lam1 = uniform_f64(C.lam1);
+  const glb_dp c_lu = uniform_ptr(C.lu);
+  const lds_dp c_pcs = uniform_ptr(C.pcs);
+  const lds_dp c_pw = uniform_ptr(C.pw);
+  const double c_rho0 = uniform_f64(C.rho0);
+  const double c_rho1 = uniform_f64(C.rho1);
+  const double c_sx = uniform_f64(C.sx);
+  const double c_sy = uniform_f64(C.sy);
+  const glb_cdp c_x = uniform_ptr(C.x);
+  const lds_dp c_red = uniform_ptr(C.red);
+  const lds_dp c_adj = uniform_ptr(C.adj);
+  const glb_dp c_coefg = uniform_ptr(C.coefg);
+
+  dev_params_ref P = dev_params();
+  // (lane and tid are formed again after every call of the manipulator block -- fresh_lane_id -- instead of being kept
+  // across it: what a lane holds in vector registers across the call goes through scratch memory)
+  int lane = C.lane, tid = C.tid;
+  const int wave = __builtin_amdgcn_readfirstlane(C.wave);
+  const int N = __builtin_amdgcn_readfirstlane(C.N), rows = __builtin_amdgcn_readfirstlane(C.rows);
+  lds_cdp cL = uniform_ptr(C.cL);
+  const glb_dp c_sbuf = uniform_ptr(C.sbuf);
+  const glb_dp c_mstash = uniform_ptr(C.mstash);
+  const int c_sbs = __builtin_amdgcn_readfirstlane(C.sb_stride);
+  const double g_skip_thr = uniform_f64(gate.skip_thr);
+  const bool g_early_ok = __builtin_amdgcn_readfirstlane(gate.early_ok ? 1 : 0) != 0;
+  GradGate ugate;   // the line search's gate in scalar registers (it is consulted after the sample passes)
+  ugate.always = __builtin_amdgcn_readfirstlane(gate.always ? 1 : 0) != 0;
+  ugate.has_early = __builtin_amdgcn_readfirstlane(gate.has_early ? 1 : 0) != 0;
+  ugate.finit = uniform_f64(gate.finit); ugate.thr = uniform_f64(gate.thr); ugate.early = uniform_f64(gate.early);
+  ugate.early_ok = g_early_ok; ugate.skip_thr = g_skip_thr;
+  int rp = 0;                                  // phase of the workgroup-reduction scratch
+  const int npl = __builtin_amdgcn_readfirstlane(C.npass_lds);
+  constexpr int RD = eval_red_doubles(NW);     // (one wave: the reductions need no LDS)
+  const lds_dp ptot = c_red + RD;              // [npass][2] pass totals of the XY prefix / chain suffix
+  const lds_dp csr = c_red + RD + 2 * npl;     // [2][NW][64] pass costs of one round (two rounds in flight; NW > 1 only)
+  TOPAY_LDS unsigned long long* jmask = (TOPAY_LDS unsigned long long*)(c_red + RD + 2 * npl + (NW > 1 ? 2 * NW * 64 : 0));   // [NW]
+  constexpr int PBR = eval_pb_rows(NW);        // rows of a wave's pass buffer
+  minco_generate<NW, OCC>(C);
+
+  // ---- jerk energy per piece (thread <-> piece; N <= NT); its dJ/dT part is formed in the gradient phase, from the same
+  // expressions (it would otherwise be carried in a register across every call of the manipulator block)
+  auto jerk_terms = [&](int i, double& e_out, double& gdT_out) __attribute__((always_inline)) {
+    double w33 = 0, w43 = 0, w44 = 0, w53 = 0, w54 = 0, w55 = 0;
+#pragma unroll
+    for (int d = 0; d < 9; d++) {
+      const double c3 = cL[d * rows + 6 * i + 3], c4 = cL[d * rows + 6 * i + 4], c5 = cL[d * rows + 6 * i + 5];
+      const double e = P.energy_weights[d];
+      w33 += (c3 * e) * c3; w43 += (c4 * e) * c3; w44 += (c4 * e) * c4;
+      w53 += (c5 * e) * c3; w54 += (c5 * e) * c4; w55 += (c5 * e) * c5;
+    }
+    const double T1 = c_Tp[i], T2 = c_Tp[N + i], T3 = c_Tp[2 * N + i], T4 = c_Tp[3 * N + i], T5 = c_Tp[4 * N + i];
+    e_out = 36.0 * w33 * T1 + 144.0 * w43 * T2 + 192.0 * w44 * T3 + 240.0 * w53 * T3 + 720.0 * w54 * T4 + 720.0 * w55 * T5;
+    gdT_out = 36.0 * w33 + 288.0 * w43 * T1 + 576.0 * w44 * T2 + 720.0 * w53 * T2 + 2880.0 * w54 * T3 + 3600.0 * w55 * T4;
+  };
+  double jerk_e = 0.0;
+  if (tid < N) {
+    double unused_;
+    jerk_terms(tid, jerk_e, unused_);
+  }
+  const double jerk_cost = wg_sum<NW>(c_red, rp, wave, jerk_e);
+
+  lds_dp gxy = c_X;                             // [13N][2] XY prefix of each even sample, then its positional gradient
+  lds_dp pball = c_X + 26 * N;                  // [NW][PBR][64] one pass buffer per wave
+  lds_dp pbuf = pball + wave * (PBR * 64);
+  const int NE = TOPAY_EP * N;
+  const int npass = (NE + 63) / 64;
+  const int nround = (npass + NW - 1) / NW;
+  const double wT = STAGE == 1 ? P.s1_time_weight : P.s2_time_weight;
+  const double time_cost = wT * wg_sum<NW>(c_red, rp, wave, tid < N ? c_Tp[tid] : 0.0);
+  bool skip_body = false;
+  double f_skip = 0.0;
+  if (STAGE == 2 && g_early_ok) {
+    const double partial = jerk_cost + time_cost;
+    if (partial > g_skip_thr && partial <= 1.79769313486231570e308) {
+      skip_body = true;
+      f_skip = partial;
+    }
+  }
+  const double wM = STAGE == 1 ? P.s1_moment_weight : P.s2_moment_weight;
+  const double wA = STAGE == 1 ? P.s1_acc_weight : P.s2_acc_weight;
+  const double wD = STAGE == 1 ? P.s1_domega_weight : P.s2_domega_weight;
+
+  STAMP(C, 3);  // jerk, row bookkeeping
+  // =========================== sweep 1, phase A: Simpson panels, prefix inside each pass, pass totals
+  for (int k = 0; k < nround; k++) {
+    const int pass = k * NW + wave;
+    if (pass < npass) {
+      const int e = pass * 64 + lane;
+      const bool act = e < NE;
+      const int i = act ? e / TOPAY_EP : N - 1;
+      const int m = act ? e - TOPAY_EP * i : 0;
+      const int j = 2 * m;
+      const double T1 = c_Tp[i];
+      const double step = T1 / TOPAY_K, half = step / 2.0, coeff = step / 6.0;
+      double f0x, f0y, Ix = 0.0, Iy = 0.0;
+      xy_integrand(cL, rows, i, j * half, f0x, f0y);
+      if (act && m < TOPAY_K) {
+        double f1x, f1y, f2x, f2y;
+        xy_integrand(cL, rows, i, (j + 1) * half, f1x, f1y);
+        xy_integrand(cL, rows, i, (j + 2) * half, f2x, f2y);
+        Ix = coeff * f0x + 4 * coeff * f1x + coeff * f2x;
+        Iy = coeff * f0y + 4 * coeff * f1y + coeff * f2y;
+      }
+      const double incx = wave_incl_scan(Ix, lane), incy = wave_incl_scan(Iy, lane);
+      if (act) {
+        gxy[2 * e] = incx - Ix;
+        gxy[2 * e + 1] = incy - Iy;
+      }
+      if (lane == 63) {
+        ptot[2 * pass] = incx;
+        ptot[2 * pass + 1] = incy;
+      }
+    }
+  }
+  wg_barrier<NW>();
+
+  // =========================== sweep 1, phase B: sample bodies, one pass per wave and round
+  double carryx = 0.0, carryy = 0.0;   // XY prefix carried across passes: the totals of the passes before `pc`, added in order (scalar registers)
+  int pc = 0;
+  double cost_pen = 0.0;               // per-lane penalty cost in the one-wave order: lane l adds its sample of pass 0, 1, 2, ...
+  for (int k = 0; k < nround; k++) {
+    const int pass = k * NW + wave;
+    double cst_out = 0.0;
+    if (pass < npass) {
+      while (pc < pass) {
+        carryx = uniform_f64(carryx + ptot[2 * pc]);
+        carryy = uniform_f64(carryy + ptot[2 * pc + 1]);
+        pc++;
+      }
+      // the sample of lane ln in this pass: index, piece, step, XY position (prefix inside the pass + carry)
+      int e, i, m, j;
+      bool act;
+      double step, half, posx, posy;
+      auto geometry = [&](int ln) __attribute__((always_inline)) {
+        e = pass * 64 + ln;
+        act = e < NE;
+        i = act ? e / TOPAY_EP : N - 1;
+        m = act ? e - TOPAY_EP * i : 0;
+        j = 2 * m;
+        const double T1 = c_Tp[i];
+        step = T1 / TOPAY_K;
+        half = step / 2.0;
+        const double px0 = act ? gxy[2 * e] : 0.0, py0 = act ? gxy[2 * e + 1] : 0.0;
+        posx = c_sx + (carryx + px0);
+        posy = c_sy + (carryy + py0);
+      };
+      geometry(lane);
+      if (act && m == TOPAY_K) {
+        c_pcs[2 * N + 2 * (i + 1)] = posx;
+        c_pcs[2 * N + 2 * (i + 1) + 1] = posy;
+      }
+      if (!skip_body) {   // (wave-uniform: no call of the non-inlined manipulator block under a partial EXEC mask, see sample_mani)
+        ManiOut mo;
+        mo.gx = mo.gy = mo.gth = mo.cost = mo.gdT = 0.0;
+        if (STAGE == 2) {
+          mo = sample_mani<OCC>(cL, rows, i, j, e, act, step, half, posx, posy, mp, c_mstash, pbuf + lane);
+          lane = fresh_lane_id(lane);
+          tid = wave * 64 + lane;
+          geometry(lane);
+        }
+        double gB[12], gdTs, gpx, gpy, cst;
+        bool jva;
+        sample_rest<STAGE>(P, cL, rows, i, j, step, half, posx, posy, mp, wM, wA, wD, mo, pbuf + lane, gB, gdTs, gpx, gpy, jva, cst);
+        if (act) {
+          cst_out = cst;
+          gxy[2 * e] = gpx;
+          gxy[2 * e + 1] = gpy;
+          glb_dp sb = c_sbuf + e;
+          const int ss = c_sbs;
+#pragma unroll
+          for (int v = 0; v < 5; v++) sb[v * ss] = gB[v];
+          sb[5 * ss] = gdTs;
+          if (STAGE == 2) {
+#pragma unroll
+            for (int v = 0; v < 7; v++) sb[(6 + v) * ss] = gB[5 + v];
+            sb[13 * ss] = jva ? 1.0 : 0.0;
+          }
+        }
+      }
+    }
+    // the costs of this round's passes, added lane by lane in pass order; early rejection tested after every pass
+    // (one wave: the cost of the round's only pass is this lane's own)
+    lds_dp cs = csr + (k & 1) * (NW * 64);
+    if (NW > 1) {
+      cs[wave * 64 + lane] = cst_out;
+      wg_barrier<NW>();
+    }
+#pragma unroll
+    for (int q = 0; q < NW; q++) {
+      const int p2 = k * NW + q;
+      if (p2 < npass) {
+        cost_pen += NW > 1 ? cs[q * 64 + lane] : cst_out;
+        if (STAGE == 2 && g_early_ok && !skip_body && p2 + 1 < npass) {
+          const double partial = jerk_cost + wave_sum(cost_pen) + time_cost;
+          if (partial > g_skip_thr && partial <= 1.79769313486231570e308) {
+            skip_body = true;
+            f_skip = partial;
+          }
+        }
+      }
+    }
+  }
+  while (pc < npass) {
+    carryx = uniform_f64(carryx + ptot[2 * pc]);
+    carryy = uniform_f64(carryy + ptot[2 * pc + 1]);
+    pc++;
+  }
+  if (NW == 1) lds_sync();   // (several waves: the barrier of the last round's cost exchange) piece-end positions are read below
+  STAMP(C, 4);  // sweep 1
+
+  // ---- per-piece terms between the sweeps
+  double cost_piece = 0.0;
+  double chain0x = 0.0, chain0y = 0.0;
+  double mt_add_all = 0.0, mt_add_own = 0.0;
+  if (STAGE == 1) {
+    if (tid < N) {
+      const double ex = c_pcs[2 * N + 2 * (tid + 1)] - c_init_xy[2 * tid];
+      const double ey = c_pcs[2 * N + 2 * (tid + 1) + 1] - c_init_xy[2 * tid + 1];
+      cost_piece = P.s1_path_pos_weight * (ex * ex + ey * ey);
+      c_pcs[2 * tid] = P.s1_path_pos_weight * 2.0 * ex;
+      c_pcs[2 * tid + 1] = P.s1_path_pos_weight * 2.0 * ey;
+    }
+    wg_barrier<NW>();
+  } else {
+    const double Tm = tid < N ? c_Tp[tid] : 0.0;
+    const double avg = wg_sum<NW>(c_red, rp, wave, Tm) / N;
+    double add_all = 0.0, add_own = 0.0;
+    if (tid < N) {
+      const double wMT = P.s2_mean_time_weight;
+      if (Tm < avg * 0.5) {
+        const double dd = Tm - avg * 0.5;
+        cost_piece += wMT * dd * dd;
+        add_all += wMT * 2.0 * dd * (-0.5 / N);
+        add_own += wMT * 2.0 * dd;
+      }
+      if (Tm > avg * 2.0) {
+        const double dd = Tm - avg * 2.0;
+        cost_piece += wMT * dd * dd;
+        add_all += wMT * 2.0 * dd * (-2.0 / N);
+        add_own += wMT * 2.0 * dd;
+      }
+    }
+    mt_add_all = add_all;
+    mt_add_own = add_own;
+    C.fxe0 = (c_sx + carryx) - c_ex;
+    C.fxe1 = (c_sy + carryy) - c_ey;
+    const double ea = C.fxe0 + c_lam0 / c_rho0, eb = C.fxe1 + c_lam1 / c_rho1;
+    if (tid == 0) cost_piece += 0.5 * (c_rho0 * (ea * ea) + c_rho1 * (eb * eb));
+    chain0x = c_rho0 * ea;
+    chain0y = c_rho1 * eb;
+  }
+  // (the lanes of wave 0 carry the per-lane sample costs: every wave holds the same cost_pen)
+  double penalty_cost = wg_sum<NW>(c_red, rp, wave, (wave == 0 ? cost_pen : 0.0) + cost_piece);
+  const bool bad = (STAGE == 2) && !(fabs(penalty_cost) <= 1.79769313486231570e308);
+  const double f_total = jerk_cost + (bad ? 1.0e+22 : penalty_cost) + time_cost;
+
+  STAMP(C, 5);  // per-piece terms, cost
+  if (skip_body) return f_skip;
+  if (!ugate.needs(f_total)) return f_total;
+
+  // =========================== gradient phase ===========================
+  // ---- row bookkeeping: thread tid owns the system rows tid + NT r (formed here, after the sample passes)
+  int rrow[RMAX], rpiece[RMAX], rk[RMAX];
+  bool ract[RMAX];
+#pragma unroll
+  for (int r = 0; r < RMAX; r++) {
+    rrow[r] = tid + NT * r;
+    ract[r] = rrow[r] < rows;
+    rpiece[r] = rrow[r] / 6;
+    rk[r] = rrow[r] - 6 * rpiece[r];
+  }
+  double jerk_gdT = 0.0;
+  if (tid < N) {
+    double unused_;
+    jerk_terms(tid, unused_, jerk_gdT);
+  }
+  // dJ/dC accumulator of this thread's rows (registers): theta, s, seven joints
+  double a0[RMAX], a1[RMAX], aq[RMAX][7];
+  double rbh[RMAX][3];   // hs-powers of each row (basis_k(k, hs))
+#pragma unroll
+  for (int r = 0; r < RMAX; r++) {
+    a0[r] = 0.0;
+    a1[r] = 0.0;
+#pragma unroll
+    for (int q = 0; q < 7; q++) aq[r][q] = 0.0;
+    rbh[r][0] = rbh[r][1] = rbh[r][2] = 0.0;
+    if (ract[r]) {
+      const double hs = c_Tp[rpiece[r]] / TOPAY_K / 2.0;
+      basis_k(rk[r], hs, rbh[r][0], rbh[r][1], rbh[r][2]);
+    }
+  }
+  constexpr int NV = (STAGE == 2) ? 13 : 6;
+  if constexpr (NW == 1) {
+    // One wave: a pass's gradient rows reach the row lanes in two halves through the 7-row pass buffer -- theta / s rows
+    // and dJ/dT first, then the seven joint rows.  Every accumulator still sees its samples in ascending order, so the sums
+    // are the sums of the 13-row round; the rare joint velocity / acceleration rows are broadcast from the flagged lanes'
+    // registers (no LDS), sample by sample in ascending order.
+    for (int pass = 0; pass < npass; pass++) {
+      const int e = pass * 64 + lane;
+      const bool act = e < NE;
+      const int i = act ? e / TOPAY_EP : N - 1;
+      const int m = act ? e - TOPAY_EP * i : 0;
+      const int j = 2 * m;
+      const double step = c_Tp[i] / TOPAY_K, half = step / 2.0;
+      bool jva = false;
+      double rawq[7];
+      {
+        glb_cdp sb = c_sbuf + (act ? e : NE - 1);
+        const int ss = c_sbs;
+        double raw[14];
+#pragma unroll
+        for (int v = 0; v < ((STAGE == 2) ? 14 : 6); v++) raw[v] = sb[v * ss];
+#pragma unroll
+        for (int v = 0; v < 6; v++) pbuf[v * 64 + lane] = act ? raw[v] : 0.0;
+#pragma unroll
+        for (int v = 0; v < 7; v++) rawq[v] = (STAGE == 2 && act) ? raw[6 + v] : 0.0;
+        if (STAGE == 2) jva = act && raw[13] != 0.0;
+      }
+      lds_sync();
+      // half 1: theta / s rows (orders 0-2 / 1-2) and dJ/dT
+#pragma unroll
+      for (int r = 0; r < RMAX; r++) {
+        if (ract[r]) {
+          const int pi = rpiece[r];
+          const double h0 = rbh[r][0], h1 = rbh[r][1], h2 = rbh[r][2];
+          const int k0 = rk[r], k1 = rk[r] >= 1 ? rk[r] - 1 : 0, k2 = rk[r] >= 2 ? rk[r] - 2 : 0;
+          const int e_lo = max(TOPAY_EP * pi, pass * 64), e_hi = min(min(TOPAY_EP * pi + TOPAY_EP, pass * 64 + 64), NE);
+          double gt = 0.0;
+          constexpr int CH = 3;
+          for (int c0 = e_lo; c0 < e_hi; c0 += CH) {
+            double pb[CH][6], t0[CH], t1[CH], t2[CH];
+#pragma unroll
+            for (int u = 0; u < CH; u++) {
+              const int ee = (c0 + u < e_hi) ? c0 + u : e_hi - 1;
+              const int l = ee - pass * 64, mm = ee - TOPAY_EP * pi;
+              lds_cdp pj = c_pw + 12 * mm;
+              t0[u] = pj[k0]; t1[u] = pj[k1]; t2[u] = pj[k2];
+#pragma unroll
+              for (int v = 0; v < 6; v++) pb[u][v] = pbuf[v * 64 + l];
+            }
+#pragma unroll
+            for (int u = 0; u < CH; u++) {
+              const bool ok = c0 + u < e_hi;
+              const double b0 = h0 * t0[u], b1 = h1 * t1[u], b2 = h2 * t2[u];
+              const double i0 = fma(b2, pb[u][2], fma(b1, pb[u][1], b0 * pb[u][0]));
+              const double i1 = fma(b2, pb[u][4], b1 * pb[u][3]);
+              a0[r] += ok ? i0 : 0.0;
+              a1[r] += ok ? i1 : 0.0;
+              gt += ok ? pb[u][5] : 0.0;
+            }
+          }
+          if (e_lo < e_hi && rk[r] == 0) c_gdT[pi] += gt;
+        }
+      }
+      if (STAGE == 2) {
+        lds_sync();
+#pragma unroll
+        for (int v = 0; v < 7; v++) pbuf[v * 64 + lane] = rawq[v];
+        lds_sync();
+        // half 2: the order-0 joint rows
+#pragma unroll
+        for (int r = 0; r < RMAX; r++) {
+          if (ract[r]) {
+            const int pi = rpiece[r];
+            const double h0 = rbh[r][0];
+            const int k0 = rk[r];
+            const int e_lo = max(TOPAY_EP * pi, pass * 64), e_hi = min(min(TOPAY_EP * pi + TOPAY_EP, pass * 64 + 64), NE);
+            constexpr int CH = 3;
+            for (int c0 = e_lo; c0 < e_hi; c0 += CH) {
+              double pb[CH][7], t0[CH];
+#pragma unroll
+              for (int u = 0; u < CH; u++) {
+                const int ee = (c0 + u < e_hi) ? c0 + u : e_hi - 1;
+                const int l = ee - pass * 64, mm = ee - TOPAY_EP * pi;
+                t0[u] = c_pw[12 * mm + k0];
+#pragma unroll
+                for (int v = 0; v < 7; v++) pb[u][v] = pbuf[v * 64 + l];
+              }
+#pragma unroll
+              for (int u = 0; u < CH; u++) {
+                const bool ok = c0 + u < e_hi;
+                const double b0 = h0 * t0[u];
+#pragma unroll
+                for (int qq = 0; qq < 7; qq++) {
+                  const double nq = fma(b0, pb[u][qq], aq[r][qq]);
+                  aq[r][qq] = ok ? nq : aq[r][qq];
+                }
+              }
+            }
+          }
+        }
+        // rare: joint velocity / acceleration gradBeta rows 1 and 2 (moma_traj_opt.cpp:1689, 1703) of the flagged samples
+        unsigned long long todo = __ballot(jva);
+        if (todo != 0) {
+          double g1[7], g2[7];
+#pragma unroll
+          for (int q = 0; q < 7; q++) { g1[q] = 0.0; g2[q] = 0.0; }
+          if (jva) {
+            Basis B;
+            make_basis(j * half, B);
+            const double omg = (j == 0 || j == 2 * TOPAY_K) ? 0.5 : 1.0;
+#pragma unroll
+            for (int q = 0; q < 7; q++) {
+              double p0, p1, p2;
+              poly3(cL, rows, i, 2 + q, B, p0, p1, p2);
+              const double vDq = p1 * p1 - P.joint_vel_limit2[q];
+              const double vD2q = p2 * p2 - P.joint_acc_limit2[q];
+              if (vDq > 0) {
+                double pe, pd;
+                smoothL1(P, vDq, P.relu_mu, pe, pd);
+                g1[q] = omg * step * P.s2_mani_vel_weight * pd * 2.0 * p1;
+              }
+              if (vD2q > 0) {
+                double pe, pd;
+                smoothL1(P, vD2q, P.relu_mu, pe, pd);
+                g2[q] = omg * step * P.s2_mani_acc_weight * pd * 2.0 * p2;
+              }
+            }
+          }
+          while (todo) {
+            const int src = __ffsll(todo) - 1;
+            todo &= todo - 1;
+            const int se = pass * 64 + src;
+            const int spi = se / TOPAY_EP, smm = se - TOPAY_EP * spi;
+            double b1v[7], b2v[7];
+#pragma unroll
+            for (int q = 0; q < 7; q++) { b1v[q] = readlane_f64(g1[q], src); b2v[q] = readlane_f64(g2[q], src); }
+#pragma unroll
+            for (int r = 0; r < RMAX; r++) {
+              if (ract[r] && rpiece[r] == spi) {
+                const int k1 = rk[r] >= 1 ? rk[r] - 1 : 0, k2 = rk[r] >= 2 ? rk[r] - 2 : 0;
+                const double b1 = rbh[r][1] * c_pw[12 * smm + k1], b2 = rbh[r][2] * c_pw[12 * smm + k2];
+#pragma unroll
+                for (int q = 0; q < 7; q++) {
+                  double a = aq[r][q];
+                  a = fma(b1, b1v[q], a);
+                  a = fma(b2, b2v[q], a);
+                  aq[r][q] = a;
+                }
+              }
+            }
+          }
+        }
+      }
+      lds_sync();   // end of the pass: the pass buffer is free again
+    }
+  } else {
+  for (int k = 0; k < nround; k++) {
+    const int pass = k * NW + wave;
+    const int e = pass * 64 + lane;
+    const bool act = pass < npass && e < NE;
+    const int i = act ? e / TOPAY_EP : N - 1;
+    const int m = act ? e - TOPAY_EP * i : 0;
+    const int j = 2 * m;
+    const double step = c_Tp[i] / TOPAY_K, half = step / 2.0;
+    bool jva = false;
+    if (pass < npass) {
+      glb_cdp sb = c_sbuf + (act ? e : NE - 1);
+      const int ss = c_sbs;
+      double raw[14];
+#pragma unroll
+      for (int v = 0; v < ((STAGE == 2) ? 14 : 6); v++) raw[v] = sb[v * ss];
+#pragma unroll
+      for (int v = 0; v < 6; v++) pbuf[v * 64 + lane] = act ? raw[v] : 0.0;
+      if (STAGE == 2) {
+#pragma unroll
+        for (int v = 0; v < 7; v++) pbuf[(6 + v) * 64 + lane] = act ? raw[6 + v] : 0.0;
+        jva = act && raw[13] != 0.0;
+      }
+    }
+    if (STAGE == 2) {
+      const unsigned long long mk = __ballot(jva);
+      if (lane == 0) jmask[wave] = mk;
+    }
+    wg_barrier<NW>();
+    // row accumulation of one pass of the round into the accumulators of row slot r
+    auto accumulate = [&](int r, int q) __attribute__((always_inline)) {
+      const int p2 = k * NW + q;
+      const int pi = rpiece[r];
+      const double h0 = rbh[r][0], h1 = rbh[r][1], h2 = rbh[r][2];
+      const int k0 = rk[r], k1 = rk[r] >= 1 ? rk[r] - 1 : 0, k2 = rk[r] >= 2 ? rk[r] - 2 : 0;
+      const int e_lo = max(TOPAY_EP * pi, p2 * 64), e_hi = min(min(TOPAY_EP * pi + TOPAY_EP, p2 * 64 + 64), NE);
+      if (e_lo >= e_hi) return;
+      lds_cdp pq = pball + q * (PBR * 64);
+      double gt = 0.0;
+      constexpr int CH = 3;
+      for (int c0 = e_lo; c0 < e_hi; c0 += CH) {
+        double pb[CH][NV], t0[CH], t1[CH], t2[CH];
+#pragma unroll
+        for (int u = 0; u < CH; u++) {
+          const int ee = (c0 + u < e_hi) ? c0 + u : e_hi - 1;
+          const int l = ee - p2 * 64, mm = ee - TOPAY_EP * pi;
+          lds_cdp pj = c_pw + 12 * mm;
+          t0[u] = pj[k0]; t1[u] = pj[k1]; t2[u] = pj[k2];
+#pragma unroll
+          for (int v = 0; v < NV; v++) pb[u][v] = pq[v * 64 + l];
+        }
+#pragma unroll
+        for (int u = 0; u < CH; u++) {
+          const bool ok = c0 + u < e_hi;
+          const double b0 = h0 * t0[u], b1 = h1 * t1[u], b2 = h2 * t2[u];
+          const double i0 = fma(b2, pb[u][2], fma(b1, pb[u][1], b0 * pb[u][0]));
+          const double i1 = fma(b2, pb[u][4], b1 * pb[u][3]);
+          a0[r] += ok ? i0 : 0.0;
+          a1[r] += ok ? i1 : 0.0;
+          gt += ok ? pb[u][5] : 0.0;
+          if (STAGE == 2) {
+#pragma unroll
+            for (int qq = 0; qq < 7; qq++) {
+              const double nq = fma(b0, pb[u][6 + qq], aq[r][qq]);
+              aq[r][qq] = ok ? nq : aq[r][qq];
+            }
+          }
+        }
+      }
+      if (rk[r] == 0) c_gdT[pi] += gt;
+    };
+    unsigned long long any = 0;
+    if (STAGE == 2) {
+#pragma unroll
+      for (int q = 0; q < NW; q++) any |= jmask[q];
+    }
+    if (any == 0) {
+      // the samples of the row's piece in ascending order, pass by pass (the one-wave order)
+#pragma unroll
+      for (int r = 0; r < RMAX; r++) {
+        if (ract[r]) {
+          for (int q = 0; q < NW; q++) accumulate(r, q);
+        }
+      }
+    } else {
+      // rare: joint velocity / acceleration gradBeta rows 1 and 2 (moma_traj_opt.cpp:1689, 1703) of flagged samples.  Within a
+      // pass the order-0 rows of all its samples first, then the rare rows of its flagged samples, pass by pass -- the
+      // one-wave order exactly, also for a piece whose samples straddle two passes of this round.
+      for (int q = 0; q < NW; q++) {
+#pragma unroll
+        for (int r = 0; r < RMAX; r++) {
+          if (ract[r]) accumulate(r, q);
+        }
+        unsigned long long todo = jmask[q];   // (the same for every thread: the barriers below are uniform)
+        if (todo == 0) continue;
+        wg_barrier<NW>();   // every row thread is done with this pass's buffer
+        if (wave == q && jva) {
+          Basis B;
+          make_basis(j * half, B);
+          const double omg = (j == 0 || j == 2 * TOPAY_K) ? 0.5 : 1.0;
+#pragma unroll
+          for (int qq = 0; qq < 7; qq++) {
+            double p0, p1, p2, g1 = 0.0, g2 = 0.0;
+            poly3(cL, rows, i, 2 + qq, B, p0, p1, p2);
+            const double vDq = p1 * p1 - P.joint_vel_limit2[qq];
+            const double vD2q = p2 * p2 - P.joint_acc_limit2[qq];
+            if (vDq > 0) {
+              double pe, pd;
+              smoothL1(P, vDq, P.relu_mu, pe, pd);
+              g1 = omg * step * P.s2_mani_vel_weight * pd * 2.0 * p1;
+            }
+            if (vD2q > 0) {
+              double pe, pd;
+              smoothL1(P, vD2q, P.relu_mu, pe, pd);
+              g2 = omg * step * P.s2_mani_acc_weight * pd * 2.0 * p2;
+            }
+            pbuf[qq * 64 + lane] = g1;
+            pbuf[(7 + qq) * 64 + lane] = g2;
+          }
+        }
+        wg_barrier<NW>();
+        lds_cdp pq = pball + q * (PBR * 64);
+        while (todo) {
+          const int src = __ffsll(todo) - 1;
+          todo &= todo - 1;
+          const int se = (k * NW + q) * 64 + src;
+          const int spi = se / TOPAY_EP, smm = se - TOPAY_EP * spi;
+          double b1v[7], b2v[7];
+#pragma unroll
+          for (int qq = 0; qq < 7; qq++) { b1v[qq] = pq[qq * 64 + src]; b2v[qq] = pq[(7 + qq) * 64 + src]; }
+#pragma unroll
+          for (int r = 0; r < RMAX; r++) {
+            if (ract[r] && rpiece[r] == spi) {
+              const int k1 = rk[r] >= 1 ? rk[r] - 1 : 0, k2 = rk[r] >= 2 ? rk[r] - 2 : 0;
+              const double b1 = rbh[r][1] * c_pw[12 * smm + k1], b2 = rbh[r][2] * c_pw[12 * smm + k2];
+#pragma unroll
+              for (int qq = 0; qq < 7; qq++) {
+                double a = aq[r][qq];
+                a = fma(b1, b1v[qq], a);
+                a = fma(b2, b2v[qq], a);
+                aq[r][qq] = a;
+              }
+            }
+          }
+        }
+      }
+    }
+    wg_barrier<NW>();   // end of the round: the pass buffers and the masks are free again
+  }
+
+  }
+  if (STAGE == 2) {
+    const double all = wg_sum<NW>(c_red, rp, wave, mt_add_all);
+    if (tid < N) c_gdT[tid] += all + mt_add_own;
+  }
+  wg_barrier<NW>();
+  // =========================== sweep 2: backward, XY-gradient chain ===========================
+  if (!bad) {
+    if (STAGE == 2) {   // phase A: pass totals of the positional gradients in the suffix scan's own order
+      for (int k = 0; k < nround; k++) {
+        const int pass = k * NW + wave;
+        if (pass < npass) {
+          const int e = pass * 64 + lane;
+          const bool act = e < NE;
+          const double gx = act ? gxy[2 * e] : 0.0, gy = act ? gxy[2 * e + 1] : 0.0;
+          const double sx_ = wave_incl_rscan(gx, lane), sy_ = wave_incl_rscan(gy, lane);
+          if (lane == 0) {
+            ptot[2 * pass] = sx_;
+            ptot[2 * pass + 1] = sy_;
+          }
+        }
+      }
+      wg_barrier<NW>();
+    }
+    double rcx = chain0x, rcy = chain0y;   // chain carried across passes: the totals of the passes after `pc - 1`, added in descending order
+    pc = npass;
+    for (int k = nround - 1; k >= 0; k--) {
+      const int pass = k * NW + wave;
+      double v0 = 0, v1 = 0, v2 = 0, v3 = 0, vT = 0;
+      if (pass < npass) {
+        const int e = pass * 64 + lane;
+        const bool act = e < NE;
+        const int i = act ? e / TOPAY_EP : N - 1;
+        const int m = act ? e - TOPAY_EP * i : 0;
+        const int j = 2 * m;
+        double chx_in, chy_in, chx_ex, chy_ex;
+        if (STAGE == 2) {
+          while (pc > pass + 1) {
+            pc--;
+            rcx += ptot[2 * pc];
+            rcy += ptot[2 * pc + 1];
+          }
+          const double gx = act ? gxy[2 * e] : 0.0, gy = act ? gxy[2 * e + 1] : 0.0;
+          const double sx_ = wave_incl_rscan(gx, lane), sy_ = wave_incl_rscan(gy, lane);
+          chx_in = sx_ + rcx; chy_in = sy_ + rcy;
+          chx_ex = chx_in - gx;   chy_ex = chy_in - gy;
+        } else {
+          double sx_ = 0.0, sy_ = 0.0;
+          for (int ii = i + 1; ii < N; ii++) { sx_ += c_pcs[2 * ii]; sy_ += c_pcs[2 * ii + 1]; }
+          chx_in = chx_ex = sx_;
+          chy_in = chy_ex = sy_;
+        }
+        if (act) {
+          const double T1 = c_Tp[i];
+          const double step = T1 / TOPAY_K, half = step / 2.0, coeff = step / 6.0;
+          const int int_6K = TOPAY_K * 6;
+#pragma unroll
+          for (int odd = 0; odd < 2; odd++) {
+            if (odd == 1 && m == TOPAY_K) break;
+            const int jj = j + odd;
+            Basis B;
+            make_basis(jj * half, B);
+            double th0, th1, th2, s0, sd1, sd2;
+            poly3(cL, rows, i, 0, B, th0, th1, th2);
+            poly3(cL, rows, i, 1, B, s0, sd1, sd2);
+            double sn, cn;
+            det_sincos(th0, &sn, &cn);
+            const double alpha = 1.0 / (2 * TOPAY_K) * jj;
+            const double W = odd ? 4.0 : ((jj == 0 || jj == 2 * TOPAY_K) ? 1.0 : 2.0);
+            const double Cx = (odd ? chx_ex : chx_in) * W, Cy = (odd ? chy_ex : chy_in) * W;
+            const double aTh = (-sd1 * sn * coeff) * Cx + (sd1 * cn * coeff) * Cy;
+            const double aS = (cn * coeff) * Cx + (sn * coeff) * Cy;
+            const double gTx = (sd2 * cn - sd1 * th1 * sn) * alpha * coeff + sd1 * cn / int_6K;
+            const double gTy = (sd2 * sn + sd1 * th1 * cn) * alpha * coeff + sd1 * sn / int_6K;
+            vT += gTx * Cx + gTy * Cy;
+            if (odd) { v2 = aTh; v3 = aS; } else { v0 = aTh; v1 = aS; }
+          }
+        }
+      }
+      pbuf[0 * 64 + lane] = v0; pbuf[1 * 64 + lane] = v1; pbuf[2 * 64 + lane] = v2; pbuf[3 * 64 + lane] = v3;
+      pbuf[4 * 64 + lane] = vT;
+      wg_barrier<NW>();
+#pragma unroll
+      for (int r = 0; r < RMAX; r++) {
+        if (ract[r]) {
+          const int pi = rpiece[r];
+          const double h0 = rbh[r][0], h1 = rbh[r][1];
+          const int k1 = rk[r] >= 1 ? rk[r] - 1 : 0;
+          for (int q = NW - 1; q >= 0; q--) {   // passes in descending order, samples inside a pass ascending
+            const int p2 = k * NW + q;
+            const int e_lo = max(TOPAY_EP * pi, p2 * 64), e_hi = min(min(TOPAY_EP * pi + TOPAY_EP, p2 * 64 + 64), NE);
+            if (e_lo >= e_hi) continue;
+            lds_cdp pq = pball + q * (PBR * 64);
+            double gt = 0.0;
+            constexpr int CH = 3;
+            for (int c0 = e_lo; c0 < e_hi; c0 += CH) {
+              double pb[CH][5], tb[CH][4];
+#pragma unroll
+              for (int u = 0; u < CH; u++) {
+                const int ee = (c0 + u < e_hi) ? c0 + u : e_hi - 1;
+                const int l = ee - p2 * 64, mm = ee - TOPAY_EP * pi;
+                lds_cdp pj = c_pw + 12 * mm;
+                tb[u][0] = pj[rk[r]]; tb[u][1] = pj[k1]; tb[u][2] = pj[6 + rk[r]]; tb[u][3] = pj[6 + k1];
+#pragma unroll
+                for (int v = 0; v < 5; v++) pb[u][v] = pq[v * 64 + l];
+              }
+#pragma unroll
+              for (int u = 0; u < CH; u++) {
+                const bool ok = c0 + u < e_hi;
+                const double b0 = h0 * tb[u][0], b1 = h1 * tb[u][1];
+                const double o0 = h0 * tb[u][2], o1 = h1 * tb[u][3];
+                const double i0 = fma(o0, pb[u][2], b0 * pb[u][0]);
+                const double i1 = fma(o1, pb[u][3], b1 * pb[u][1]);
+                a0[r] += ok ? i0 : 0.0;
+                a1[r] += ok ? i1 : 0.0;
+                gt += ok ? pb[u][4] : 0.0;
+              }
+            }
+            if (rk[r] == 0) c_gdT[pi] += gt;
+          }
+        }
+      }
+      wg_barrier<NW>();
+    }
+  } else {
+    penalty_cost = 1.0e+22;
+#pragma unroll
+    for (int r = 0; r < RMAX; r++) {
+      a0[r] = 0.0;
+      a1[r] = 0.0;
+#pragma unroll
+      for (int q = 0; q < 7; q++) aq[r][q] = 0.0;
+    }
+    if (tid < N) c_gdT[tid] = 0.0;
+    wg_barrier<NW>();
+  }
+
+  STAMP(C, 6);  // gradient rows to the row threads, sweep 2
+  // ---- total dJ/dC = jerk part (minco.hpp:951-976) + penalty part; adjoint solve (banded_system.hpp:123-145)
+  double tot[RMAX][9];
+#pragma unroll
+  for (int r = 0; r < RMAX; r++) {
+    if (ract[r]) {
+      const int pi = rpiece[r], kk = rk[r];
+      const double T1 = c_Tp[pi], T2 = c_Tp[N + pi], T3 = c_Tp[2 * N + pi], T4 = c_Tp[3 * N + pi], T5 = c_Tp[4 * N + pi];
+#pragma unroll
+      for (int d = 0; d < 9; d++) {
+        double jg = 0.0;
+        if (kk >= 3) {
+          const double c3 = cL[d * rows + 6 * pi + 3], c4 = cL[d * rows + 6 * pi + 4], c5 = cL[d * rows + 6 * pi + 5];
+          const double e = P.energy_weights[d];
+          if (kk == 5) jg = 240.0 * c3 * e * T3 + 720.0 * c4 * e * T4 + 1440.0 * c5 * e * T5;
+          else if (kk == 4) jg = 144.0 * c3 * e * T2 + 384.0 * c4 * e * T3 + 720.0 * c5 * e * T4;
+          else jg = 72.0 * c3 * e * T1 + 144.0 * c4 * e * T2 + 240.0 * c5 * e * T3;
+        }
+        tot[r][d] = jg + (d == 0 ? a0[r] : (d == 1 ? a1[r] : aq[r][d >= 2 ? d - 2 : 0]));
+      }
+    }
+  }
+  // the adjoint solve takes the coefficients' LDS block: they go to the candidate's result block in HBM first (which
+  // is where a solve that ends here leaves them anyway); the dJ/dT correction below reads them back from there
+  for (int t = tid; t < 9 * rows; t += NT) c_coefg[t] = cL[t];
+  C.cl_in_lds = 0;
+  wg_global_barrier<NW>();
+  // (the LU factors stream from the candidate's LU block through the windows of band_sweep: nothing to reload)
+#pragma unroll
+  for (int r = 0; r < RMAX; r++) {
+    if (ract[r]) {
+#pragma unroll
+      for (int d = 0; d < 9; d++) c_adj[d * rows + rrow[r]] = tot[r][d];
+    }
+  }
+  wg_barrier<NW>();
+  if (wave == 0) {
+    const bool owner = lane < 9;
+    const lds_dp mine = c_adj + (owner ? lane : 8) * rows;
+    band_sweep<2>(mine, owner, (glb_cdp)c_lu, c_X, rows, lane);
+    band_sweep<3>(mine, owner, (glb_cdp)c_lu, c_X, rows, lane);
+  }
+  wg_barrier<NW>();
+  STAMP(C, 7);  // adjoint solve
+  // ---- dJ/dT correction  gdT(i) += sum(B1 .* adj rows 6i+3..6i+8) — minco.hpp:1016-1067
+#pragma unroll
+  for (int r = 0; r < RMAX; r++) {
+    if (ract[r]) {
+      const int row = rrow[r];
+      int pi, br;
+      bool use = true;
+      if (row >= rows - 3) { pi = N - 1; br = 10 + (row - (rows - 3)); }
+      else if (row < 3) { use = false; pi = 0; br = 0; }
+      else { pi = (row - 3) / 6; br = (row - 3) - 6 * pi; }
+      double part = 0.0;
+      if (use) {
+        const double T1 = c_Tp[pi], T2 = c_Tp[N + pi], T3 = c_Tp[2 * N + pi], T4 = c_Tp[3 * N + pi];
+#pragma unroll
+        for (int d = 0; d < 9; d++) {
+          glb_cdp cg = c_coefg + d * rows + 6 * pi;   // (the LDS block holds the adjoint now)
+          const double c1 = cg[1], c2 = cg[2], c3 = cg[3], c4 = cg[4], c5 = cg[5];
+          double b;
+          if (br == 0) b = -(24.0 * c4 + 120.0 * T1 * c5);
+          else if (br == 1) b = -120.0 * c5;
+          else if (br == 2 || br == 3 || br == 10) b = -(c1 + 2.0 * T1 * c2 + 3.0 * T2 * c3 + 4.0 * T3 * c4 + 5.0 * T4 * c5);
+          else if (br == 4 || br == 11) b = -(2.0 * c2 + 6.0 * T1 * c3 + 12.0 * T2 * c4 + 20.0 * T3 * c5);
+          else b = -(6.0 * c3 + 24.0 * T1 * c4 + 60.0 * T2 * c5);
+          part += b * c_adj[d * rows + row];
+        }
+      }
+      c_X[row] = part;   // (the windows of the sweeps are dead)
+    }
+  }
+  wg_barrier<NW>();
+  double gdT_tot = 0.0;
+  if (tid < N) {
+    const int i = tid;
+    double s = 0.0;
+    if (i < N - 1) { for (int r = 0; r < 6; r++) s += c_X[6 * i + 3 + r]; }
+    else { for (int r = 0; r < 3; r++) s += c_X[rows - 3 + r]; }
+    gdT_tot = jerk_gdT + c_gdT[i] + s;
+  }
+  // ---- chain rule to the decision variables — moma_traj_opt.cpp:936-948
+  glb_cdp Tau = c_x;
+  glb_cdp Vq = c_x + 3 * N - 1;
+  if (tid < N) c_g[tid] = (gdT_tot + wT) * dTdTau(Tau[tid]);
+  for (int t = tid; t < 9 * (N - 1); t += NT) {
+    const int i = t / 9, d = t - 9 * i;
+    const double gp = c_adj[d * rows + 6 * i + 5];
+    const int dq = d >= 2 ? d - 2 : 0;
+    if (d == 0) c_g[N + i] = gp;
+    else if (d == 1) c_g[2 * N - 1 + i] = gp;
+    else c_g[3 * N - 1 + 7 * i + dq] = gp * dQdVq(Vq[7 * i + dq], P.joint_pos_limit_max[dq]);
+  }
+  if (tid == 0) c_g[3 * N - 2] = c_adj[1 * rows + rows - 3];
+  wg_global_barrier<NW>();
+  STAMP(C, 8);  // dJ/dT correction, chain rule
+  return f_total;
 }
 
 }  // namespace topay

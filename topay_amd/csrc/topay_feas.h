@@ -13,7 +13,7 @@
 // report[kReportLen] = { |v|, |a|, |omega|, |domega| maxima, |q| max[7], |dq| max[7], |d2q| max[7], chassis min distance,
 // sphere min distance[12] }.
 #pragma once
-#include "topay_eval.h"
+#include "topay_mani.h"
 
 namespace topay {
 

@@ -312,7 +312,7 @@ static topay_status launch_classes(topay_ctx* c, bool persistent, Args... args) 
     const bool lat = !EVAL && ct[k].lat && (c->latency_mode == 2 || (c->latency_mode == 1 && c->B <= c->simd_slots));
     size_t lds = class_lds_bytes(ct[k], nm);
     if (lat) {
-      lds = (size_t)(lds_doubles_mw(nm, kLatWaves) + 8 + 40 + TOPAY_CMD_DOUBLES) * sizeof(double);
+      lds = (size_t)(eval_lds_total(nm, kLatWaves) + solve_tail_doubles(true)) * sizeof(double);
       grid = nk;   // a workgroup per candidate of the class
     }
     if (k == topay_ctx::NBUCKET - 2 && !c->cls[topay_ctx::NBUCKET - 1].empty() && c->bstream[k] == c->stream)

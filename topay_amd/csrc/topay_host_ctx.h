@@ -121,9 +121,7 @@ static const ClassDef kClassTable[TOPAY_NBUCKET] = {
 static const double kOcc2Gain = 1.7;
 static const int kLdsDoublesPerCU = 160 * 1024 / 8;
 static size_t class_lds_bytes(const ClassDef& cd, int nm) {
-  const int d = lds_doubles_mw(nm, cd.nw);
-  // + past-cost ring [8] + the solver state parked across an evaluation [40] (+ the command block of a helper-wave kernel)
-  return (size_t)(d + 8 + 40 + (cd.helpers() ? TOPAY_CMD_DOUBLES : 0)) * sizeof(double);
+  return (size_t)(eval_lds_total(nm, cd.nw) + solve_tail_doubles(cd.helpers())) * sizeof(double);
 }
 
 // Runs when the library is loaded: effective if the HIP runtime has not been initialised yet in this process
@@ -349,8 +347,8 @@ template <typename T> static hipError_t d2h(topay_ctx* c, T* dst, const T* src, 
 static topay_status validate_params(const topay_params_t* params) {
   if (params->int_K != TOPAY_K) { set_err("int_K must be 12 in this build"); return TOPAY_ERR_UNSUPPORTED; }
   if (!sphere_layout_ok(*params)) { set_err("unsupported collision sphere layout"); return TOPAY_ERR_UNSUPPORTED; }
-  if (params->s1_lbfgs.mem_size <= 0 || params->s2_lbfgs.mem_size <= 0 || params->s1_lbfgs.mem_size > 256 ||
-      params->s2_lbfgs.mem_size > 256 || params->s1_lbfgs.past > 8 ||
+  if (params->s1_lbfgs.mem_size <= 0 || params->s2_lbfgs.mem_size <= 0 || params->s1_lbfgs.mem_size > kLbfgsMaxMem ||
+      params->s2_lbfgs.mem_size > kLbfgsMaxMem || params->s1_lbfgs.past > 8 ||
       params->s2_lbfgs.past > 8 || params->s1_shot_path_past > 8 || params->s1_normal_past > 8) {
     set_err("lbfgs mem_size must be in 1..256 (the reference uses 256) and past <= 8");
     return TOPAY_ERR_INVALID_ARG;

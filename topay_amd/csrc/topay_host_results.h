@@ -329,7 +329,7 @@ topay_status topay_eval(topay_ctx* c, int stage, int i, const double* x, const d
 }
 
 // Test hook: the same evaluation by the kernel with `waves` wavefronts per trajectory (1, 2 or 4) instead of the
-// candidate's class default.  An evaluation is order-identical whatever the number of waves (topay_eval_mw.h): the
+// candidate's class default.  An evaluation is order-identical whatever the number of waves (topay_eval.h): the
 // results must agree bit for bit.
 topay_status topay_eval_waves(topay_ctx* c, int stage, int i, int waves, const double* x, const double* alm_lambda, const double* alm_rho,
                               double* f, double* g, double* final_xy_error) {

@@ -15,7 +15,7 @@
 // allocator takes as 256 VGPRs and no AGPRs.  The serial chains of a solve (banded LU, substitutions, hand-offs) overlap
 // with the second resident wave; the sample body and the two-loop recursion are bound by VALU issue and do not
 // (DESIGN.md section 9).  Every device function of the call graph has to fit, so the non-inlined ones (manipulator_block,
-// minco_generate_mw, eval_cost_grad_mw, the in-solve gate) are templated on OCC and the kernel's attribute reaches them per
+// minco_generate, eval_cost_grad, the in-solve gate) are templated on OCC and the kernel's attribute reaches them per
 // instantiation.
 using namespace topay;
 
@@ -47,10 +47,10 @@ __device__ __forceinline__ long long uniform_i64(long long v) {
   return (long long)(((unsigned long long)hi << 32) | lo);
 }
 
-// LDS of one trajectory's workgroup: the evaluation's blocks, then [8] past costs and [40] solver state parked across an evaluation
+// LDS of one trajectory's workgroup: the evaluation's blocks (eval_lds_plan), then the solver's tail (solve_tail_doubles)
 template <int NW>
 __host__ __device__ __forceinline__ int eval_lds_doubles(int Nmax_lds) {
-  return lds_doubles_mw(Nmax_lds, NW);
+  return eval_lds_total(Nmax_lds, NW);
 }
 
 // The candidate's blocks (DevBatch views) and the evaluation's LDS blocks into the context of its workgroup of NW waves
@@ -63,7 +63,7 @@ __device__ __forceinline__ void load_ctx(EvalCtx& C, const DevBatch& Bt, int b, 
   C.rows = 6 * C.N;
   C.n = 10 * C.N - 8;
   C.red = nullptr; C.adj = nullptr; C.cl_in_lds = 1;
-  carve_mw(C, TOPAY_LDS_PTR, Nmax_lds, NW);
+  eval_lds_carve(C, TOPAY_LDS_PTR, Nmax_lds, NW);
   fill_power_table(C.pw, C.lane);
   // (spelled out, like the FeasIO of solve_one: through head_of / tail_of this image's compiler gives the solve kernels another
   // schedule; worth another try with the next compiler)
@@ -129,8 +129,8 @@ __device__ __forceinline__ void eval_body(const DevBatch& Bt, const DevMap* maps
     gate.always = !cost_only; gate.has_early = false; gate.finit = 0.0; gate.thr = -1.0e300; gate.early = 0.0;
     gate.early_ok = false; gate.skip_thr = 0.0;
     __syncthreads();
-    if (stage == 1) f = eval_cost_grad_mw<1, RMAX, NW, OCC>(C, mp, gate);
-    else f = eval_cost_grad_mw<2, RMAX, NW, OCC>(C, mp, gate);
+    if (stage == 1) f = eval_cost_grad<1, RMAX, NW, OCC>(C, mp, gate);
+    else f = eval_cost_grad<2, RMAX, NW, OCC>(C, mp, gate);
   }
   if (C.tid == 0) {
     Bt.fout[b] = f;
@@ -182,7 +182,7 @@ __device__ __forceinline__ void solve_one(const DevBatch& Bt, const DevMap* maps
   EvalCtx C;
   load_ctx<NWE>(C, Bt, b, Nmax_lds);
   const TOPAY_GLB DevMap* mp = (const TOPAY_GLB DevMap*)(maps + __builtin_amdgcn_readfirstlane(Bt.map_id[b]));
-  lds_dp pf = TOPAY_LDS_PTR + eval_lds_doubles<NWE>(Nmax_lds);  // [8] past costs, then [40] solver state parked across an evaluation (+ the command block of the helper-wave kernels)
+  lds_dp pf = TOPAY_LDS_PTR + eval_lds_doubles<NWE>(Nmax_lds);  // the solver's tail: past costs, parked state (+ the command block of the helper-wave kernels)
   const long long no = uniform_i64(Bt.noff[b]);
   const int n = C.n;
   SolveIO S;
@@ -215,7 +215,7 @@ __device__ __forceinline__ void solve_one(const DevBatch& Bt, const DevMap* maps
     C.g = S.g;
     __syncthreads();   // x0 is in place for wave 0
     if (C.wave == 0) solve_trajectory<RMAX, OCC, NWE, RMAX_E>(C, mp, S, Bt.s1_past[b], pf, success, cost, interrupted);
-    else eval_helper_loop<RMAX_E, NWE, OCC>(C, mp, pf + 48);
+    else eval_helper_loop<RMAX_E, NWE, OCC>(C, mp, pf + kSolvePastDoubles + kSolveParkDoubles);
   } else {
     solve_trajectory<RMAX, OCC>(C, mp, S, Bt.s1_past[b], pf, success, cost, interrupted);
   }

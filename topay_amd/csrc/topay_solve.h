@@ -10,14 +10,11 @@
 // dot products are wave reductions; the whole solve is one launch with a single evaluation call site.
 #pragma once
 #include "topay_eval.h"
-#include "topay_eval_mw.h"
 
-#ifndef TOPAY_PF_ELEMS
+// Depth of the history prefetch ring of the two-loop recursion: TOPAY_PF_ELEMS / EPL pairs in flight, at most TOPAY_PF_MAX
+// (docs/EXPERIMENTS.md, round 5)
 #define TOPAY_PF_ELEMS 24
-#endif
-#ifndef TOPAY_PF_MAX
 #define TOPAY_PF_MAX 12
-#endif
 
 namespace topay {
 
@@ -61,9 +58,7 @@ __device__ __forceinline__ bool vec_in(int tid, int t, int n) { return 2 * (64 *
 // and pushes reused lines (scratch, parked rows, LU factors) out of L2.  Measured with nt = 1 (round 5, docs/EXPERIMENTS.md):
 // HBM-side writes - 20 %, reads + 6 %, strictly serial step + 4 % (the second loop re-reads the oldest pairs of the first
 // right away): off.
-#ifndef TOPAY_HIST_AUX
 #define TOPAY_HIST_AUX 0
-#endif
 template <bool STREAM = false>
 __device__ __forceinline__ dpair row_pair_or_zero(glb_cdp row, int n, int i) {
 #ifndef TOPAY_CPU_EMU
@@ -115,12 +110,22 @@ __device__ __forceinline__ double vec_dot_part(glb_cdp a, glb_cdp b, int n, int 
 // Helper waves (the kernels of the long classes and for a handful of candidates, topay_kernels.h: k_long*, k_lat*).  With
 // NWE > 1 the workgroup has NWE waves but the solver runs on wave 0 alone -- its vectors, reductions and two-loop recursion are those of the one-wave
 // kernels, so the bits of a solve are the one-wave bits -- and the other waves only join the evaluations (which are
-// order-identical for any number of waves, topay_eval_mw.h): wave 0 posts the evaluation's inputs in a command block in
+// order-identical for any number of waves, topay_eval.h): wave 0 posts the evaluation's inputs in a command block in
 // LDS, every wave meets at a workgroup barrier and evaluates.  What that shortens is the sample passes of the two sweeps (a
 // 10-piece candidate has three; four waves run them side by side); the solver's serial chains stay.
 //   command block, 16 doubles: finit, thr, early, skip_thr, lam0, lam1, rho0, rho1 | ints: op (1 evaluate, 0 leave), stage,
 //   gate.always, gate.has_early, gate.early_ok
 #define TOPAY_CMD_DOUBLES 16
+// The solver's tail of a workgroup's LDS, behind the evaluation's blocks (eval_lds_total): the costs of the last `past`
+// iterations (past <= 8), the solver's state parked across an evaluation (10 doubles, 22 ints, 14 pointers), and in a
+// helper-wave kernel the command block.
+constexpr int kSolvePastDoubles = 8;
+constexpr int kSolveParkDoubles = 40;
+__host__ __device__ constexpr int solve_tail_doubles(bool helpers) {
+  return kSolvePastDoubles + kSolveParkDoubles + (helpers ? TOPAY_CMD_DOUBLES : 0);
+}
+// (between two evaluations the solver's alpha ring, one double per history pair, borrows EvalCtx::X: smallest at one piece)
+static_assert(kLbfgsMaxMem <= eval_borrow_doubles(1, 1) && kLbfgsMaxMem <= eval_borrow_doubles(1, 4), "the alpha ring fits behind the coefficients");
 template <int RMAX_E, int NWE, int OCC>
 __device__ __forceinline__ void eval_helper_loop(EvalCtx& C, const TOPAY_GLB DevMap* mp, lds_dp cmd) {
   for (;;) {
@@ -132,8 +137,8 @@ __device__ __forceinline__ void eval_helper_loop(EvalCtx& C, const TOPAY_GLB Dev
     C.lam0 = cmd[4]; C.lam1 = cmd[5]; C.rho0 = cmd[6]; C.rho1 = cmd[7];
     const int stage = __builtin_amdgcn_readfirstlane(ic[1]);
     gate.always = ic[2] != 0; gate.has_early = ic[3] != 0; gate.early_ok = ic[4] != 0;
-    if (stage == 1) (void)eval_cost_grad_mw<1, RMAX_E, NWE, OCC>(C, mp, gate);
-    else (void)eval_cost_grad_mw<2, RMAX_E, NWE, OCC>(C, mp, gate);
+    if (stage == 1) (void)eval_cost_grad<1, RMAX_E, NWE, OCC>(C, mp, gate);
+    else (void)eval_cost_grad<2, RMAX_E, NWE, OCC>(C, mp, gate);
     wg_lds_barrier();
   }
 }
@@ -155,7 +160,7 @@ __device__ __forceinline__ void eval_helper_loop(EvalCtx& C, const TOPAY_GLB Dev
 // waves join a one-wave solver.
 template <int RMAX, int OCC = 2, int NWE = 1, int RMAX_E = RMAX>
 __device__ __forceinline__ void solve_trajectory(EvalCtx& C, const TOPAY_GLB DevMap* mp, SolveIO& S, int s1_past,
-                                                 lds_dp pf /* LDS [8 + 40], then the command block if NWE != 1 */, int& success_out,
+                                                 lds_dp pf /* LDS: the solver's tail (solve_tail_doubles) */, int& success_out,
                                                  double& cost_out, int& interrupted_out) {
   constexpr bool HELPERS = NWE != 1;
   dev_params_ref P = dev_params();
@@ -243,7 +248,7 @@ __device__ __forceinline__ void solve_trajectory(EvalCtx& C, const TOPAY_GLB Dev
     // what is live across a call would otherwise be spilled to scratch memory): every lane writes the same values to
     // the same words and reads them back afterwards.
     {
-      lds_dp pk = pf + 8;
+      lds_dp pk = pf + kSolvePastDoubles;
       pk[0] = fx; pk[1] = step; pk[2] = stp; pk[3] = finit; pk[4] = dginit; pk[5] = dgtest; pk[6] = dstest; pk[7] = mu;
       pk[8] = nu; pk[9] = cost;
       TOPAY_LDS int* ik = (TOPAY_LDS int*)(pk + 10);
@@ -259,7 +264,7 @@ __device__ __forceinline__ void solve_trajectory(EvalCtx& C, const TOPAY_GLB Dev
       qk[12] = (unsigned long long)S.grp_tau; qk[13] = (unsigned long long)S.cancel_flag;
     }
     if constexpr (HELPERS) {
-      lds_dp cmd = pf + 48;
+      lds_dp cmd = pf + kSolvePastDoubles + kSolveParkDoubles;
       cmd[0] = gate.finit; cmd[1] = gate.thr; cmd[2] = gate.early; cmd[3] = gate.skip_thr;
       cmd[4] = C.lam0; cmd[5] = C.lam1; cmd[6] = C.rho0; cmd[7] = C.rho1;
       TOPAY_LDS int* ic = (TOPAY_LDS int*)(cmd + 8);
@@ -267,15 +272,15 @@ __device__ __forceinline__ void solve_trajectory(EvalCtx& C, const TOPAY_GLB Dev
       __syncthreads();   // the helper waves wait here (eval_helper_loop); x written above is visible to them
     }
     LSTAMP(15);   // interruption poll, barrier, state parked
-    if (stage == 1) f = eval_cost_grad_mw<1, RMAX_E, NWE, OCC>(C, mp, gate);
-    else f = eval_cost_grad_mw<2, RMAX_E, NWE, OCC>(C, mp, gate);
+    if (stage == 1) f = eval_cost_grad<1, RMAX_E, NWE, OCC>(C, mp, gate);
+    else f = eval_cost_grad<2, RMAX_E, NWE, OCC>(C, mp, gate);
 #ifdef TOPAY_STAMPS
     lt_ = (long long)__builtin_amdgcn_s_memtime();
 #endif
     if (NWE > 1) wg_lds_barrier();   // every wave is out of the evaluation's last reduction before the scratch is used again
     {
       // (read back as wave-uniform values: scalar registers, scalar branches, scalar base addresses for the vector loads)
-      lds_cdp pk = pf + 8;
+      lds_cdp pk = pf + kSolvePastDoubles;
       fx = uniform_f64(pk[0]); step = uniform_f64(pk[1]); stp = uniform_f64(pk[2]); finit = uniform_f64(pk[3]);
       dginit = uniform_f64(pk[4]); dgtest = uniform_f64(pk[5]); dstest = uniform_f64(pk[6]); mu = uniform_f64(pk[7]);
       nu = uniform_f64(pk[8]); cost = uniform_f64(pk[9]);
@@ -484,8 +489,8 @@ __device__ __forceinline__ void solve_trajectory(EvalCtx& C, const TOPAY_GLB Dev
               for (int t = 0; t < EPL; t++) dr[t] = vec_in(tid, t, n) ? -gv[t] : 0.0;
             }
             double sb[PF][EPL], yb[PF][EPL], rb[PF];
-            // [mem <= 256]: every lane writes / reads the same entry (LDS broadcast).  The ring lives in the evaluation's
-            // scratch region (band / pass buffers, >= 960 doubles): nothing of an evaluation stays there between two calls,
+            // [mem <= kLbfgsMaxMem]: every lane writes / reads the same entry (LDS broadcast).  The ring lives in the evaluation's
+            // scratch region (EvalCtx::X: positional gradients / pass buffers): nothing of an evaluation stays there between two calls,
             // and the recursion runs between them -- 2 KB less LDS per workgroup.
             lds_dp alpha = C.X;
             // wave-uniform loop state in scalar registers (the values are uniform by construction; the compiler only
@@ -651,7 +656,7 @@ __device__ __forceinline__ void solve_trajectory(EvalCtx& C, const TOPAY_GLB Dev
     }
   }
   if constexpr (HELPERS) {   // release the helper waves
-    TOPAY_LDS int* ic = (TOPAY_LDS int*)(pf + 48 + 8);
+    TOPAY_LDS int* ic = (TOPAY_LDS int*)(pf + kSolvePastDoubles + kSolveParkDoubles + 8);
     ic[0] = 0;
     __syncthreads();
   }

@@ -7,7 +7,7 @@
 #define TOPAY_EP 13         // even ("full") samples per piece = K+1
 #define TOPAY_NSPH 12       // collision spheres (moma_param.h:94-109)
 // Pieces per trajectory this build solves: 170 (a 255 s trajectory at the reference's 1.5 s sample_interval) -- what the LDS of a
-// compute unit holds: 1020 system rows = 4 per thread of a four-wave workgroup and 158 of the 160 KB (topay_eval_mw.h); the
+// compute unit holds: 1020 system rows = 4 per thread of a four-wave workgroup and 154 of the 160 KB (eval_lds_total + solve_tail_doubles); the
 // one-wave solver of that class keeps 28 vector elements per lane (1792 >= 10 N - 8).  Launch classes: N <= 10 / 15 / 21 / 32
 // one wave per trajectory (1 / 2 / 2 / 3 system rows per lane), N <= 42 / 64 / 170 four waves in the evaluations (2 / 2 / 4 rows
 // per thread) with the solver on the first.  The reference itself has no cap (moma_traj_opt.cpp:245, 300-321); longer
@@ -51,6 +51,7 @@ struct DevMap {
   glb_cdp esdf2d_critical;   // map came through topay_set_map without them)
 };
 
+constexpr int kLbfgsMaxMem = 256;   // longest L-BFGS history topay_set_params accepts (the reference's mem_size)
 struct DevLbfgs {
   int mem_size, past, max_iterations, max_linesearch;
   double g_epsilon, delta, min_step, max_step, f_dec_coeff, s_curv_coeff, cautious_factor, machine_prec;
@@ -149,7 +150,7 @@ struct DevBatch {
   double* alm;        // [B][kAlmLen] lambda0,1 rho0,1 (eval hook input / solver output)
   double* fout;       // [B] eval hook output
   double* sbuf;       // [kSbufPerPiece poff]  [14][TOPAY_EP N] per-sample gradient rows parked between the cost and the gradient phase
-  double* mstash;     // [kMstashPerPiece poff]  [TOPAY_EP N][36] forces of self-colliding sphere pairs of a sample (rarely touched, topay_eval.h)
+  double* mstash;     // [kMstashPerPiece poff]  [TOPAY_EP N][36] forces of self-colliding sphere pairs of a sample (rarely touched, topay_mani.h)
   double* start_us;   // [B] start of the solve on the device's constant clock (scheduling diagnostics)
   // persistent launches: one queue per N-class = positions [queue_off[k], queue_off[k] + queue_count[k]) of `order`, handed
   // out through the device counters queue_next[k]; a workgroup of class queue_class drains its own queue, then the
