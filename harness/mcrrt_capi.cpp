@@ -4,6 +4,7 @@
 #include "mcrrt.hpp"
 #include "jps.hpp"
 #include "topo_prm.hpp"
+#include "replan.hpp"
 
 using namespace topay_wl;
 
@@ -148,3 +149,42 @@ int wl_topo_samples_in(void* world, const double* inflate, const double* critica
   }
 }
 }
+
+extern "C" {
+
+// ---- the replanning cycle's restatement (harness/replan.hpp) ----------------------------------------------------------
+// A MomaTraj from setTraj's arguments: start (x, y, theta), durations [n], coefficients [n][9][6], highest order first.
+void* wl_replan_traj_create(const double* start3, int n, const double* durations, const double* coeffs) {
+  ReplanTraj* t = new ReplanTraj();
+  for (int a = 0; a < 3; a++) t->start_state[a] = start3[a];
+  t->T.assign(durations, durations + n);
+  t->C.assign(coeffs, coeffs + (size_t)n * 54);
+  t->init();
+  return t;
+}
+void wl_replan_traj_destroy(void* h) { delete (ReplanTraj*)h; }
+int wl_replan_car_seq_len(void* h) { return (int)((ReplanTraj*)h)->car_seq.size(); }
+void wl_replan_state(void* h, double t, double* state10, double* dstate10) {
+  ((ReplanTraj*)h)->getState(t, state10);
+  ((ReplanTraj*)h)->getDState(t, dstate10);
+}
+// safeCallback against the given fields.  first_hit[2] = sample, body; hit[2] = time, distance; returns is_safe.
+int wl_replan_safe(void* h, const double* origin, double res, const int* dims, const double* min_b, const double* max_b, const double* esdf2d,
+                   const double* esdf3d, int* first_hit, double* hit, double* min_margin) {
+  topay_oracle::Map m;
+  m.set(origin, res, dims, esdf2d, esdf3d);
+  m.setBounds(min_b, max_b);
+  const topay_oracle::Robot robot;
+  const ReplanSafe r = replan_safe(*(ReplanTraj*)h, m, robot);
+  first_hit[0] = r.sample; first_hit[1] = r.body;
+  hit[0] = r.t; hit[1] = r.d;
+  *min_margin = r.min_margin;
+  return r.is_safe ? 1 : 0;
+}
+int wl_replan_endpoints(void* end_traj, void* global_traj, double since_last_replan, double since_begin, const double* global_goal,
+                        double planning_budget, double planning_horizon, double* start, double* start_v, double* goal) {
+  return replan_endpoints(*(ReplanTraj*)end_traj, (const ReplanTraj*)global_traj, since_last_replan, since_begin, global_goal, planning_budget,
+                          planning_horizon, start, start_v, goal);
+}
+
+}  // extern "C"

@@ -309,8 +309,62 @@ def mlib():
         L.wl_rs_interpolate.restype = None
         L.wl_mcrrt_u01.argtypes = [C.c_uint64] * 4
         L.wl_mcrrt_u01.restype = C.c_double
+        L.wl_replan_traj_create.argtypes = [c_dp, C.c_int, c_dp, c_dp]
+        L.wl_replan_traj_create.restype = C.c_void_p
+        L.wl_replan_traj_destroy.argtypes = [C.c_void_p]
+        L.wl_replan_traj_destroy.restype = None
+        L.wl_replan_car_seq_len.argtypes = [C.c_void_p]
+        L.wl_replan_state.argtypes = [C.c_void_p, C.c_double, c_dp, c_dp]
+        L.wl_replan_state.restype = None
+        L.wl_replan_safe.argtypes = [C.c_void_p, c_dp, C.c_double, c_ip, c_dp, c_dp, c_dp, c_dp, c_ip, c_dp, c_dp]
+        L.wl_replan_endpoints.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, c_dp, C.c_double, C.c_double, c_dp, c_dp, c_dp]
         _MLIB = L
     return _MLIB
+
+
+class ReplanTraj:
+    """CPU restatement of MomaTraj with Planner::safeCallback and the endpoints of Planner::replanCallback (harness/replan.hpp).
+    start3 = (x, y, theta), durations [N], coeffs [N, 9, 6] with the highest order first, as setTraj takes them."""
+
+    def __init__(self, start3, durations, coeffs):
+        self.L = mlib()
+        s3 = np.ascontiguousarray(start3, dtype=np.float64).reshape(-1)[:3].copy()
+        dur = np.ascontiguousarray(durations, dtype=np.float64).reshape(-1)
+        co = np.ascontiguousarray(coeffs, dtype=np.float64).reshape(-1)
+        assert len(co) == 54 * len(dur)
+        self.T = float(np.add.accumulate(dur)[-1])
+        self.h = self.L.wl_replan_traj_create(_dp(s3), len(dur), _dp(dur), _dp(co))
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.L.wl_replan_traj_destroy(self.h)
+            self.h = None
+
+    def state(self, t):
+        """(getState(t), getDState(t))"""
+        s, d = np.zeros(10), np.zeros(10)
+        self.L.wl_replan_state(self.h, float(t), _dp(s), _dp(d))
+        return s, d
+
+    def safe(self, origin, res, dims, min_b, max_b, esdf2d, esdf3d):
+        """safeCallback against the given fields: dict(safe, sample, body, t, d, min_margin) -- min_margin = the smallest
+        |d - 0.99 r| over every body of every sample up to and including the first hit."""
+        org = np.ascontiguousarray(origin, dtype=np.float64)
+        dm = np.ascontiguousarray(dims, dtype=np.int32)
+        mn, mx = np.ascontiguousarray(min_b, dtype=np.float64), np.ascontiguousarray(max_b, dtype=np.float64)
+        e2, e3 = np.ascontiguousarray(esdf2d, dtype=np.float64), np.ascontiguousarray(esdf3d, dtype=np.float64)
+        fh, hit, mm = np.zeros(2, dtype=np.int32), np.zeros(2), np.zeros(1)
+        ok = self.L.wl_replan_safe(self.h, _dp(org), float(res), dm.ctypes.data_as(c_ip), _dp(mn), _dp(mx), _dp(e2), _dp(e3), fh.ctypes.data_as(c_ip),
+                                   _dp(hit), _dp(mm))
+        return dict(safe=bool(ok), sample=int(fh[0]), body=int(fh[1]), t=float(hit[0]), d=float(hit[1]), min_margin=float(mm[0]))
+
+    def endpoints(self, global_traj, t_since_replan, t_since_begin, global_goal, planning_budget, planning_horizon):
+        """replanCallback:708-731 with this trajectory as end_traj: (start, start_v, goal, goal_source)."""
+        gg = np.ascontiguousarray(global_goal, dtype=np.float64)
+        st, sv, go = np.zeros(10), np.zeros(10), np.zeros(10)
+        src = self.L.wl_replan_endpoints(self.h, global_traj.h if global_traj is not None else None, float(t_since_replan), float(t_since_begin),
+                                         _dp(gg), float(planning_budget), float(planning_horizon), _dp(st), _dp(sv), _dp(go))
+        return st, sv, go, int(src)
 
 
 def mcrrt_plan(world, start, end, car_path, params=None, inst=0, track_slack=False, want_nodes=True):

@@ -546,6 +546,72 @@ topay_status topay_plan_get_front_path(topay_ctx* ctx, int call, int cap_states,
 topay_status topay_plan_stage_ms(topay_ctx* ctx, double* ms /* 8 */);
 topay_status topay_plan_test_chunk(topay_ctx* ctx, int calls);
 
+/* ---- the replanning cycle: what runs around planMomaParallel while the robot moves.
+ * Tracked trajectories.  A context keeps, per robot slot (0 .. TOPAY_TRACK_SLOTS - 1 = 4095), up to two committed trajectories
+ * that outlive planning calls: 1 = end_traj, the one the robot follows and the planner replaces (planner.cpp:1010), and
+ * 2 = global_traj, the one local goals are taken from.  A trajectory is a MomaTraj (moma_traj_opt.h:26-110): start state
+ * (x, y, theta), up to 170 pieces -- durations and coefficients in the layout of topay_get_results, per piece 9 x 6, highest
+ * order first -- and car_seq, which is computed once when the trajectory is committed, as MomaTraj's constructor does.
+ *   topay_track_set          MomaTraj::setTraj (moma_traj_opt.h:96-110) from host data; which: 1, 2 or 3 = both
+ *   topay_track_commit_plan  the winners of calls call_idx[k] of the last topay_plan_calls into slots robots[k], device to
+ *                            device; committed[k] (may be NULL) = 1, or 0 when the call has no winner: the slot stays as it was
+ *   topay_track_get          *n_pieces = pieces of the slot's trajectory (0: none; which: 1 or 2); the other outputs may be NULL
+ *   topay_track_clear        both trajectories of the slot
+ * TOPAY_ERR_INVALID_ARG: a robot slot out of range, which out of range, n_pieces outside 1..170, a total duration that is
+ * not in (0, 1e4) (the gate's "no trajectory" rule; a NaN among the durations is such a one); a robot slot named twice in
+ * one topay_track_commit_plan.
+ * Memory: the trajectories lie in one device arena that grows and gives nothing back before topay_destroy.  A slot's block is
+ * sized to the next power of two above what its trajectory needs (55 doubles per piece and 2 per 0.025 s of duration; at least
+ * 1024 doubles) and is
+ * reused by every later trajectory that fits, topay_track_clear included; one that does not fit gets a new block and the old
+ * one is lost.  The lost blocks of a slot sum to less than its last one, so the arena stays below four times what the largest
+ * trajectory of every (slot, which) ever committed needs (16 KiB where that is more), however long the loop runs. */
+#define TOPAY_TRACK_SLOTS 4096
+topay_status topay_track_set(topay_ctx* ctx, int robot, int which, const double* start3, int n_pieces, const double* durations,
+                             const double* coeffs /* n_pieces x 9 x 6 */);
+topay_status topay_track_commit_plan(topay_ctx* ctx, int n, const int* robots, const int* call_idx, int which, int* committed);
+topay_status topay_track_get(topay_ctx* ctx, int robot, int which, int cap_pieces, int* n_pieces, double* start3, double* durations,
+                             double* coeffs);
+topay_status topay_track_clear(topay_ctx* ctx, int robot);
+/* == Planner::safeCallback (planner.cpp:597-638) for n robots: end_traj of slot robots[k] sampled every 0.01 s (t = 0; t < T;
+ * t += 0.01, the running sum) through getState against map slot map_ids[k] AS IT IS NOW -- not the map the trajectory was
+ * planned on: getDistance2d of the chassis against 0.99 chassis_colli_radius, then getDistance3d of the 12 collision spheres
+ * against 0.99 radius, in that order; the sweep of a robot ends at its first violation.  A point outside the map is 1e10 away.
+ *   safe[k]          1 / 0
+ *   first_hit[k][2]  index of the first violating sample and the first body in the reference's loop order at that sample
+ *                    (0 chassis, 1..12 spheres); -1, -1 when safe
+ *   hit[k][2]        time and distance of that hit; NaN when safe
+ * Output pointers may be NULL.  TOPAY_ERR_NO_TRAJ: a slot without an end_traj; TOPAY_ERR_NO_MAP: a map slot that is not set.
+ * topay_track_safe_ms: device time (HIP events around the launch) of the last sweep. */
+topay_status topay_track_safe(topay_ctx* ctx, int n, const int* robots, const int* map_ids, int* safe, int* first_hit, double* hit);
+topay_status topay_track_safe_ms(topay_ctx* ctx, double* ms);
+/* The endpoints of a replan, Planner::replanCallback (planner.cpp:708-731), for n robots:
+ *   start[k]    end_traj.getState(t_s), t_s = t_since_replan[k] + planning_budget
+ *   start_v[k]  end_traj.getDState(t_s) (moma_traj_opt.h:149-158): ds/dt, dtheta/dt, 0, the seven joint rates; t clamped to [0, T]
+ *   goal[k]     the first state of global_traj on the grid t = t_since_begin[k], += 0.1, while t < T_g, whose xy is more than
+ *               planning_horizon from start's xy; else global_goal[k] (also when the slot has no global_traj)
+ *   goal_source[k]  the index of that step, -1 when global_goal was used
+ * The clocks must be finite and t_since_begin not negative.  TOPAY_ERR_NO_TRAJ: a slot without an end_traj. */
+topay_status topay_replan_inputs(topay_ctx* ctx, int n, const int* robots, const double* t_since_replan, const double* t_since_begin,
+                                 const double* global_goal /* n x 10 */, double planning_budget, double planning_horizon,
+                                 double* start /* n x 10 */, double* start_v /* n x 10 */, double* goal /* n x 10 */, int* goal_source);
+/* One round of Planner::replanCallback (planner.cpp:640-750) for n robots: the safety sweep of every robot against
+ * map_ids[k]; the trigger t_since_replan > replan_interval || !safe, unless now_xy (n x 2, may be NULL) is within 0.5 m of
+ * global_goal's xy (planner.cpp:649: arrived); the endpoints of the triggered robots; ONE planning call for all of them, as
+ * topay_plan_calls runs it, robot k's call numbered first_call + k -- k its position among the n given, so that its result does
+ * not depend on which others triggered; the winners committed as end_traj (global_traj stays).  The three 10-vectors per
+ * triggered robot pass through the host between the stages; trajectories, fields and sweeps stay on the device.  A robot
+ * slot may be named only once among the n (TOPAY_ERR_INVALID_ARG).
+ *   status[k][4]     outcome (0 not due, 1 replanned and committed, 2 due but no winner: the old trajectory is kept, 3 arrived),
+ *                    safe, the robot's row in the plan store (what topay_plan_get_trajs takes) or -1, goal_source
+ *   endpoints[k][30] (optional) start, start_v, goal of the triggered robots, NaN for the others
+ *   plan_result[k][8], plan_candidates[k][2][8][4]  (optional) the tables of topay_plan_calls for the triggered robots, zeros
+ *                    for the others */
+topay_status topay_replan_calls(topay_ctx* ctx, int n, const int* robots, const int* map_ids, const double* t_since_replan,
+                                const double* t_since_begin, const double* now_xy, const double* global_goal, double replan_interval,
+                                double planning_budget, double planning_horizon, const topay_plan_params_t* params,
+                                unsigned long long first_call, int* status, double* endpoints, int* plan_result, int* plan_candidates);
+
 /* ompl::base::ReedsSheppStateSpace(rho) for n pose pairs (x, y, theta): distance[i] = distance(from_i, to_i), word[i] /
  * lengths[i][5] = the shortest path's segment word (0..17, OMPL's reedsSheppPathType numbering) and signed segment lengths
  * in units of rho, pose[i] = interpolate(from_i, to_i, t[i]) when t is given.  Output pointers may be NULL. */

@@ -170,6 +170,16 @@ def load(path=None):
         L.topay_plan_get_front_path.argtypes = [C.c_void_p, C.c_int, C.c_int, c_ip, c_dp]
         L.topay_plan_stage_ms.argtypes = [C.c_void_p, c_dp]
         L.topay_plan_test_chunk.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(L, "topay_replan_calls"):   # (older builds of the library under tools/libs, A/B runs)
+        L.topay_track_set.argtypes = [C.c_void_p, C.c_int, C.c_int, c_dp, C.c_int, c_dp, c_dp]
+        L.topay_track_commit_plan.argtypes = [C.c_void_p, C.c_int, c_ip, c_ip, C.c_int, c_ip]
+        L.topay_track_get.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, c_ip, c_dp, c_dp, c_dp]
+        L.topay_track_clear.argtypes = [C.c_void_p, C.c_int]
+        L.topay_track_safe.argtypes = [C.c_void_p, C.c_int, c_ip, c_ip, c_ip, c_ip, c_dp]
+        L.topay_track_safe_ms.argtypes = [C.c_void_p, c_dp]
+        L.topay_replan_inputs.argtypes = [C.c_void_p, C.c_int, c_ip, c_dp, c_dp, c_dp, C.c_double, C.c_double, c_dp, c_dp, c_dp, c_ip]
+        L.topay_replan_calls.argtypes = [C.c_void_p, C.c_int, c_ip, c_ip, c_dp, c_dp, c_dp, c_dp, C.c_double, C.c_double, C.c_double,
+                                         C.POINTER(PlanParams), C.c_ulonglong, c_ip, c_dp, c_ip, c_ip]
     L.topay_reeds_shepp.argtypes = [C.c_void_p, C.c_int, c_dp, c_dp, c_dp, C.c_double, c_dp, c_ip, c_dp, c_dp]
     L.topay_dense_path.argtypes = [C.c_void_p, C.c_int, c_ip, c_dp, C.c_double, c_dp, c_dp, C.c_double, C.c_double, C.c_int, c_ip, c_dp]
     L.topay_connect_check_num.argtypes = [C.c_int, c_dp, c_dp, c_dp, C.c_double, c_ip]
@@ -884,8 +894,17 @@ class MomaTrajOptBatch:
         res, cand, wcd = np.zeros((n, 8), dtype=np.int32), np.zeros((n, 2, 8, 4), dtype=np.int32), np.zeros((n, 2))
         _chk(self.L, self.L.topay_plan_calls(self.h, n, _ip(mid), _dp(st), _dp(en), _dp(sv), None if params is None else C.byref(params),
                                              int(first_call), _ip(res), _ip(cand), _dp(wcd)))
-        self._plan_pieces = np.where(res[:, 0] == 1, res[:, 5], 0)
+        self._note_plan_store(np.arange(n), res)
         return res, cand, wcd
+
+    def _note_plan_store(self, rows, res):
+        """What plan_trajs needs to size its buffers: the pieces of the winner in every row of the plan store, from the result
+        table of the call that filled it (rows[k] = the store row of res[k], -1: none).  plan_calls and replan_calls share it."""
+        rows = np.asarray(rows)
+        pieces = np.zeros(int(rows.max()) + 1 if (rows >= 0).any() else 0, dtype=np.int32)
+        has = rows >= 0
+        pieces[rows[has]] = np.where(res[has, 0] == 1, res[has, 5], 0)
+        self._plan_pieces = pieces
 
     def plan_trajs(self, calls):
         """The winners of a selection of calls of the last plan_calls, packed like getTrajs: piece_off[n+1], durations[P],
@@ -918,6 +937,86 @@ class MomaTrajOptBatch:
         ms = np.zeros(8)
         _chk(self.L, self.L.topay_plan_stage_ms(self.h, _dp(ms)))
         return dict(zip(PLAN_STAGE_MS_KEYS, ms.tolist()))
+
+    # ---- tracked trajectories and the replanning cycle (topay_host_track.h)
+    def track_set(self, robot, which, start3, durations, coeffs):
+        """MomaTraj::setTraj into robot slot `robot`: which 1 = end_traj, 2 = global_traj, 3 = both; coeffs [N, 9, 6] in the
+        layout of getTrajs (highest order first)."""
+        s3 = np.ascontiguousarray(start3, dtype=np.float64).reshape(-1)[:3].copy()
+        dur = np.ascontiguousarray(durations, dtype=np.float64).reshape(-1)
+        co = np.ascontiguousarray(coeffs, dtype=np.float64).reshape(-1)
+        if len(co) != 54 * len(dur):
+            raise ValueError("coeffs must hold 9 x 6 values per piece")
+        _chk(self.L, self.L.topay_track_set(self.h, int(robot), int(which), _dp(s3), len(dur), _dp(dur), _dp(co)))
+
+    def track_commit_plan(self, robots, calls, which=1):
+        """The winners of `calls` of the last plan_calls into the robot slots, on the device.  Returns committed [n] (0: the call
+        had no winner, the slot is as it was)."""
+        rb = np.ascontiguousarray(robots, dtype=np.int32)
+        ci = np.ascontiguousarray(calls, dtype=np.int32)
+        done = np.zeros(len(rb), dtype=np.int32)
+        _chk(self.L, self.L.topay_track_commit_plan(self.h, len(rb), _ip(rb), _ip(ci), int(which), _ip(done)))
+        return done
+
+    def track_get(self, robot, which=1):
+        """(start3, durations [N], coeffs [N, 9, 6]) of the slot's trajectory, or None when it holds none."""
+        n = C.c_int(0)
+        _chk(self.L, self.L.topay_track_get(self.h, int(robot), int(which), 0, C.byref(n), None, None, None))
+        if n.value == 0:
+            return None
+        s3, dur, co = np.zeros(3), np.zeros(n.value), np.zeros(n.value * 54)
+        _chk(self.L, self.L.topay_track_get(self.h, int(robot), int(which), n.value, C.byref(n), _dp(s3), _dp(dur), _dp(co)))
+        return s3, dur, co.reshape(-1, 9, 6)
+
+    def track_clear(self, robot):
+        _chk(self.L, self.L.topay_track_clear(self.h, int(robot)))
+
+    def track_safe(self, robots, map_ids):
+        """Planner::safeCallback of the robots' end_traj against the map slots as they are now.  Returns (safe [n] bool,
+        first_hit [n, 2] = (sample, body), hit [n, 2] = (time, distance))."""
+        rb = np.ascontiguousarray(robots, dtype=np.int32)
+        mid = np.ascontiguousarray(map_ids, dtype=np.int32)
+        n = len(rb)
+        safe, fh, hit = np.zeros(n, dtype=np.int32), np.zeros((n, 2), dtype=np.int32), np.zeros((n, 2))
+        _chk(self.L, self.L.topay_track_safe(self.h, n, _ip(rb), _ip(mid), _ip(safe), _ip(fh), _dp(hit)))
+        return safe.astype(bool), fh, hit
+
+    def track_safe_ms(self):
+        """Device time of the last track_safe (or of the sweep of the last replan_calls), milliseconds."""
+        ms = np.zeros(1)
+        _chk(self.L, self.L.topay_track_safe_ms(self.h, _dp(ms)))
+        return float(ms[0])
+
+    def replan_inputs(self, robots, t_since_replan, t_since_begin, global_goal, planning_budget, planning_horizon):
+        """The endpoints of Planner::replanCallback: (start [n, 10], start_v [n, 10], goal [n, 10], goal_source [n])."""
+        rb = np.ascontiguousarray(robots, dtype=np.int32)
+        n = len(rb)
+        tr = np.ascontiguousarray(np.broadcast_to(np.asarray(t_since_replan, dtype=np.float64), (n,)))
+        tb = np.ascontiguousarray(np.broadcast_to(np.asarray(t_since_begin, dtype=np.float64), (n,)))
+        gg = np.ascontiguousarray(global_goal, dtype=np.float64).reshape(n, 10)
+        st, sv, go, src = np.zeros((n, 10)), np.zeros((n, 10)), np.zeros((n, 10)), np.zeros(n, dtype=np.int32)
+        _chk(self.L, self.L.topay_replan_inputs(self.h, n, _ip(rb), _dp(tr), _dp(tb), _dp(gg), float(planning_budget), float(planning_horizon),
+                                                _dp(st), _dp(sv), _dp(go), _ip(src)))
+        return st, sv, go, src
+
+    def replan_calls(self, robots, map_ids, t_since_replan, t_since_begin, global_goal, replan_interval, planning_budget, planning_horizon,
+                     now_xy=None, params=None, first_call=0):
+        """One round of Planner::replanCallback for n robots (topay_replan_calls).  Returns (status [n, 4] = (outcome, safe, row
+        in the plan store, goal_source), endpoints [n, 3, 10] = (start, start_v, goal), result [n, 8], candidates [n, 2, 8, 4])."""
+        rb = np.ascontiguousarray(robots, dtype=np.int32)
+        n = len(rb)
+        mid = np.ascontiguousarray(map_ids, dtype=np.int32)
+        tr = np.ascontiguousarray(np.broadcast_to(np.asarray(t_since_replan, dtype=np.float64), (n,)))
+        tb = np.ascontiguousarray(np.broadcast_to(np.asarray(t_since_begin, dtype=np.float64), (n,)))
+        gg = np.ascontiguousarray(global_goal, dtype=np.float64).reshape(n, 10)
+        xy = None if now_xy is None else np.ascontiguousarray(now_xy, dtype=np.float64).reshape(n, 2)
+        status, ends = np.zeros((n, 4), dtype=np.int32), np.zeros((n, 3, 10))
+        res, cand = np.zeros((n, 8), dtype=np.int32), np.zeros((n, 2, 8, 4), dtype=np.int32)
+        _chk(self.L, self.L.topay_replan_calls(self.h, n, _ip(rb), _ip(mid), _dp(tr), _dp(tb), _dp(xy), _dp(gg), float(replan_interval),
+                                               float(planning_budget), float(planning_horizon), None if params is None else C.byref(params),
+                                               int(first_call), _ip(status), _dp(ends), _ip(res), _ip(cand)))
+        self._note_plan_store(status[:, 2], res)
+        return status, ends, res, cand
 
     def mcrrt_params(self, **kw):
         p = McrrtParams()

@@ -95,6 +95,33 @@ __device__ __forceinline__ double feas_dist3d(const DevMap& M, double px, double
 }
 __device__ __forceinline__ double wave_min(double v) { return -wave_max(-v); }
 
+// car_seq (moma_traj_opt.h:40-69): the chassis xy after every Simpson panel of 0.025 s into F.cseq[0 .. num].  Lanes <->
+// panels, inclusive wave scan with a carry across the passes of 64.  The one statement of it: the gate, playback() and
+// k_track_commit (topay_track.h) call this.
+__device__ __forceinline__ void feas_car_seq(const FeasIO& F, long long num, int lane) {
+  const double seq_res = 0.1;
+  const int approx_res = 4;
+  const double h = seq_res / approx_res, hh = h / 2.0, h6 = h / 6.0;
+  if (lane == 0) { F.cseq[0] = F.x0; F.cseq[1] = F.y0; }
+  double carryx = 0.0, carryy = 0.0;
+  for (long long p0 = 0; p0 < num; p0 += 64) {
+    const long long i = p0 + lane;
+    double ix = 0.0, iy = 0.0;
+    if (i < num) {
+      // p1 of panel i is the reference's p3 of panel i-1, i.e. evaluated at (i-1)*h + h
+      const double ta = i == 0 ? 0.0 : (double)(i - 1) * h + h;
+      feas_simpson(F, ta, (double)i * h + hh, (double)i * h + h, h6, ix, iy);
+    }
+    const double sx = wave_incl_scan(ix, lane), sy = wave_incl_scan(iy, lane);
+    if (i < num) {
+      F.cseq[2 * (i + 1)] = F.x0 + (carryx + sx);
+      F.cseq[2 * (i + 1) + 1] = F.y0 + (carryy + sy);
+    }
+    carryx += __shfl(sx, 63);
+    carryy += __shfl(sy, 63);
+  }
+}
+
 __device__ __forceinline__ void feasibility_gate(const FeasIO& F, const TOPAY_GLB DevMap* mp) {
   dev_params_ref P = dev_params();
   const int lane = threadIdx.x & 63;
@@ -114,7 +141,7 @@ __device__ __forceinline__ void feasibility_gate(const FeasIO& F, const TOPAY_GL
   // ---- 1. car_seq
   const double seq_res = 0.1;
   const int approx_res = 4;
-  const double h = seq_res / approx_res, hh = h / 2.0, h6 = h / 6.0;
+  const double h = seq_res / approx_res;
   long long num = (long long)floor(Ttot / h);
   if (num > F.cap_panels || (long long)(Ttot / 0.01) + 2 > F.cap_samples) {
     // the scratch cannot hold this trajectory: nothing is sampled (a truncated sweep would miss the tail's violations)
@@ -132,24 +159,7 @@ __device__ __forceinline__ void feasibility_gate(const FeasIO& F, const TOPAY_GL
     }
     return;
   }
-  if (lane == 0) { F.cseq[0] = F.x0; F.cseq[1] = F.y0; }
-  double carryx = 0.0, carryy = 0.0;
-  for (long long p0 = 0; p0 < num; p0 += 64) {
-    const long long i = p0 + lane;
-    double ix = 0.0, iy = 0.0;
-    if (i < num) {
-      // p1 of panel i is the reference's p3 of panel i-1, i.e. evaluated at (i-1)*h + h
-      const double ta = i == 0 ? 0.0 : (double)(i - 1) * h + h;
-      feas_simpson(F, ta, (double)i * h + hh, (double)i * h + h, h6, ix, iy);
-    }
-    const double sx = wave_incl_scan(ix, lane), sy = wave_incl_scan(iy, lane);
-    if (i < num) {
-      F.cseq[2 * (i + 1)] = F.x0 + (carryx + sx);
-      F.cseq[2 * (i + 1) + 1] = F.y0 + (carryy + sy);
-    }
-    carryx += __shfl(sx, 63);
-    carryy += __shfl(sy, 63);
-  }
+  feas_car_seq(F, num, lane);
   // ---- 2. sample times (t += res from 0 while t < T)
   long long nsamp = 0;
   if (lane == 0) {
@@ -285,26 +295,10 @@ __device__ __forceinline__ void playback(const FeasIO& F, int nq, const double* 
   }
   const double seq_res = 0.1;
   const int approx_res = 4;
-  const double h = seq_res / approx_res, hh = h / 2.0, h6 = h / 6.0;
+  const double h = seq_res / approx_res;
   long long num = (long long)floor(Ttot / h);
   if (num > F.cap_panels) num = F.cap_panels;
-  if (lane == 0) { F.cseq[0] = F.x0; F.cseq[1] = F.y0; }
-  double carryx = 0.0, carryy = 0.0;
-  for (long long p0 = 0; p0 < num; p0 += 64) {
-    const long long i = p0 + lane;
-    double ix = 0.0, iy = 0.0;
-    if (i < num) {
-      const double ta = i == 0 ? 0.0 : (double)(i - 1) * h + h;
-      feas_simpson(F, ta, (double)i * h + hh, (double)i * h + h, h6, ix, iy);
-    }
-    const double sx = wave_incl_scan(ix, lane), sy = wave_incl_scan(iy, lane);
-    if (i < num) {
-      F.cseq[2 * (i + 1)] = F.x0 + (carryx + sx);
-      F.cseq[2 * (i + 1) + 1] = F.y0 + (carryy + sy);
-    }
-    carryx += __shfl(sx, 63);
-    carryy += __shfl(sy, 63);
-  }
+  feas_car_seq(F, num, lane);
   wave_global_sync();
   const long long nseq = num / approx_res + 1;
   if (seq_out) {

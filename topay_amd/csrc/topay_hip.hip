@@ -25,6 +25,7 @@
 #include "topay_jps.h"
 #include "topay_topo.h"
 #include "topay_plan.h"
+#include "topay_track.h"
 #include "topay_yaml.h"
 
 #include "topay_kernels.h"
@@ -39,3 +40,4 @@
 #include "topay_host_dist.h"
 #include "topay_host_plan.h"
 #include "topay_host_world.h"
+#include "topay_host_track.h"

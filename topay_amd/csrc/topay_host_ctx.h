@@ -210,6 +210,13 @@ struct topay_ctx {
   std::vector<char> pl_event_done;
   int pl_chunk = 0;   // topay_plan_test_chunk: calls per front-end launch, 0 = the constant
   double pl_stage_ms[8] = {0};
+  // tracked trajectories (topay_host_track.h): the arena, the slots' descriptors (host: what the kernels are handed per call),
+  // the upload block of topay_track_set and the inputs / outputs of the sweep and endpoint kernels
+  DevBuf tr_arena, tr_stage, tr_io;
+  size_t tr_used = 0;   // doubles of the arena handed out
+  struct TrackSlot { topay::TrackDesc d[2] = {{0, 0, 0}, {0, 0, 0}}; long long cap[2] = {0, 0}; double T[2] = {0, 0}; };   // [0] end_traj, [1] global_traj
+  std::vector<TrackSlot> tr_slots;
+  double tr_safe_ms = 0.0;   // device time of the last k_track_safe launch
   DevBuf paths, path_off, path_len, bvel, bacc, scratch;
   DevBuf N, s1_past, map_id, head, tail, start_xy, goal_xy, init_xy, x0;
   DevBuf x, work, hist_s, hist_y, hist_ys, hist_alpha, lu;

@@ -76,10 +76,11 @@ struct PlanTry {   // the survivors of one try, over all front-end launches: the
 };
 
 // One try (t = 0 plain, 1 critical) for the calls `act`: front-end in launches of kPlanChunk calls, one solve, winners
-// into the store.  Fills the calls' rows of result / cand (n x 2 x 8 x 4) / wcd.
+// into the store.  Fills the calls' rows of result / cand (n x 2 x 8 x 4) / wcd.  Call p has the number call_nos[p], or
+// first_call + p when call_nos is null (the replanning cycle numbers its calls itself).
 static topay_status plan_try(topay_ctx* c, int t, const std::vector<int>& act, const std::vector<int>& mids, const double* start, const double* end,
-                             const double* start_v, const topay_plan_params_t& P, unsigned long long first_call, int* result, int* cand,
-                             double* wcd, PlanClock& clk) {
+                             const double* start_v, const topay_plan_params_t& P, unsigned long long first_call, const unsigned long long* call_nos, int* result,
+                             int* cand, double* wcd, PlanClock& clk) {
   topay_status s;
   PlanTry T;
   const int cap_paths = P.topo.reserve_num;
@@ -100,7 +101,7 @@ static topay_status plan_try(topay_ctx* c, int t, const std::vector<int>& act, c
       sxy[2 * (size_t)q] = start[10 * (size_t)p]; sxy[2 * (size_t)q + 1] = start[10 * (size_t)p + 1];
       exy[2 * (size_t)q] = end[10 * (size_t)p]; exy[2 * (size_t)q + 1] = end[10 * (size_t)p + 1];
       cmid[q] = mids[p];
-      call_no[q] = first_call + (unsigned long long)p;
+      call_no[q] = call_nos ? call_nos[p] : first_call + (unsigned long long)p;
       inst[q] = 2ull * call_no[q] + (unsigned long long)t;
       const DevMap& m = c->hmaps[cmid[q]];
       cap_points = std::max(cap_points, topo_pt_cap(m.dims[0], m.dims[1]));   // no selected path has more points than its map's cap
@@ -339,9 +340,9 @@ void topay_plan_default_params(topay_plan_params_t* p) {
   p->critical_retry = 1;       // planner.cpp:961-963
 }
 
-topay_status topay_plan_calls(topay_ctx* c, int n, const int* map_ids, const double* start, const double* end, const double* start_v,
-                              const topay_plan_params_t* params, unsigned long long first_call, int* result, int* candidates,
-                              double* winner_cost_duration) {
+static topay_status plan_calls_impl(topay_ctx* c, int n, const int* map_ids, const double* start, const double* end, const double* start_v,
+                                    const topay_plan_params_t* params, unsigned long long first_call, const unsigned long long* call_nos, int* result,
+                                    int* candidates, double* winner_cost_duration) {
   if (!c || n <= 0 || !start || !end || !result) return TOPAY_ERR_INVALID_ARG;
   topay_plan_params_t P;
   if (params) P = *params;
@@ -381,11 +382,17 @@ topay_status topay_plan_calls(topay_ctx* c, int n, const int* map_ids, const dou
     for (int p = 0; p < n; p++)
       if (result[8 * (size_t)p] == 0) act.push_back(p);
     if (act.empty()) break;
-    s = plan_try(c, t, act, mids, start, end, start_v, P, first_call, result, candidates, winner_cost_duration, clk);
+    s = plan_try(c, t, act, mids, start, end, start_v, P, first_call, call_nos, result, candidates, winner_cost_duration, clk);
   }
   clk.collect();
   if (s != TOPAY_OK) { c->ps_calls.clear(); return s; }
   return TOPAY_OK;
+}
+
+topay_status topay_plan_calls(topay_ctx* c, int n, const int* map_ids, const double* start, const double* end, const double* start_v,
+                              const topay_plan_params_t* params, unsigned long long first_call, int* result, int* candidates,
+                              double* winner_cost_duration) {
+  return plan_calls_impl(c, n, map_ids, start, end, start_v, params, first_call, nullptr, result, candidates, winner_cost_duration);
 }
 
 topay_status topay_plan_get_trajs(topay_ctx* c, int n, const int* call_idx, int cap_pieces, int* piece_off, double* durations, double* coeffs,

@@ -1,0 +1,351 @@
+// Host side of the C-ABI, part 9: tracked trajectories (end_traj / global_traj of every robot slot), the safety sweep, the
+// endpoints of a replan and the replanning cycle (topay_track.h; Planner::safeCallback and replanCallback).
+
+#pragma once
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The store.  One arena (c->tr_arena) holds every tracked trajectory in the layout stated in topay_track.h; it grows by
+// ragged offsets and keeps its contents.  A slot whose block is large enough for its next trajectory reuses it; one that is
+// not gets a new block and the old one is lost.  Blocks are sized to a power of two, so the lost blocks of a slot sum to
+// less than its last one: the arena is bounded by four times the largest need of every (slot, which), whatever the order
+// of the trajectories (include/topay.h states it).  track_commit_impl takes every (robot, w) at most once per call: two
+// workgroups would write one block.
+// ---------------------------------------------------------------------------------------------------------------------
+static const double kTrackPanel = 0.1 / 4;   // seq_res / approx_res (moma_traj_opt.h:28-29), the expression of the kernels
+
+static bool track_duration_ok(const double* dur, int N, double& T) {   // the gate's "no trajectory" rule
+  T = 0.0;
+  for (int i = 0; i < N; i++) T += dur[i];
+  return T > 0.0 && T < 1.0e4;
+}
+
+struct TrackPut {   // one trajectory on its way into the arena
+  int robot, w;     // w: 0 end_traj, 1 global_traj
+  int N;
+  double T;
+  long long src_piece, src_start;
+};
+
+// Blocks for `puts` (reused or appended), then k_track_commit from (s_dur, s_coef, s_start) on the device.
+static topay_status track_commit_impl(topay_ctx* c, const std::vector<TrackPut>& puts, const double* s_dur, const double* s_coef, const double* s_start) {
+  const size_t n = puts.size();
+  if (n == 0) return TOPAY_OK;
+  if (c->tr_slots.empty()) c->tr_slots.resize(TOPAY_TRACK_SLOTS);
+  std::vector<topay::TrackDesc> dst(n);
+  std::vector<long long> sp(n), ss(n), cap(n);
+  size_t used = c->tr_used;
+  for (size_t k = 0; k < n; k++) {
+    const TrackPut& p = puts[k];
+    const long long num = (long long)std::floor(p.T / kTrackPanel);
+    const long long need = topay::track_doubles(p.N, num);
+    const topay_ctx::TrackSlot& sl = c->tr_slots[p.robot];
+    dst[k].N = p.N;
+    dst[k].num = (int)num;
+    if (sl.cap[p.w] >= need) { dst[k].off = sl.d[p.w].off; cap[k] = sl.cap[p.w]; }
+    else {
+      long long blk = 1024;
+      while (blk < need) blk *= 2;
+      dst[k].off = (long long)used; cap[k] = blk; used += (size_t)blk;
+    }
+    sp[k] = p.src_piece; ss[k] = p.src_start;
+  }
+  topay_status s;
+  if ((s = grow_keep(c, c->tr_arena, used * 8, c->tr_used * 8)) != TOPAY_OK) return s;
+  topay::TrackDesc* d_dst; long long *d_sp, *d_ss;
+  auto lay = [&](Carver& k) { d_sp = k.take<long long>(n); d_ss = k.take<long long>(n); d_dst = k.take<topay::TrackDesc>(n); };
+  if ((s = c->tr_io.carve(lay)) != TOPAY_OK) return s;
+  HIPCHK(h2d(c, d_sp, sp.data(), n));
+  HIPCHK(h2d(c, d_ss, ss.data(), n));
+  HIPCHK(h2d(c, d_dst, dst.data(), n));
+  hipLaunchKernelGGL(topay::k_track_commit, dim3((unsigned)n), dim3(64), 0, c->stream, (int)n, (const topay::TrackDesc*)d_dst, (const long long*)d_sp,
+                     (const long long*)d_ss, s_dur, s_coef, s_start, c->tr_arena.as<double>());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->tr_used = used;
+  for (size_t k = 0; k < n; k++) {
+    topay_ctx::TrackSlot& sl = c->tr_slots[puts[k].robot];
+    sl.d[puts[k].w] = dst[k];
+    sl.cap[puts[k].w] = cap[k];
+    sl.T[puts[k].w] = puts[k].T;
+  }
+  return TOPAY_OK;
+}
+
+static bool track_robot_ok(int robot) { return robot >= 0 && robot < TOPAY_TRACK_SLOTS; }
+static bool track_robots_distinct(int n, const int* robots) {   // (every robots[k] in range)
+  std::vector<char> seen(TOPAY_TRACK_SLOTS, 0);
+  for (int k = 0; k < n; k++) {
+    if (seen[robots[k]]) return false;
+    seen[robots[k]] = 1;
+  }
+  return true;
+}
+static const topay::TrackDesc* track_find(topay_ctx* c, int robot, int w) {
+  if (c->tr_slots.empty() || c->tr_slots[robot].d[w].N <= 0) return nullptr;
+  return &c->tr_slots[robot].d[w];
+}
+
+// The arguments every sweep / endpoint call checks: robot slots with an end_traj; map slots with distance fields.
+static topay_status track_check(topay_ctx* c, int n, const int* robots, const int* map_ids, const char* who) {
+  for (int k = 0; k < n; k++) {
+    if (!track_robot_ok(robots[k])) { set_err(std::string(who) + ": robot slot out of range"); return TOPAY_ERR_INVALID_ARG; }
+    if (map_ids) {
+      const int m = map_ids[k];
+      if (m < 0 || m >= TOPAY_MAX_MAPS) return TOPAY_ERR_INVALID_ARG;
+      if (!c->have_map[m] || !c->hmaps[m].esdf2d || !c->hmaps[m].esdf3d) { set_err(std::string(who) + ": map slot " + std::to_string(m) + " has no fields"); return TOPAY_ERR_NO_MAP; }
+    }
+  }
+  for (int k = 0; k < n; k++)
+    if (!track_find(c, robots[k], 0)) { set_err(std::string(who) + ": robot slot " + std::to_string(robots[k]) + " has no end_traj"); return TOPAY_ERR_NO_TRAJ; }
+  return TOPAY_OK;
+}
+
+static topay_status track_safe_impl(topay_ctx* c, int n, const int* robots, const int* map_ids, int* safe, int* first_hit, double* hit) {
+  const size_t N = (size_t)n;
+  std::vector<topay::TrackDesc> desc(N);
+  for (int k = 0; k < n; k++) desc[k] = *track_find(c, robots[k], 0);
+  topay::TrackDesc* d_desc; int *d_mid, *d_safe, *d_fh; double* d_hit;
+  auto lay = [&](Carver& k) {
+    d_hit = k.take<double>(2 * N); d_desc = k.take<topay::TrackDesc>(N); d_mid = k.take<int>(N); d_safe = k.take<int>(N); d_fh = k.take<int>(2 * N);
+  };
+  topay_status s;
+  if ((s = c->tr_io.carve(lay)) != TOPAY_OK) return s;
+  HIPCHK(h2d(c, d_desc, desc.data(), N));
+  HIPCHK(h2d(c, d_mid, map_ids, N));
+  if ((s = push_params(c)) != TOPAY_OK) return s;
+  topay::TrackSafeArgs A;
+  A.n = n; A.desc = d_desc; A.arena = c->tr_arena.as<double>(); A.map_id = d_mid; A.safe = d_safe; A.first_hit = d_fh; A.hit = d_hit;
+  HIPCHK(hipEventRecord(c->ev0, c->stream));
+  hipLaunchKernelGGL(topay::k_track_safe, dim3((unsigned)n), dim3(64), 0, c->stream, A, (const DevMap*)c->dmaps.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->ev1, c->stream));
+  if (safe) HIPCHK(d2h(c, safe, d_safe, N));
+  if (first_hit) HIPCHK(d2h(c, first_hit, d_fh, 2 * N));
+  if (hit) HIPCHK(d2h(c, hit, d_hit, 2 * N));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->tr_safe_ms = ms;
+  return TOPAY_OK;
+}
+
+static topay_status track_endpoints_impl(topay_ctx* c, int n, const int* robots, const double* t_replan, const double* t_begin, const double* global_goal,
+                                         double budget, double horizon, double* start, double* start_v, double* goal, int* goal_source) {
+  const size_t N = (size_t)n;
+  for (int k = 0; k < n; k++)
+    if (!(std::fabs(t_replan[k]) < 1.0e9 && t_begin[k] >= 0.0 && t_begin[k] < 1.0e9)) {   // (the walk along global_traj starts at t_begin)
+      set_err("topay_replan_inputs: the clocks must be finite, t_since_begin not negative");
+      return TOPAY_ERR_INVALID_ARG;
+    }
+  if (!(std::fabs(budget) < 1.0e9) || !(horizon >= 0.0)) return TOPAY_ERR_INVALID_ARG;
+  std::vector<topay::TrackDesc> de(N), dg(N);
+  for (int k = 0; k < n; k++) {
+    de[k] = *track_find(c, robots[k], 0);
+    const topay::TrackDesc* g = track_find(c, robots[k], 1);
+    if (g) dg[k] = *g;
+    else { dg[k].off = 0; dg[k].N = 0; dg[k].num = 0; }
+  }
+  topay::TrackDesc *d_de, *d_dg; double *d_tr, *d_tb, *d_gg, *d_st, *d_sv, *d_go; int* d_src;
+  auto lay = [&](Carver& k) {
+    d_tr = k.take<double>(N); d_tb = k.take<double>(N); d_gg = k.take<double>(10 * N);
+    d_st = k.take<double>(10 * N); d_sv = k.take<double>(10 * N); d_go = k.take<double>(10 * N);   // (contiguous: one copy back)
+    d_de = k.take<topay::TrackDesc>(N); d_dg = k.take<topay::TrackDesc>(N); d_src = k.take<int>(N);
+  };
+  topay_status s;
+  if ((s = c->tr_io.carve(lay)) != TOPAY_OK) return s;
+  HIPCHK(h2d(c, d_tr, t_replan, N));
+  HIPCHK(h2d(c, d_tb, t_begin, N));
+  HIPCHK(h2d(c, d_gg, global_goal, 10 * N));
+  HIPCHK(h2d(c, d_de, de.data(), N));
+  HIPCHK(h2d(c, d_dg, dg.data(), N));
+  topay::TrackEndArgs A;
+  A.n = n; A.end_desc = d_de; A.glob_desc = d_dg; A.arena = c->tr_arena.as<double>(); A.t_replan = d_tr; A.t_begin = d_tb; A.global_goal = d_gg;
+  A.budget = budget; A.horizon = horizon; A.start = d_st; A.start_v = d_sv; A.goal = d_go; A.goal_source = d_src;
+  hipLaunchKernelGGL(topay::k_track_endpoints, dim3((unsigned)n), dim3(64), 0, c->stream, A);
+  HIPCHK(hipGetLastError());
+  HIPCHK(d2h(c, start, d_st, 10 * N));
+  HIPCHK(d2h(c, start_v, d_sv, 10 * N));
+  HIPCHK(d2h(c, goal, d_go, 10 * N));
+  HIPCHK(d2h(c, goal_source, d_src, N));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return TOPAY_OK;
+}
+
+// Winners of the last planning call into the slots: device to device from the plan store.
+static topay_status track_commit_plan_impl(topay_ctx* c, int n, const int* robots, const int* call_idx, int which, int* committed) {
+  std::vector<double> hdur(std::max<size_t>(1, c->ps_pieces));
+  if (c->ps_pieces > 0) HIPCHK(d2h_sync(c, hdur.data(), c->ps_dur.as<double>(), c->ps_pieces));
+  std::vector<TrackPut> puts;
+  for (int k = 0; k < n; k++) {
+    const topay_ctx::PlanStored& e = c->ps_calls[call_idx[k]];
+    if (committed) committed[k] = 0;
+    if (e.n_pieces <= 0) continue;
+    TrackPut p;
+    p.robot = robots[k]; p.N = e.n_pieces; p.src_piece = e.piece0; p.src_start = 10ll * e.front0;
+    if (!track_duration_ok(&hdur[(size_t)e.piece0], e.n_pieces, p.T)) continue;
+    for (int w = 0; w < 2; w++)
+      if (which & (1 << w)) { p.w = w; puts.push_back(p); }
+    if (committed) committed[k] = 1;
+  }
+  return track_commit_impl(c, puts, c->ps_dur.as<double>(), c->ps_coef.as<double>(), c->ps_front.as<double>());
+}
+
+extern "C" {
+
+topay_status topay_track_set(topay_ctx* c, int robot, int which, const double* start3, int n_pieces, const double* durations, const double* coeffs) {
+  if (!c || !start3 || !durations || !coeffs) return TOPAY_ERR_INVALID_ARG;
+  if (!track_robot_ok(robot)) { set_err("topay_track_set: robot slot out of range"); return TOPAY_ERR_INVALID_ARG; }
+  if (which < 1 || which > 3) { set_err("topay_track_set: which must be 1 (end_traj), 2 (global_traj) or 3 (both)"); return TOPAY_ERR_INVALID_ARG; }
+  if (n_pieces < 1 || n_pieces > TOPAY_MAX_N) { set_err("topay_track_set: 1..170 pieces"); return TOPAY_ERR_INVALID_ARG; }
+  TrackPut p;
+  p.robot = robot; p.N = n_pieces; p.src_piece = 0; p.src_start = 0;
+  if (!track_duration_ok(durations, n_pieces, p.T)) { set_err("topay_track_set: the total duration must lie in (0, 1e4)"); return TOPAY_ERR_INVALID_ARG; }
+  HIPCHK(hipSetDevice(c->device));
+  const size_t N = (size_t)n_pieces;
+  double *d_dur, *d_coef, *d_start;
+  auto lay = [&](Carver& k) { d_dur = k.take<double>(N); d_coef = k.take<double>(N * kCoefPerPiece); d_start = k.take<double>(4); };
+  if (topay_status s = c->tr_stage.carve(lay); s != TOPAY_OK) return s;
+  HIPCHK(h2d(c, d_dur, durations, N));
+  HIPCHK(h2d(c, d_coef, coeffs, N * kCoefPerPiece));
+  HIPCHK(h2d(c, d_start, start3, 3));
+  std::vector<TrackPut> puts;
+  for (int w = 0; w < 2; w++)
+    if (which & (1 << w)) { p.w = w; puts.push_back(p); }
+  return track_commit_impl(c, puts, d_dur, d_coef, d_start);
+}
+
+topay_status topay_track_commit_plan(topay_ctx* c, int n, const int* robots, const int* call_idx, int which, int* committed) {
+  if (!c || n < 0 || (n > 0 && (!robots || !call_idx))) return TOPAY_ERR_INVALID_ARG;
+  if (which < 1 || which > 3) { set_err("topay_track_commit_plan: which must be 1, 2 or 3"); return TOPAY_ERR_INVALID_ARG; }
+  if (c->ps_calls.empty()) { set_err("topay_track_commit_plan: no planning call has been run"); return TOPAY_ERR_NO_TRAJ; }
+  for (int k = 0; k < n; k++) {
+    if (!track_robot_ok(robots[k])) { set_err("topay_track_commit_plan: robot slot out of range"); return TOPAY_ERR_INVALID_ARG; }
+    if (call_idx[k] < 0 || call_idx[k] >= (int)c->ps_calls.size()) return TOPAY_ERR_INVALID_ARG;
+  }
+  if (!track_robots_distinct(n, robots)) { set_err("topay_track_commit_plan: a robot slot is named twice"); return TOPAY_ERR_INVALID_ARG; }
+  HIPCHK(hipSetDevice(c->device));
+  return track_commit_plan_impl(c, n, robots, call_idx, which, committed);
+}
+
+topay_status topay_track_get(topay_ctx* c, int robot, int which, int cap_pieces, int* n_pieces, double* start3, double* durations, double* coeffs) {
+  if (!c || !n_pieces || cap_pieces < 0) return TOPAY_ERR_INVALID_ARG;
+  if (!track_robot_ok(robot)) { set_err("topay_track_get: robot slot out of range"); return TOPAY_ERR_INVALID_ARG; }
+  if (which < 1 || which > 2) { set_err("topay_track_get: which must be 1 (end_traj) or 2 (global_traj)"); return TOPAY_ERR_INVALID_ARG; }
+  const topay::TrackDesc* D = track_find(c, robot, which - 1);
+  *n_pieces = D ? D->N : 0;
+  if (!D) return TOPAY_OK;
+  if (!start3 && !durations && !coeffs) return TOPAY_OK;
+  if (D->N > cap_pieces) { set_err("topay_track_get: cap_pieces too small"); return TOPAY_ERR_INVALID_ARG; }
+  HIPCHK(hipSetDevice(c->device));
+  const int N = D->N, rows = 6 * N;
+  std::vector<double> h(4 + (size_t)N + (size_t)N * kCoefPerPiece);
+  HIPCHK(d2h_sync(c, h.data(), c->tr_arena.as<double>() + D->off, h.size()));
+  if (start3) memcpy(start3, h.data(), 24);
+  if (durations) memcpy(durations, h.data() + 4, (size_t)N * 8);
+  if (coeffs) {
+    const double* cm = h.data() + 4 + N;
+    for (int t = 0; t < N * kCoefPerPiece; t++) {
+      const int p = t / kCoefPerPiece, r = t - kCoefPerPiece * p, d = r / 6, kk = r - 6 * d;
+      coeffs[t] = cm[(size_t)d * rows + 6 * p + 5 - kk];
+    }
+  }
+  return TOPAY_OK;
+}
+
+topay_status topay_track_clear(topay_ctx* c, int robot) {
+  if (!c) return TOPAY_ERR_INVALID_ARG;
+  if (!track_robot_ok(robot)) { set_err("topay_track_clear: robot slot out of range"); return TOPAY_ERR_INVALID_ARG; }
+  if (!c->tr_slots.empty())
+    for (int w = 0; w < 2; w++) c->tr_slots[robot].d[w].N = 0;   // (the block stays the slot's: its next trajectory may reuse it)
+  return TOPAY_OK;
+}
+
+topay_status topay_track_safe(topay_ctx* c, int n, const int* robots, const int* map_ids, int* safe, int* first_hit, double* hit) {
+  if (!c || n <= 0 || !robots || !map_ids) return TOPAY_ERR_INVALID_ARG;
+  if (topay_status s = track_check(c, n, robots, map_ids, "topay_track_safe"); s != TOPAY_OK) return s;
+  HIPCHK(hipSetDevice(c->device));
+  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }
+  return track_safe_impl(c, n, robots, map_ids, safe, first_hit, hit);
+}
+
+topay_status topay_track_safe_ms(topay_ctx* c, double* ms) {
+  if (!c || !ms) return TOPAY_ERR_INVALID_ARG;
+  *ms = c->tr_safe_ms;
+  return TOPAY_OK;
+}
+
+topay_status topay_replan_inputs(topay_ctx* c, int n, const int* robots, const double* t_since_replan, const double* t_since_begin,
+                                 const double* global_goal, double planning_budget, double planning_horizon, double* start, double* start_v,
+                                 double* goal, int* goal_source) {
+  if (!c || n <= 0 || !robots || !t_since_replan || !t_since_begin || !global_goal || !start || !start_v || !goal || !goal_source) return TOPAY_ERR_INVALID_ARG;
+  if (topay_status s = track_check(c, n, robots, nullptr, "topay_replan_inputs"); s != TOPAY_OK) return s;
+  HIPCHK(hipSetDevice(c->device));
+  return track_endpoints_impl(c, n, robots, t_since_replan, t_since_begin, global_goal, planning_budget, planning_horizon, start, start_v, goal, goal_source);
+}
+
+topay_status topay_replan_calls(topay_ctx* c, int n, const int* robots, const int* map_ids, const double* t_since_replan, const double* t_since_begin,
+                                const double* now_xy, const double* global_goal, double replan_interval, double planning_budget,
+                                double planning_horizon, const topay_plan_params_t* params, unsigned long long first_call, int* status,
+                                double* endpoints, int* plan_result, int* plan_candidates) {
+  if (!c || n <= 0 || !robots || !map_ids || !t_since_replan || !t_since_begin || !global_goal || !status) return TOPAY_ERR_INVALID_ARG;
+  topay_status s;
+  if ((s = track_check(c, n, robots, map_ids, "topay_replan_calls")) != TOPAY_OK) return s;
+  if (!track_robots_distinct(n, robots)) { set_err("topay_replan_calls: a robot slot is named twice"); return TOPAY_ERR_INVALID_ARG; }
+  HIPCHK(hipSetDevice(c->device));
+  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }
+  const size_t N = (size_t)n;
+  // ---- 1. safety sweep (safeCallback) of every robot against its map of now
+  std::vector<int> safe(N);
+  if ((s = track_safe_impl(c, n, robots, map_ids, safe.data(), nullptr, nullptr)) != TOPAY_OK) return s;
+  // ---- 2. trigger (replanCallback:649, 705-706)
+  std::vector<int> trig;
+  for (int r = 0; r < n; r++) {
+    int* st = status + 4 * (size_t)r;
+    st[0] = 0; st[1] = safe[r]; st[2] = -1; st[3] = -1;
+    if (now_xy) {
+      const double dx = now_xy[2 * (size_t)r] - global_goal[10 * (size_t)r], dy = now_xy[2 * (size_t)r + 1] - global_goal[10 * (size_t)r + 1];
+      if (std::sqrt(dx * dx + dy * dy) < 0.5) { st[0] = 3; continue; }
+    }
+    if (t_since_replan[r] > replan_interval || !safe[r]) trig.push_back(r);
+  }
+  if (endpoints) std::fill(endpoints, endpoints + 30 * N, 0.0 / 0.0);
+  if (plan_result) std::fill(plan_result, plan_result + 8 * N, 0);
+  if (plan_candidates) std::fill(plan_candidates, plan_candidates + 64 * N, 0);
+  const int m = (int)trig.size();
+  if (m == 0) return TOPAY_OK;
+  // ---- 3. endpoints of the triggered robots
+  const size_t M = (size_t)m;
+  std::vector<int> rob(M), mid(M), src(M);
+  std::vector<double> tr(M), tb(M), gg(10 * M), st10(10 * M), sv10(10 * M), go10(10 * M);
+  std::vector<unsigned long long> call_no(M);
+  for (int j = 0; j < m; j++) {
+    const int r = trig[j];
+    rob[j] = robots[r]; mid[j] = map_ids[r]; tr[j] = t_since_replan[r]; tb[j] = t_since_begin[r];
+    memcpy(&gg[10 * (size_t)j], global_goal + 10 * (size_t)r, 80);
+    call_no[j] = first_call + (unsigned long long)r;   // the robot's position among the n given, not among the triggered
+  }
+  if ((s = track_endpoints_impl(c, m, rob.data(), tr.data(), tb.data(), gg.data(), planning_budget, planning_horizon, st10.data(), sv10.data(), go10.data(),
+                                src.data())) != TOPAY_OK)
+    return s;
+  // ---- 4. the planning call (planMomaParallel(local_start, local_goal, local_v))
+  std::vector<int> res(8 * M), cand(64 * M);
+  if ((s = plan_calls_impl(c, m, mid.data(), st10.data(), go10.data(), sv10.data(), params, 0, call_no.data(), res.data(), cand.data(), nullptr)) != TOPAY_OK) return s;
+  // ---- 5. winners become end_traj (planner.cpp:1010); global_traj stays
+  std::vector<int> idx(M), done(M);
+  std::iota(idx.begin(), idx.end(), 0);
+  if ((s = track_commit_plan_impl(c, m, rob.data(), idx.data(), 1, done.data())) != TOPAY_OK) return s;
+  for (int j = 0; j < m; j++) {
+    const int r = trig[j];
+    int* st = status + 4 * (size_t)r;
+    st[0] = done[j] ? 1 : 2; st[2] = j; st[3] = src[j];
+    if (endpoints) {
+      memcpy(endpoints + 30 * (size_t)r, &st10[10 * (size_t)j], 80);
+      memcpy(endpoints + 30 * (size_t)r + 10, &sv10[10 * (size_t)j], 80);
+      memcpy(endpoints + 30 * (size_t)r + 20, &go10[10 * (size_t)j], 80);
+    }
+    if (plan_result) memcpy(plan_result + 8 * (size_t)r, &res[8 * (size_t)j], 32);
+    if (plan_candidates) memcpy(plan_candidates + 64 * (size_t)r, &cand[64 * (size_t)j], 256);
+  }
+  return TOPAY_OK;
+}
+
+}  // extern "C"
