@@ -500,13 +500,15 @@ topay_status topay_topo_raw_paths(topay_ctx* ctx, int instance, int which, int c
  * outside this library.
  * The result of a call depends on nothing but the call: with c = first_call + p the roadmap draws with instance 2 c + t and
  * the search of candidate k with instance 16 c + 8 t + k, so a call may be batched with any others, in any order.
- *   result[p][8]             status (1 winner, 0 none, -3 too many candidates), try that decided the call (the winner's, else
+ *   result[p][8]             (columns TOPAY_PLAN_RES_*, TOPAY_PLAN_RES_LEN of them)
+ *                            status (1 winner, 0 none, -3 too many candidates), try that decided the call (the winner's, else
  *                            the last one attempted; -1 none), candidates of try 0, of try 1, winner k or -1, the winner's
  *                            pieces, roadmap status of the last try attempted, the winner's index in the batch of its try
  *                            or -1 (what the per-candidate getters take while that batch is the resident one; a
  *                            position in the batch, hence the one entry that depends on what the call is batched with)
- *   candidates[p][2][8][4]   (optional) stage, n_pieces, search status, solver stage-2 status; stage: 0 absent, 1 search
- *                            failed, 2 too many pieces, 3 solver failed, 4 gate failed, 5 interrupted, 6 counts
+ *   candidates[p][2][8][4]   (optional; per try TOPAY_PLAN_MAX_CAND entries of columns TOPAY_PLAN_CAND_*, TOPAY_PLAN_CAND_ROW_LEN
+ *                            ints per call) stage, n_pieces, search status, solver stage-2 status; stage (TOPAY_PLAN_STAGE_*):
+ *                            0 absent, 1 search failed, 2 too many pieces, 3 solver failed, 4 gate failed, 5 interrupted, 6 counts
  *   winner_cost_duration[p][2]  (optional) the winner's traj_cost and total duration (NaN without a winner)
  * The winners' durations, coefficients, knots and whole-body init paths are gathered on the device into a store of the
  * context (the second try reuses the workspace); it stays valid until the next topay_plan_calls or topay_destroy and is what
@@ -521,9 +523,18 @@ topay_status topay_topo_raw_paths(topay_ctx* ctx, int instance, int which, int c
  * most 1024 calls (a constant: results do not depend on it), so n calls need about min(n, 1024) x 2.2 MB + n x 3 x 0.4 MB.
  * topay_plan_test_chunk (test hook): another number of calls per front-end launch for this context, 0 = the constant.
  * topay_plan_stage_ms: device time of the last topay_plan_calls by stage, from pairs of HIP events around the stage's
- * launches on the context's stream (uploads, allocations and the host's waits between the stages are outside), 8 doubles:
- * roadmap, JPS, candidate table + dense paths, search (with its hand-off), init (hand-off + k_init), solve, gate + winner,
- * store gather. */
+ * launches on the context's stream (uploads, allocations and the host's waits between the stages are outside), 8 doubles
+ * (TOPAY_PLAN_MS_*): roadmap, JPS, candidate table + dense paths, search (with its hand-off), init (hand-off + k_init), solve,
+ * gate + winner, store gather. */
+#define TOPAY_PLAN_MAX_CAND 8   /* candidates per call and try: traj_opters.size(), planner.cpp:59 */
+enum { TOPAY_PLAN_RES_STATUS, TOPAY_PLAN_RES_TRY, TOPAY_PLAN_RES_CANDIDATES0, TOPAY_PLAN_RES_CANDIDATES1, TOPAY_PLAN_RES_WINNER,
+       TOPAY_PLAN_RES_N_PIECES, TOPAY_PLAN_RES_TOPO_STATUS, TOPAY_PLAN_RES_WINNER_BATCH_INDEX, TOPAY_PLAN_RES_LEN };
+enum { TOPAY_PLAN_CAND_STAGE, TOPAY_PLAN_CAND_N_PIECES, TOPAY_PLAN_CAND_SEARCH_STATUS, TOPAY_PLAN_CAND_SOLVER_STATUS, TOPAY_PLAN_CAND_LEN };
+#define TOPAY_PLAN_CAND_ROW_LEN (2 * TOPAY_PLAN_MAX_CAND * TOPAY_PLAN_CAND_LEN)   /* 64 */
+enum { TOPAY_PLAN_STAGE_ABSENT, TOPAY_PLAN_STAGE_SEARCH_FAILED, TOPAY_PLAN_STAGE_TOO_MANY_PIECES, TOPAY_PLAN_STAGE_SOLVER_FAILED,
+       TOPAY_PLAN_STAGE_GATE_FAILED, TOPAY_PLAN_STAGE_INTERRUPTED, TOPAY_PLAN_STAGE_COUNTS, TOPAY_PLAN_STAGE_LEN };
+enum { TOPAY_PLAN_MS_ROADMAP, TOPAY_PLAN_MS_JPS, TOPAY_PLAN_MS_DENSE, TOPAY_PLAN_MS_SEARCH, TOPAY_PLAN_MS_INIT, TOPAY_PLAN_MS_SOLVE,
+       TOPAY_PLAN_MS_GATE_WINNER, TOPAY_PLAN_MS_STORE, TOPAY_PLAN_MS_LEN };
 typedef struct {
   topay_topo_params_t topo;      /* topay_topo_default_params */
   topay_mcrrt_params_t mcrrt;    /* topay_mcrrt_default_params */
@@ -602,11 +613,12 @@ topay_status topay_replan_inputs(topay_ctx* ctx, int n, const int* robots, const
  * not depend on which others triggered; the winners committed as end_traj (global_traj stays).  The three 10-vectors per
  * triggered robot pass through the host between the stages; trajectories, fields and sweeps stay on the device.  A robot
  * slot may be named only once among the n (TOPAY_ERR_INVALID_ARG).
- *   status[k][4]     outcome (0 not due, 1 replanned and committed, 2 due but no winner: the old trajectory is kept, 3 arrived),
+ *   status[k][4]     (columns TOPAY_REPLAN_ST_*) outcome (0 not due, 1 replanned and committed, 2 due but no winner: the old trajectory is kept, 3 arrived),
  *                    safe, the robot's row in the plan store (what topay_plan_get_trajs takes) or -1, goal_source
  *   endpoints[k][30] (optional) start, start_v, goal of the triggered robots, NaN for the others
  *   plan_result[k][8], plan_candidates[k][2][8][4]  (optional) the tables of topay_plan_calls for the triggered robots, zeros
  *                    for the others */
+enum { TOPAY_REPLAN_ST_OUTCOME, TOPAY_REPLAN_ST_SAFE, TOPAY_REPLAN_ST_STORE_ROW, TOPAY_REPLAN_ST_GOAL_SOURCE, TOPAY_REPLAN_ST_LEN };
 topay_status topay_replan_calls(topay_ctx* ctx, int n, const int* robots, const int* map_ids, const double* t_since_replan,
                                 const double* t_since_begin, const double* now_xy, const double* global_goal, double replan_interval,
                                 double planning_budget, double planning_horizon, const topay_plan_params_t* params,

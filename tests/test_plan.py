@@ -7,6 +7,8 @@ same inputs, so every comparison is bit for bit: the result table, the per-candi
 their durations / coefficients / knots and the whole-body init paths.
 """
 import ctypes as C
+import os
+import re
 
 import numpy as np
 import pytest
@@ -245,6 +247,28 @@ def test_plan_calls_independent_of_batch(emu8):
     # a reversed PAIR is, through two calls that differ in their position only
     rev = _plan(opt, st[[5, 2]], en[[5, 2]], mid[[5, 2]], first_call=45)             # position 0 = call 5 -> number 45
     assert (rev[0][0, :7] == a[0][5, :7]).all() and (rev[1][0] == a[1][5]).all() and np.array_equal(rev[2][0], a[2][5], equal_nan=True)
+
+
+def test_api_names_follow_the_header():
+    """The three lists of names in api.py are the header's constants: each enum of include/topay.h that names the rows of a
+    table has, after its prefix and in lower case, the entries of the list, in the list's order and counted from 0, and its
+    last member -- the row length -- equals the list's length."""
+    text = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "topay.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)               # (the prose cites the names too)
+    value = {}
+    for body in re.findall(r"\benum\s*\{([^}]*)\}", text):
+        nxt = 0
+        for item in filter(None, (x.strip() for x in body.split(","))):
+            name, _, v = (x.strip() for x in item.partition("="))
+            nxt = (int(v, 0) if v else nxt) + 1
+            value[name] = nxt - 1
+    for keys, prefix in ((api.PLAN_RESULT_KEYS, "TOPAY_PLAN_RES_"), (api.PLAN_STAGES, "TOPAY_PLAN_STAGE_"), (api.PLAN_STAGE_MS_KEYS, "TOPAY_PLAN_MS_")):
+        mine = sorted((v, k[len(prefix):].lower()) for k, v in value.items() if k.startswith(prefix))
+        assert mine == list(enumerate(keys + ["len"])), (prefix, mine)
+    cols = sorted((v, k) for k, v in value.items() if k.startswith("TOPAY_PLAN_CAND_"))
+    assert [k for _, k in cols] == ["TOPAY_PLAN_CAND_" + x for x in ("STAGE", "N_PIECES", "SEARCH_STATUS", "SOLVER_STATUS", "LEN")] and [v for v, _ in cols] == list(range(5))
+    assert value["TOPAY_PLAN_RES_LEN"] == 8 and value["TOPAY_PLAN_MS_LEN"] == 8 and value["TOPAY_REPLAN_ST_LEN"] == 4
+    assert re.search(r"#define\s+TOPAY_PLAN_MAX_CAND\s+8\b", text) and re.search(r"#define\s+TOPAY_PLAN_CAND_ROW_LEN\s+\(2 \* TOPAY_PLAN_MAX_CAND \* TOPAY_PLAN_CAND_LEN\)", text)
 
 
 def test_plan_calls_refusals_and_edges(emu8):

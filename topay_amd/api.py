@@ -85,6 +85,8 @@ class PlanParams(C.Structure):
                 ("cancel_budget", C.c_int), ("max_candidates", C.c_int), ("critical_retry", C.c_int), ("reserved", C.c_int)]
 
 
+# The rows of plan_calls' tables by name: the enums TOPAY_PLAN_RES_*, TOPAY_PLAN_STAGE_* and TOPAY_PLAN_MS_* of include/topay.h
+# (tests/test_plan.py holds the lists to them).
 PLAN_RESULT_KEYS = ["status", "try", "candidates0", "candidates1", "winner", "n_pieces", "topo_status", "winner_batch_index"]
 PLAN_STAGES = ["absent", "search_failed", "too_many_pieces", "solver_failed", "gate_failed", "interrupted", "counts"]
 PLAN_STAGE_MS_KEYS = ["roadmap", "jps", "dense", "search", "init", "solve", "gate_winner", "store"]

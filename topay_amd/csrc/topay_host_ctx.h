@@ -1,5 +1,6 @@
-// Host side of the C-ABI, part 1: the error text, owning device buffers and the carver of packed blocks, the launch-class
-// table, the context, parameters, create and destroy.
+// Host side of the C-ABI, part 1: the error text, owning device buffers (grow-and-discard, grow-and-keep) and the carver of
+// packed blocks, the launch-class table, the state of the planning call by subject (PlanStore: the winners of the last call
+// and the layout of its buffers; PlanWork: the buffers of a try and the stage clock), the context, parameters, create and destroy.
 
 #pragma once
 
@@ -56,6 +57,21 @@ struct DevBuf {
     bytes = n;
     return TOPAY_OK;
   }
+  // ensure() that keeps the first `used` bytes when it has to grow (at least doubling): the append of the plan store, of a
+  // try's init paths and of the tracked trajectories' arena.  The copy runs on `stream` and is waited for.
+  topay_status ensure_keep(hipStream_t stream, size_t need, size_t used) {
+    if (need <= bytes) return TOPAY_OK;
+    DevBuf nb;
+    const topay_status s = nb.ensure(std::max(need, 2 * bytes));
+    if (s != TOPAY_OK) return s;
+    if (used > 0 && p) {
+      hipError_t e = hipMemcpyAsync(nb.p, p, used, hipMemcpyDeviceToDevice, stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(stream);
+      if (e != hipSuccess) { set_err(std::string("grow_keep: ") + hipGetErrorString(e)); return TOPAY_ERR_NO_DEVICE; }
+    }
+    *this = std::move(nb);
+    return TOPAY_OK;
+  }
   void release() {   // free early on purpose (a map slot being refilled, an arena, a workspace that is no longer needed)
     if (p) (void)hipFree(p);
     p = nullptr;
@@ -69,6 +85,9 @@ struct DevBuf {
     Carver at(p);
     if (s == TOPAY_OK) lay(at);
     return s;
+  }
+  template <typename B> topay_status place(B& block) {   // ... whose layout is the block's own lay(Carver&)
+    return carve([&](Carver& k) { block.lay(k); });
   }
 };
 
@@ -137,6 +156,76 @@ static std::vector<topay_ctx*> g_contexts;
 
 static topay_ctx* g_last_issued = nullptr;
 
+// The winners of the last topay_plan_calls, kept on the device until the next one.  Nothing outside this struct knows how they
+// lie in the four buffers: a winner's pieces are contiguous (1 duration and kCoefPerPiece coefficients per piece); its N + 1
+// knots follow those of the winners before it, as k_gather_results lays them out, so the winners stored so far take
+// 2 (pieces + winners) doubles; an init path holds 10 doubles per state.
+struct PlanStore {
+  struct Entry { int n_pieces = 0, piece0 = 0, knot0 = 0, front0 = 0, front_len = 0; };   // a call without a winner: zeros
+  struct Winners {   // of one try: call, index in the solved batch, and the running piece / init-path state offsets (W + 1 each)
+    std::vector<int> call, idx, piece_off{0}, front_off{0};
+    void add(int p, int b, int n_pieces, int front_len) {
+      call.push_back(p); idx.push_back(b);
+      piece_off.push_back(piece_off.back() + n_pieces); front_off.push_back(front_off.back() + front_len);
+    }
+    size_t size() const { return idx.size(); }
+  };
+  struct Dest { double *dur, *coef, *knots, *front; };   // where k_gather_results and k_plan_gather_front write a try's winners
+
+  void reset(int n_calls) { calls.assign((size_t)n_calls, Entry()); pieces = winners = states = 0; }
+  void clear() { calls.clear(); }   // a planning call that failed leaves nothing to read
+  bool empty() const { return calls.empty(); }   // no planning call has been run
+  bool has(int call) const { return call >= 0 && call < (int)calls.size(); }
+  const Entry& entry(int call) const { return calls[(size_t)call]; }
+  size_t n_pieces() const { return pieces; }
+  double* durations() { return dur.as<double>(); }
+  double* coeffs() { return coef.as<double>(); }
+  double* knots() { return kn.as<double>(); }
+  double* fronts() { return front.as<double>(); }
+  static long long front_double0(const Entry& e) { return 10ll * e.front0; }
+
+  // Room for W behind what is stored (the buffers grow keeping their contents), the entries of its calls, and the
+  // destinations of the gathers.  The counts move with appended(), once the gathers have succeeded.
+  topay_status reserve(hipStream_t stream, const Winners& W, Dest& d) {
+    const size_t np = (size_t)W.piece_off.back(), nw = W.size(), ns = (size_t)W.front_off.back();
+    for (size_t w = 0; w < nw; w++) {
+      Entry& e = calls[(size_t)W.call[w]];
+      e.n_pieces = W.piece_off[w + 1] - W.piece_off[w];
+      e.piece0 = (int)pieces + W.piece_off[w];
+      e.knot0 = (int)pieces + (int)winners + W.piece_off[w] + (int)w;
+      e.front0 = (int)states + W.front_off[w];
+      e.front_len = W.front_off[w + 1] - W.front_off[w];
+    }
+    topay_status s;
+    if ((s = dur.ensure_keep(stream, (pieces + np) * 8, pieces * 8)) != TOPAY_OK ||
+        (s = coef.ensure_keep(stream, (pieces + np) * kCoefPerPiece * 8, pieces * kCoefPerPiece * 8)) != TOPAY_OK ||
+        (s = kn.ensure_keep(stream, 2 * (pieces + winners + np + nw) * 8, 2 * (pieces + winners) * 8)) != TOPAY_OK ||
+        (s = front.ensure_keep(stream, (states + ns) * 80, states * 80)) != TOPAY_OK)
+      return s;
+    d.dur = durations() + pieces; d.coef = coeffs() + kCoefPerPiece * pieces; d.knots = knots() + 2 * (pieces + winners); d.front = fronts() + 10 * states;
+    return TOPAY_OK;
+  }
+  void appended(const Winners& W) { pieces += (size_t)W.piece_off.back(); winners += W.size(); states += (size_t)W.front_off.back(); }
+
+ private:
+  DevBuf dur, coef, kn, front;
+  std::vector<Entry> calls;   // per call of the last topay_plan_calls: where its winner lies
+  size_t pieces = 0, winners = 0, states = 0;
+};
+
+// What a try of topay_plan_calls works in (topay_host_plan.h states the blocks' layouts), and the stage clock (PlanClock).
+struct PlanWork {
+  DevBuf raw, jps_io;     // raw paths of the roadmap and of JPS in one buffer; the JPS launcher's own block
+  DevBuf io, tab, mc;     // per front-end launch: the calls, candidate table + dense paths, search inputs / outputs
+  DevBuf paths, bvel;     // the try's init paths and boundary velocities, appended launch by launch
+  DevBuf idx, win;        // index block of the hand-off to the solver, then of the store; winner block
+  std::vector<hipEvent_t> events;   // PlanClock: pairs of events, and per pair its stage and whether its end was recorded in this call
+  std::vector<int> event_stage;
+  std::vector<char> event_done;
+  double stage_ms[TOPAY_PLAN_MS_LEN] = {0};
+  int chunk = 0;   // topay_plan_test_chunk: calls per front-end launch, 0 = the constant
+};
+
 struct topay_ctx {
   int device = 0;
   topay_params_t hp;
@@ -199,17 +288,8 @@ struct topay_ctx {
   DevBuf tp_i, tp_d, tp_raw, tp_pts, tp_io;   // graphs, raw paths and point buffers of the last topay_topo_paths (topay_topo_graph / _raw_paths)
   int tp_n = 0, tp_pt_cap = 0, tp_nbuf = 0;
   topay_topo_params_t tp_P;
-  // topay_plan_calls: the raw paths, candidate table + dense paths, search inputs / results, the try's init paths and boundary
-  // velocities, index blocks of the hand-offs, and the winner store (durations, coefficients, knots, init paths)
-  DevBuf pl_raw, pl_jps_io, pl_io, pl_tab, pl_mc, pl_paths, pl_bvel, pl_sel, pl_win, ps_dur, ps_coef, ps_kn, ps_front;
-  struct PlanStored { int n_pieces = 0, piece0 = 0, knot0 = 0, front0 = 0, front_len = 0; };
-  std::vector<PlanStored> ps_calls;   // per call of the last topay_plan_calls: where its winner lies in the store
-  size_t ps_pieces = 0, ps_winners = 0, ps_states = 0;
-  std::vector<hipEvent_t> pl_events;
-  std::vector<int> pl_event_stage;
-  std::vector<char> pl_event_done;
-  int pl_chunk = 0;   // topay_plan_test_chunk: calls per front-end launch, 0 = the constant
-  double pl_stage_ms[8] = {0};
+  PlanWork plan;          // topay_plan_calls: what a try works in, the stage clock
+  PlanStore plan_store;   // ... and the winners of the last call
   // tracked trajectories (topay_host_track.h): the arena, the slots' descriptors (host: what the kernels are handed per call),
   // the upload block of topay_track_set and the inputs / outputs of the sweep and endpoint kernels
   DevBuf tr_arena, tr_stage, tr_io;
@@ -585,7 +665,7 @@ void topay_destroy(topay_ctx* c) {
     g_contexts.erase(std::remove(g_contexts.begin(), g_contexts.end(), c), g_contexts.end());
   }
   (void)hipSetDevice(c->device);
-  for (hipEvent_t e : c->pl_events) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->plan.events) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->world_ev)
     if (e) (void)hipEventDestroy(e);
   for (int k = 0; k < topay_ctx::NBUCKET; k++) {

@@ -1,4 +1,8 @@
-// Host side of the C-ABI, part 7: topay_plan_calls and the store of its winners.
+// Host side of the C-ABI, part 7: topay_plan_calls.  A call is up to two tries; a try (plan_try) is the stages of
+// include/topay.h in their order, one function each: per front-end launch the calls, roadmap + JPS, candidate table + dense
+// paths, search, hand-off to the solver; then once per try solve + gate + winner, and the winners into the store.  What passes
+// between the stages is a PlanTry; every packed device block is a struct that states its layout once.  The buffers and the
+// clock's events are the context's PlanWork, the winners go to its PlanStore (topay_host_ctx.h), which the getters below read.
 
 #pragma once
 
@@ -6,52 +10,40 @@
 // topay_plan_calls: Planner::planMomaParallel (planner.cpp:792-1061) with every hand-off on the device (topay_plan.h)
 // ---------------------------------------------------------------------------------------------------------------------
 // Calls per launch of the front-end stages (roadmap, JPS, dense paths, search).  The instance numbers of the draws are
-// those of the call, so results do not depend on it; it bounds the roadmap's 1.1 MB per query.
-#ifndef TOPAY_PLAN_CHUNK
-#define TOPAY_PLAN_CHUNK 1024
-#endif
-static const int kPlanChunk = TOPAY_PLAN_CHUNK;
+// those of the call, so results do not depend on it; it bounds the roadmap's 1.1 MB per query.  topay_plan_test_chunk sets another.
+static const int kPlanChunk = 1024;
 static const int kPlanDenseCap = 256;   // entries per dense path kept (the search takes at most 255 layers)
 static const int kPlanJpsCap = 512;     // points per JPS path kept
 
-// A device buffer that keeps its first `used` bytes when it has to grow.
-static topay_status grow_keep(topay_ctx* c, DevBuf& b, size_t need, size_t used) {
-  if (need <= b.bytes) return TOPAY_OK;
-  DevBuf nb;
-  topay_status s = nb.ensure(std::max(need, 2 * b.bytes));
-  if (s != TOPAY_OK) return s;
-  if (used > 0 && b.p) {
-    hipError_t e = memcpy_sync(c, nb.p, b.p, used, hipMemcpyDeviceToDevice);
-    if (e != hipSuccess) { set_err(std::string("grow_keep: ") + hipGetErrorString(e)); return TOPAY_ERR_NO_DEVICE; }
-  }
-  b = std::move(nb);
-  return TOPAY_OK;
-}
+// Rows of the caller's tables (include/topay.h: TOPAY_PLAN_RES_*, TOPAY_PLAN_CAND_*).
+static int* result_row(int* result, int p) { return result + TOPAY_PLAN_RES_LEN * (size_t)p; }
+static int* cand_row(int* cand, int p, int t, int k) { return cand + (((size_t)p * 2 + t) * TOPAY_PLAN_MAX_CAND + k) * TOPAY_PLAN_CAND_LEN; }
 
-// Device time of one stage: a pair of events around its launches on the context's stream, read once the call has finished.
-// Only pairs whose end has been recorded in THIS call are read (an error return between begin and end leaves none behind).
+// Device time of one stage (TOPAY_PLAN_MS_*): a pair of events around its launches on the context's stream, read once the call
+// has finished.  Only pairs whose end has been recorded in THIS call are read (an error return between begin and end leaves none behind).
 struct PlanClock {
   topay_ctx* c;
+  PlanWork& w;
   size_t used = 0;
-  explicit PlanClock(topay_ctx* c_) : c(c_) {}
+  explicit PlanClock(topay_ctx* c_) : c(c_), w(c_->plan) {}
   int reserve(int stage) {   // a pair for a launcher that records the events itself, around its kernels only; then done(id)
-    if (used + 2 > c->pl_events.size()) {
+    if (used + 2 > w.events.size()) {
       hipEvent_t a = nullptr, b = nullptr;
       if (hipEventCreate(&a) != hipSuccess) return -1;
       if (hipEventCreate(&b) != hipSuccess) { (void)hipEventDestroy(a); return -1; }
-      c->pl_events.push_back(a);
-      c->pl_events.push_back(b);
+      w.events.push_back(a);
+      w.events.push_back(b);
     }
-    c->pl_event_stage.resize(c->pl_events.size() / 2);
-    c->pl_event_done.resize(c->pl_events.size() / 2);
+    w.event_stage.resize(w.events.size() / 2);
+    w.event_done.resize(w.events.size() / 2);
     const int id = (int)(used / 2);
-    c->pl_event_stage[id] = stage;
-    c->pl_event_done[id] = 0;
+    w.event_stage[id] = stage;
+    w.event_done[id] = 0;
     used += 2;
     return id;
   }
-  hipEvent_t ev(int id, int which) { return id < 0 ? nullptr : c->pl_events[2 * (size_t)id + which]; }
-  void done(int id) { if (id >= 0) c->pl_event_done[id] = 1; }
+  hipEvent_t ev(int id, int which) { return id < 0 ? nullptr : w.events[2 * (size_t)id + which]; }
+  void done(int id) { if (id >= 0) w.event_done[id] = 1; }
   int begin(int stage) {
     const int id = reserve(stage);
     if (id >= 0) (void)hipEventRecord(ev(id, 0), c->stream);
@@ -64,266 +56,355 @@ struct PlanClock {
     (void)hipStreamSynchronize(c->stream);
     for (size_t i = 0; i + 1 < used; i += 2) {
       float ms = 0.f;
-      if (c->pl_event_done[i / 2] && hipEventElapsedTime(&ms, c->pl_events[i], c->pl_events[i + 1]) == hipSuccess)
-        c->pl_stage_ms[c->pl_event_stage[i / 2]] += ms;
+      if (w.event_done[i / 2] && hipEventElapsedTime(&ms, w.events[i], w.events[i + 1]) == hipSuccess) w.stage_ms[w.event_stage[i / 2]] += ms;
     }
   }
 };
 
-struct PlanTry {   // the survivors of one try, over all front-end launches: the batch that is solved
+// The planning call as plan_calls_impl checked it: the caller's arrays and tables.  Call p has the number call_nos[p], or
+// first_call + p when call_nos is null (the replanning cycle numbers its calls itself).
+struct PlanReq {
+  topay_plan_params_t P;
+  std::vector<int> mids;
+  const double *start, *end, *start_v; unsigned long long first_call; const unsigned long long* call_nos;
+  int *result, *cand;   // n x TOPAY_PLAN_RES_LEN; n x TOPAY_PLAN_CAND_ROW_LEN or null
+  double* wcd;          // n x 2 or null
+  unsigned long long number(int p) const { return call_nos ? call_nos[p] : first_call + (unsigned long long)p; }
+};
+
+// ---- the packed device blocks of a try
+struct PlanCallBlock {   // the launch's calls as the caller gave them: PlanWork::io
+  size_t n = 0;
+  double *start, *end, *start_v; unsigned long long* call_no; int* mid;   // (the states: 10 per call)
+  void lay(Carver& k) {
+    start = k.take<double>(10 * n); end = k.take<double>(10 * n); start_v = k.take<double>(10 * n);
+    call_no = k.take<unsigned long long>(n); mid = k.take<int>(n);
+  }
+};
+struct PlanCandBlock {   // candidate table (slot = call x TOPAY_PLAN_MAX_CAND + k) and the dense paths of its slots: PlanWork::tab
+  size_t n = 0;          // calls
+  double *syaw, *eyaw, *dense; long long* raw_off; int *ncand, *raw_len, *dense_len;
+  void lay(Carver& k) {
+    const size_t ns = n * TOPAY_PLAN_MAX_CAND;
+    syaw = k.take<double>(ns); eyaw = k.take<double>(ns); raw_off = k.take<long long>(ns); dense = k.take<double>(ns * kPlanDenseCap * 4);
+    ncand = k.take<int>(n); raw_len = k.take<int>(ns); dense_len = k.take<int>(ns);
+  }
+};
+struct PlanSearchBlock {   // per search instance: the inputs k_plan_pack_search writes for k_mcrrt, and its outputs: PlanWork::mc
+  size_t n = 0;
+  int layer_cap = 2;       // states per whole-body path kept
+  long long* off; unsigned long long* inst; double *start, *end, *wb, *cmax; int *slot, *len, *mid, *wb_len, *stats;
+  void lay(Carver& k) {
+    off = k.take<long long>(n); inst = k.take<unsigned long long>(n);
+    start = k.take<double>(10 * n); end = k.take<double>(10 * n); wb = k.take<double>(n * layer_cap * 10); cmax = k.take<double>(n);
+    slot = k.take<int>(n); len = k.take<int>(n); mid = k.take<int>(n); wb_len = k.take<int>(n); stats = k.take<int>(8 * n);
+  }
+};
+struct PlanHandoffBlock {   // per survivor of the launch: first state of its init path, its search instance, its call in the launch: PlanWork::idx
+  size_t n = 0;
+  long long* path_off; int *src, *src_call;
+  void lay(Carver& k) { path_off = k.take<long long>(n); src = k.take<int>(n); src_call = k.take<int>(n); }
+};
+struct PlanWinnerBlock {   // per call of the solved batch its candidates' range, winner, cost and duration; per candidate its stage: PlanWork::win
+  size_t calls = 0, batch = 0;
+  double* wcd; int *first, *count, *win, *stage;
+  void lay(Carver& k) {
+    wcd = k.take<double>(2 * calls);
+    first = k.take<int>(calls); count = k.take<int>(calls); win = k.take<int>(calls); stage = k.take<int>(batch);
+  }
+};
+struct PlanStoreIdxBlock {   // per winner its index in the batch, and the running piece / state offsets (PlanStore::Winners): PlanWork::idx
+  size_t n = 0;
+  int *idx, *piece_off, *front_off;
+  void lay(Carver& k) { idx = k.take<int>(n); piece_off = k.take<int>(n + 1); front_off = k.take<int>(n + 1); }
+};
+
+// One try (t = 0 plain, 1 critical) for the calls `act`: what passes between its stages.
+struct PlanTry {
+  topay_ctx* c; PlanReq& R; const int t; const std::vector<int>& act; PlanClock& clk;
+  // the survivors over all front-end launches: the batch that is solved
   std::vector<int> call, k, len, mid;
   std::vector<long long> off{0};
+  // the front-end launch under way: calls act[a0 .. a0 + nc); the host arrays live until the launch's last wait
+  size_t a0 = 0, topo_pts = 0;
+  int nc = 0, cap_points = 2;
+  std::vector<double> sxy, exy, st10, en10, sv10;
+  std::vector<int> cmid, crit;
+  std::vector<unsigned long long> inst, call_no;
+  TopoDev td; JpsDev jd;   // where the roadmap and JPS left their results
+  std::vector<int> sel;    // the candidate slots that are searched
+  PlanCallBlock in; PlanCandBlock tab; PlanSearchBlock mc;
+  int p_of(int q) const { return act[a0 + (size_t)q]; }
 };
 
-// One try (t = 0 plain, 1 critical) for the calls `act`: front-end in launches of kPlanChunk calls, one solve, winners
-// into the store.  Fills the calls' rows of result / cand (n x 2 x 8 x 4) / wcd.  Call p has the number call_nos[p], or
-// first_call + p when call_nos is null (the replanning cycle numbers its calls itself).
-static topay_status plan_try(topay_ctx* c, int t, const std::vector<int>& act, const std::vector<int>& mids, const double* start, const double* end,
-                             const double* start_v, const topay_plan_params_t& P, unsigned long long first_call, const unsigned long long* call_nos, int* result,
-                             int* cand, double* wcd, PlanClock& clk) {
-  topay_status s;
-  PlanTry T;
-  const int cap_paths = P.topo.reserve_num;
-  const size_t chunk = (size_t)(c->pl_chunk > 0 ? c->pl_chunk : kPlanChunk);
-  for (size_t a0 = 0; a0 < act.size(); a0 += chunk) {
-    const int nc = (int)std::min<size_t>(chunk, act.size() - a0);
-    const size_t NC = (size_t)nc, NS = NC * TOPAY_PLAN_MAX_CAND;
-    // ---- the launch's calls: inputs of the caller, gathered on the host
-    std::vector<double> sxy(2 * NC), exy(2 * NC), st10(10 * NC), en10(10 * NC), sv10(10 * NC, 0.0);
-    std::vector<int> cmid(NC), crit(NC, t);
-    std::vector<unsigned long long> inst(NC), call_no(NC);
-    int cap_points = 2;
-    for (int q = 0; q < nc; q++) {
-      const int p = act[a0 + q];
-      memcpy(&st10[10 * (size_t)q], start + 10 * (size_t)p, 80);
-      memcpy(&en10[10 * (size_t)q], end + 10 * (size_t)p, 80);
-      if (start_v) memcpy(&sv10[10 * (size_t)q], start_v + 10 * (size_t)p, 80);
-      sxy[2 * (size_t)q] = start[10 * (size_t)p]; sxy[2 * (size_t)q + 1] = start[10 * (size_t)p + 1];
-      exy[2 * (size_t)q] = end[10 * (size_t)p]; exy[2 * (size_t)q + 1] = end[10 * (size_t)p + 1];
-      cmid[q] = mids[p];
-      call_no[q] = call_nos ? call_nos[p] : first_call + (unsigned long long)p;
-      inst[q] = 2ull * call_no[q] + (unsigned long long)t;
-      const DevMap& m = c->hmaps[cmid[q]];
-      cap_points = std::max(cap_points, topo_pt_cap(m.dims[0], m.dims[1]));   // no selected path has more points than its map's cap
-    }
-    const size_t topo_pts = NC * (size_t)cap_paths * cap_points;
-    if ((s = c->pl_raw.ensure((topo_pts + NC * kPlanJpsCap) * 16)) != TOPAY_OK) return s;
-    // calls: start | end | start_v (10 each), call numbers, map slots
-    double *d_st, *d_en, *d_sv; unsigned long long* d_callno; int* d_cmid;
-    auto lay_io = [&](Carver& k) {
-      d_st = k.take<double>(10 * NC); d_en = k.take<double>(10 * NC); d_sv = k.take<double>(10 * NC);
-      d_callno = k.take<unsigned long long>(NC); d_cmid = k.take<int>(NC);
-    };
-    if ((s = c->pl_io.carve(lay_io)) != TOPAY_OK) return s;
-    HIPCHK(h2d(c, d_st, st10.data(), 10 * NC));
-    HIPCHK(h2d(c, d_en, en10.data(), 10 * NC));
-    HIPCHK(h2d(c, d_sv, sv10.data(), 10 * NC));
-    HIPCHK(h2d(c, d_callno, call_no.data(), NC));
-    HIPCHK(h2d(c, d_cmid, cmid.data(), NC));
-    // ---- roadmap, JPS
-    TopoDev td;
-    int id = clk.reserve(0);   // (the launchers record around their kernels: uploads, allocations and waits stay outside)
-    s = topo_impl(c, nc, cmid.data(), sxy.data(), exy.data(), crit.data(), &P.topo, 0, inst.data(), cap_paths, cap_points, c->pl_raw.as<double>(), false, &td,
-                  clk.ev(id, 0), clk.ev(id, 1));
-    if (s != TOPAY_OK) return s;
-    clk.done(id);
-    JpsDev jd;
-    jd.len = nullptr;
-    if (t == 0) {
-      id = clk.reserve(1);
-      s = jps_impl(c, nc, cmid.data(), sxy.data(), exy.data(), c->hp.chassis_colli_radius + P.jps_margin, kPlanJpsCap, c->pl_jps_io,
-                   c->pl_raw.as<double>() + 2 * topo_pts, &jd, clk.ev(id, 0), clk.ev(id, 1));
-      if (s != TOPAY_OK) return s;
-      clk.done(id);
-    }
-    // ---- candidate table, dense paths
-    double *d_syaw, *d_eyaw, *d_dense; long long* d_rawoff; int *d_ncand, *d_rawlen, *d_denselen;
-    auto lay_tab = [&](Carver& k) {
-      d_syaw = k.take<double>(NS); d_eyaw = k.take<double>(NS); d_rawoff = k.take<long long>(NS); d_dense = k.take<double>(NS * kPlanDenseCap * 4);
-      d_ncand = k.take<int>(NC); d_rawlen = k.take<int>(NS); d_denselen = k.take<int>(NS);
-    };
-    if ((s = c->pl_tab.carve(lay_tab)) != TOPAY_OK) return s;
-    topay::PlanCandArgs A;
-    A.n = nc; A.cap_paths = cap_paths; A.cap_points = cap_points; A.jps_cap = kPlanJpsCap; A.max_cand = P.max_candidates;
-    A.jps_base = (long long)topo_pts;
-    A.topo_np = td.n_paths; A.topo_len = td.path_len; A.jps_len = jd.len; A.start = d_st; A.end = d_en;
-    A.ncand = d_ncand; A.raw_off = d_rawoff; A.raw_len = d_rawlen; A.syaw = d_syaw; A.eyaw = d_eyaw;
-    id = clk.begin(2);
-    hipLaunchKernelGGL(topay::k_plan_candidates, dim3((nc + 63) / 64), dim3(64), 0, c->stream, A);
-    HIPCHK(hipGetLastError());
-    if ((s = dense_launch(c, (int)NS, c->pl_raw.as<double>(), d_rawoff, d_rawlen, P.dense_step, d_syaw, d_eyaw, c->hp.max_v, c->hp.max_w, kPlanDenseCap,
-                          d_dense, d_denselen)) != TOPAY_OK)
-      return s;
-    clk.end(id);
-    std::vector<int> ncand(NC), dlen(NS), tstat(NC * 8);
-    HIPCHK(d2h(c, ncand.data(), d_ncand, NC));
-    HIPCHK(d2h(c, dlen.data(), d_denselen, NS));
-    HIPCHK(d2h(c, tstat.data(), td.stats, NC * 8));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    std::vector<int> sel;
-    int layer_cap = 2;
-    for (int q = 0; q < nc; q++) {
-      const int p = act[a0 + q];
-      int* r = result + 8 * (size_t)p;
-      r[1] = t;
-      r[2 + t] = std::abs(ncand[q]);
-      r[6] = tstat[8 * (size_t)q];
-      if (ncand[q] < 0) { r[0] = -3; continue; }
-      for (int k = 0; k < ncand[q]; k++) {
-        const int sl = q * TOPAY_PLAN_MAX_CAND + k;
-        sel.push_back(sl);
-        layer_cap = std::max(layer_cap, std::min(dlen[sl], 255));
-        if (cand) cand[(((size_t)p * 2 + t) * 8 + k) * 4] = topay::PLAN_SEARCH_FAILED;   // until it gets further
-      }
-    }
-    const int ni = (int)sel.size();
-    if (ni == 0) continue;
-    // ---- the search: hand-off kernel, k_mcrrt
-    const size_t NI = (size_t)ni;
-    long long* d_off; unsigned long long* d_inst; double *d_s, *d_e, *d_wb, *d_cmax; int *d_sel, *d_len, *d_mid, *d_wlen, *d_mstat;
-    auto lay_mc = [&](Carver& k) {
-      d_off = k.take<long long>(NI); d_inst = k.take<unsigned long long>(NI);
-      d_s = k.take<double>(10 * NI); d_e = k.take<double>(10 * NI); d_wb = k.take<double>(NI * layer_cap * 10); d_cmax = k.take<double>(NI);
-      d_sel = k.take<int>(NI); d_len = k.take<int>(NI); d_mid = k.take<int>(NI); d_wlen = k.take<int>(NI); d_mstat = k.take<int>(8 * NI);
-    };
-    if ((s = c->pl_mc.carve(lay_mc)) != TOPAY_OK) return s;
-    HIPCHK(h2d(c, d_sel, sel.data(), NI));
-    id = clk.begin(3);
-    hipLaunchKernelGGL(topay::k_plan_pack_search, dim3((ni + 63) / 64), dim3(64), 0, c->stream, ni, (const int*)d_sel, kPlanDenseCap, (const int*)d_denselen,
-                       (const double*)d_st, (const double*)d_en, (const int*)d_cmid, (const unsigned long long*)d_callno, t, d_off, d_len, d_s, d_e, d_mid,
-                       d_inst);
-    HIPCHK(hipGetLastError());
-    McIo io;
-    io.off = d_off; io.len = d_len; io.car = d_dense; io.start = d_s; io.end = d_e; io.mid = d_mid; io.inst = d_inst;
-    io.wb_len = d_wlen; io.wb = d_wb; io.stats = d_mstat; io.cmax = d_cmax;
-    if ((s = mcrrt_launch(c, ni, P.mcrrt, 0, layer_cap, io)) != TOPAY_OK) return s;
-    clk.end(id);
-    std::vector<int> wlen(NI), mstat(NI * 8);
-    HIPCHK(d2h(c, wlen.data(), d_wlen, NI));
-    HIPCHK(d2h(c, mstat.data(), d_mstat, 8 * NI));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    std::vector<int> src, src_call;
-    std::vector<long long> poff;
-    const int b0 = (int)T.call.size();
-    for (int i = 0; i < ni; i++) {
-      const int q = sel[i] / TOPAY_PLAN_MAX_CAND, k = sel[i] % TOPAY_PLAN_MAX_CAND, p = act[a0 + q];
-      if (cand) cand[(((size_t)p * 2 + t) * 8 + k) * 4 + 2] = mstat[8 * (size_t)i];
-      if (mstat[8 * (size_t)i] != 1 || wlen[i] < 2) continue;
-      src.push_back(i);
-      src_call.push_back(q);
-      poff.push_back(T.off.back());
-      T.call.push_back(p); T.k.push_back(k); T.len.push_back(wlen[i]); T.mid.push_back(mids[p]);
-      T.off.push_back(T.off.back() + wlen[i]);
-    }
-    const int nsv = (int)src.size();
-    if (nsv == 0) continue;
-    // ---- hand-off to the solver: ragged init paths and boundary velocities of the try, appended launch by launch
-    if ((s = grow_keep(c, c->pl_paths, (size_t)T.off.back() * 80, (size_t)poff[0] * 80)) != TOPAY_OK) return s;
-    if ((s = grow_keep(c, c->pl_bvel, T.call.size() * 160, (size_t)b0 * 160)) != TOPAY_OK) return s;
-    long long* d_poff; int *d_src, *d_srccall;
-    auto lay_sel = [&](Carver& k) { d_poff = k.take<long long>((size_t)nsv); d_src = k.take<int>((size_t)nsv); d_srccall = k.take<int>((size_t)nsv); };
-    if ((s = c->pl_sel.carve(lay_sel)) != TOPAY_OK) return s;
-    HIPCHK(h2d(c, d_poff, poff.data(), (size_t)nsv));
-    HIPCHK(h2d(c, d_src, src.data(), (size_t)nsv));
-    HIPCHK(h2d(c, d_srccall, src_call.data(), (size_t)nsv));
-    id = clk.begin(4);
-    hipLaunchKernelGGL(topay::k_plan_pack_solver, dim3((unsigned)nsv), dim3(64), 0, c->stream, nsv, (const int*)d_src, (const int*)d_srccall, layer_cap,
-                       (const int*)d_wlen, (const double*)d_wb, (const long long*)d_poff, (const double*)d_sv, b0, c->pl_paths.as<double>(),
-                       c->pl_bvel.as<double>());
-    HIPCHK(hipGetLastError());
-    clk.end(id);
-    HIPCHK(hipStreamSynchronize(c->stream));   // (the launch's buffers are reused by the next one)
+// ---- the launch's calls: inputs of the caller, gathered on the host
+static topay_status plan_gather_calls(PlanTry& T) {
+  topay_ctx* c = T.c;
+  const PlanReq& R = T.R;
+  const size_t NC = (size_t)T.nc;
+  T.sxy.assign(2 * NC, 0.0); T.exy.assign(2 * NC, 0.0); T.st10.assign(10 * NC, 0.0); T.en10.assign(10 * NC, 0.0); T.sv10.assign(10 * NC, 0.0);
+  T.cmid.assign(NC, 0); T.crit.assign(NC, T.t); T.inst.assign(NC, 0); T.call_no.assign(NC, 0);
+  T.cap_points = 2;
+  for (int q = 0; q < T.nc; q++) {
+    const int p = T.p_of(q);
+    const size_t q10 = 10 * (size_t)q, p10 = 10 * (size_t)p;
+    memcpy(&T.st10[q10], R.start + p10, 80);
+    memcpy(&T.en10[q10], R.end + p10, 80);
+    if (R.start_v) memcpy(&T.sv10[q10], R.start_v + p10, 80);
+    T.sxy[2 * (size_t)q] = R.start[p10]; T.sxy[2 * (size_t)q + 1] = R.start[p10 + 1];
+    T.exy[2 * (size_t)q] = R.end[p10]; T.exy[2 * (size_t)q + 1] = R.end[p10 + 1];
+    T.cmid[q] = R.mids[p];
+    T.call_no[q] = R.number(p);
+    T.inst[q] = 2ull * T.call_no[q] + (unsigned long long)T.t;
+    const DevMap& m = c->hmaps[T.cmid[q]];
+    T.cap_points = std::max(T.cap_points, topo_pt_cap(m.dims[0], m.dims[1]));   // no selected path has more points than its map's cap
   }
-  const int B = (int)T.call.size();
-  if (B == 0) return TOPAY_OK;   // no candidate of any call survived to the solve: the try fails for all of them
-  // ---- one batch: init, groups, solve, gate
-  int id = clk.begin(4);
-  s = set_init_traj_impl(c, B, T.len.data(), c->pl_paths.as<double>(), c->pl_bvel.as<double>(), nullptr, T.mid.data(), hipMemcpyDeviceToDevice);
-  clk.end(id);
+  T.topo_pts = NC * (size_t)R.P.topo.reserve_num * T.cap_points;
+  topay_status s;
+  if ((s = c->plan.raw.ensure((T.topo_pts + NC * kPlanJpsCap) * 16)) != TOPAY_OK) return s;
+  T.in.n = NC;
+  if ((s = c->plan.io.place(T.in)) != TOPAY_OK) return s;
+  HIPCHK(h2d(c, T.in.start, T.st10.data(), 10 * NC));
+  HIPCHK(h2d(c, T.in.end, T.en10.data(), 10 * NC));
+  HIPCHK(h2d(c, T.in.start_v, T.sv10.data(), 10 * NC));
+  HIPCHK(h2d(c, T.in.call_no, T.call_no.data(), NC));
+  HIPCHK(h2d(c, T.in.mid, T.cmid.data(), NC));
+  return TOPAY_OK;
+}
+
+// ---- roadmap, JPS (the launchers record around their kernels: uploads, allocations and waits stay outside)
+static topay_status plan_roadmap_jps(PlanTry& T) {
+  topay_ctx* c = T.c;
+  const topay_plan_params_t& P = T.R.P;
+  double* raw = c->plan.raw.as<double>();
+  int ev = T.clk.reserve(TOPAY_PLAN_MS_ROADMAP);
+  topay_status s = topo_impl(c, T.nc, T.cmid.data(), T.sxy.data(), T.exy.data(), T.crit.data(), &P.topo, 0, T.inst.data(), P.topo.reserve_num, T.cap_points, raw,
+                             false, &T.td, T.clk.ev(ev, 0), T.clk.ev(ev, 1));
+  if (s != TOPAY_OK) return s;
+  T.clk.done(ev);
+  T.jd.len = nullptr;
+  if (T.t == 0) {   // (the second try has no JPS candidate)
+    ev = T.clk.reserve(TOPAY_PLAN_MS_JPS);
+    s = jps_impl(c, T.nc, T.cmid.data(), T.sxy.data(), T.exy.data(), c->hp.chassis_colli_radius + P.jps_margin, kPlanJpsCap, c->plan.jps_io, raw + 2 * T.topo_pts,
+                 &T.jd, T.clk.ev(ev, 0), T.clk.ev(ev, 1));
+    if (s != TOPAY_OK) return s;
+    T.clk.done(ev);
+  }
+  return TOPAY_OK;
+}
+
+// ---- candidate table, dense paths; the calls' counts into `result`, the slots that go on into T.sel
+static topay_status plan_candidates(PlanTry& T) {
+  topay_ctx* c = T.c;
+  const PlanReq& R = T.R;
+  const size_t NC = (size_t)T.nc, NS = NC * TOPAY_PLAN_MAX_CAND;
+  topay_status s;
+  T.tab.n = NC;
+  if ((s = c->plan.tab.place(T.tab)) != TOPAY_OK) return s;
+  topay::PlanCandArgs A;
+  A.n = T.nc; A.cap_paths = R.P.topo.reserve_num; A.cap_points = T.cap_points; A.jps_cap = kPlanJpsCap; A.max_cand = R.P.max_candidates;
+  A.jps_base = (long long)T.topo_pts;
+  A.topo_np = T.td.n_paths; A.topo_len = T.td.path_len; A.jps_len = T.jd.len; A.start = T.in.start; A.end = T.in.end;
+  A.ncand = T.tab.ncand; A.raw_off = T.tab.raw_off; A.raw_len = T.tab.raw_len; A.syaw = T.tab.syaw; A.eyaw = T.tab.eyaw;
+  const int ev = T.clk.begin(TOPAY_PLAN_MS_DENSE);
+  hipLaunchKernelGGL(topay::k_plan_candidates, dim3((T.nc + 63) / 64), dim3(64), 0, c->stream, A);
+  HIPCHK(hipGetLastError());
+  if ((s = dense_launch(c, (int)NS, c->plan.raw.as<double>(), T.tab.raw_off, T.tab.raw_len, R.P.dense_step, T.tab.syaw, T.tab.eyaw, c->hp.max_v, c->hp.max_w,
+                        kPlanDenseCap, T.tab.dense, T.tab.dense_len)) != TOPAY_OK)
+    return s;
+  T.clk.end(ev);
+  std::vector<int> ncand(NC), dlen(NS), tstat(NC * 8);
+  HIPCHK(d2h(c, ncand.data(), T.tab.ncand, NC));
+  HIPCHK(d2h(c, dlen.data(), T.tab.dense_len, NS));
+  HIPCHK(d2h(c, tstat.data(), T.td.stats, NC * 8));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  T.sel.clear();
+  T.mc.layer_cap = 2;
+  for (int q = 0; q < T.nc; q++) {
+    const int p = T.p_of(q);
+    int* r = result_row(R.result, p);
+    r[TOPAY_PLAN_RES_TRY] = T.t;
+    r[TOPAY_PLAN_RES_CANDIDATES0 + T.t] = std::abs(ncand[q]);
+    r[TOPAY_PLAN_RES_TOPO_STATUS] = tstat[8 * (size_t)q];
+    if (ncand[q] < 0) { r[TOPAY_PLAN_RES_STATUS] = -3; continue; }
+    for (int k = 0; k < ncand[q]; k++) {
+      const int sl = q * TOPAY_PLAN_MAX_CAND + k;
+      T.sel.push_back(sl);
+      T.mc.layer_cap = std::max(T.mc.layer_cap, std::min(dlen[sl], 255));
+      if (R.cand) cand_row(R.cand, p, T.t, k)[TOPAY_PLAN_CAND_STAGE] = TOPAY_PLAN_STAGE_SEARCH_FAILED;   // until it gets further
+    }
+  }
+  return TOPAY_OK;
+}
+
+// ---- the search: hand-off kernel, k_mcrrt; the lengths and statuses of the whole-body paths come back
+static topay_status plan_search(PlanTry& T, std::vector<int>& wlen, std::vector<int>& mstat) {
+  topay_ctx* c = T.c;
+  const int ni = (int)T.sel.size();
+  const size_t NI = (size_t)ni;
+  PlanSearchBlock& M = T.mc;
+  topay_status s;
+  M.n = NI;
+  if ((s = c->plan.mc.place(M)) != TOPAY_OK) return s;
+  HIPCHK(h2d(c, M.slot, T.sel.data(), NI));
+  const int ev = T.clk.begin(TOPAY_PLAN_MS_SEARCH);
+  hipLaunchKernelGGL(topay::k_plan_pack_search, dim3((ni + 63) / 64), dim3(64), 0, c->stream, ni, (const int*)M.slot, kPlanDenseCap, (const int*)T.tab.dense_len,
+                     (const double*)T.in.start, (const double*)T.in.end, (const int*)T.in.mid, (const unsigned long long*)T.in.call_no, T.t, M.off, M.len, M.start,
+                     M.end, M.mid, M.inst);
+  HIPCHK(hipGetLastError());
+  McIo io;
+  io.off = M.off; io.len = M.len; io.car = T.tab.dense; io.start = M.start; io.end = M.end; io.mid = M.mid; io.inst = M.inst;
+  io.wb_len = M.wb_len; io.wb = M.wb; io.stats = M.stats; io.cmax = M.cmax;
+  if ((s = mcrrt_launch(c, ni, T.R.P.mcrrt, 0, M.layer_cap, io)) != TOPAY_OK) return s;
+  T.clk.end(ev);
+  wlen.resize(NI); mstat.resize(NI * 8);
+  HIPCHK(d2h(c, wlen.data(), M.wb_len, NI));
+  HIPCHK(d2h(c, mstat.data(), M.stats, 8 * NI));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return TOPAY_OK;
+}
+
+// ---- hand-off to the solver: the launch's survivors join the try's batch; their ragged init paths and boundary velocities
+// are appended to the try's, launch by launch
+static topay_status plan_handoff(PlanTry& T, const std::vector<int>& wlen, const std::vector<int>& mstat) {
+  topay_ctx* c = T.c;
+  std::vector<int> src, src_call;
+  std::vector<long long> poff;
+  const int b0 = (int)T.call.size();
+  for (int i = 0; i < (int)T.sel.size(); i++) {
+    const int q = T.sel[i] / TOPAY_PLAN_MAX_CAND, k = T.sel[i] % TOPAY_PLAN_MAX_CAND, p = T.p_of(q);
+    if (T.R.cand) cand_row(T.R.cand, p, T.t, k)[TOPAY_PLAN_CAND_SEARCH_STATUS] = mstat[8 * (size_t)i];
+    if (mstat[8 * (size_t)i] != 1 || wlen[i] < 2) continue;
+    src.push_back(i);
+    src_call.push_back(q);
+    poff.push_back(T.off.back());
+    T.call.push_back(p); T.k.push_back(k); T.len.push_back(wlen[i]); T.mid.push_back(T.R.mids[p]);
+    T.off.push_back(T.off.back() + wlen[i]);
+  }
+  const int nsv = (int)src.size();
+  if (nsv == 0) return TOPAY_OK;
+  topay_status s;
+  if ((s = c->plan.paths.ensure_keep(c->stream, (size_t)T.off.back() * 80, (size_t)poff[0] * 80)) != TOPAY_OK) return s;
+  if ((s = c->plan.bvel.ensure_keep(c->stream, T.call.size() * 160, (size_t)b0 * 160)) != TOPAY_OK) return s;
+  PlanHandoffBlock H;
+  H.n = (size_t)nsv;
+  if ((s = c->plan.idx.place(H)) != TOPAY_OK) return s;
+  HIPCHK(h2d(c, H.path_off, poff.data(), H.n));
+  HIPCHK(h2d(c, H.src, src.data(), H.n));
+  HIPCHK(h2d(c, H.src_call, src_call.data(), H.n));
+  const int ev = T.clk.begin(TOPAY_PLAN_MS_INIT);
+  hipLaunchKernelGGL(topay::k_plan_pack_solver, dim3((unsigned)nsv), dim3(64), 0, c->stream, nsv, (const int*)H.src, (const int*)H.src_call, T.mc.layer_cap,
+                     (const int*)T.mc.wb_len, (const double*)T.mc.wb, (const long long*)H.path_off, (const double*)T.in.start_v, b0, c->plan.paths.as<double>(),
+                     c->plan.bvel.as<double>());
+  HIPCHK(hipGetLastError());
+  T.clk.end(ev);
+  HIPCHK(hipStreamSynchronize(c->stream));   // (the launch's buffers are reused by the next one)
+  return TOPAY_OK;
+}
+
+// ---- one batch: init, groups, solve, gate; then per call one lane over its candidates (adjacent in the batch, in candidate
+// order) for the winner.  Fills the candidates' rows and the winners' rows of `result` / `wcd`; W = the winners for the store.
+static topay_status plan_solve(PlanTry& T, PlanStore::Winners& W) {
+  topay_ctx* c = T.c;
+  const PlanReq& R = T.R;
+  const int B = (int)T.call.size(), t = T.t;
+  int ev = T.clk.begin(TOPAY_PLAN_MS_INIT);
+  topay_status s = set_init_traj_impl(c, B, T.len.data(), c->plan.paths.as<double>(), c->plan.bvel.as<double>(), nullptr, T.mid.data(), hipMemcpyDeviceToDevice);
+  T.clk.end(ev);
   if (s == TOPAY_ERR_TOO_MANY_PIECES) {   // every candidate needs more pieces than the build solves
-    if (cand)
-      for (int b = 0; b < B; b++) cand[(((size_t)T.call[b] * 2 + t) * 8 + T.k[b]) * 4] = topay::PLAN_TOO_MANY_PIECES;
+    if (R.cand)
+      for (int b = 0; b < B; b++) cand_row(R.cand, T.call[b], t, T.k[b])[TOPAY_PLAN_CAND_STAGE] = TOPAY_PLAN_STAGE_TOO_MANY_PIECES;
     return TOPAY_OK;
   }
   if (s != TOPAY_OK) return s;
-  if ((s = topay_set_groups(c, T.call.data(), P.cancel_budget)) != TOPAY_OK) return s;
+  if ((s = topay_set_groups(c, T.call.data(), R.P.cancel_budget)) != TOPAY_OK) return s;
   if ((s = topay_optimize(c)) != TOPAY_OK) return s;
-  c->pl_stage_ms[5] += c->last_ms;
+  c->plan.stage_ms[TOPAY_PLAN_MS_SOLVE] += c->last_ms;
   std::vector<int> feas(B);
-  id = clk.begin(6);
+  ev = T.clk.begin(TOPAY_PLAN_MS_GATE_WINNER);
   if ((s = topay_check_feasible(c, feas.data())) != TOPAY_OK) return s;
-  // ---- winners: per call one lane over its candidates (adjacent in the batch, in candidate order)
   std::vector<int> qcall, first, count;
   for (int b = 0; b < B; b++) {
     if (qcall.empty() || qcall.back() != T.call[b]) { qcall.push_back(T.call[b]); first.push_back(b); count.push_back(0); }
     count.back()++;
   }
   const int Q = (int)qcall.size();
-  double* d_wcd; int *d_first, *d_count, *d_win, *d_stage;
-  auto lay_win = [&](Carver& k) {
-    d_wcd = k.take<double>(2 * (size_t)Q);
-    d_first = k.take<int>((size_t)Q); d_count = k.take<int>((size_t)Q); d_win = k.take<int>((size_t)Q); d_stage = k.take<int>((size_t)B);
-  };
-  if ((s = c->pl_win.carve(lay_win)) != TOPAY_OK) return s;
-  HIPCHK(h2d(c, d_first, first.data(), (size_t)Q));
-  HIPCHK(h2d(c, d_count, count.data(), (size_t)Q));
-  hipLaunchKernelGGL(topay::k_plan_winner, dim3((Q + 63) / 64), dim3(64), 0, c->stream, c->db, Q, (const int*)d_first, (const int*)d_count, d_stage, d_win, d_wcd);
+  PlanWinnerBlock D;
+  D.calls = (size_t)Q; D.batch = (size_t)B;
+  if ((s = c->plan.win.place(D)) != TOPAY_OK) return s;
+  HIPCHK(h2d(c, D.first, first.data(), D.calls));
+  HIPCHK(h2d(c, D.count, count.data(), D.calls));
+  hipLaunchKernelGGL(topay::k_plan_winner, dim3((Q + 63) / 64), dim3(64), 0, c->stream, c->db, Q, (const int*)D.first, (const int*)D.count, D.stage, D.win, D.wcd);
   HIPCHK(hipGetLastError());
-  clk.end(id);
+  T.clk.end(ev);
   std::vector<int> win(Q), stage(B), sst((size_t)B * kStatsLen);
-  std::vector<double> hw(2 * (size_t)Q);
-  HIPCHK(d2h(c, win.data(), d_win, (size_t)Q));
-  HIPCHK(d2h(c, stage.data(), d_stage, (size_t)B));
-  HIPCHK(d2h(c, hw.data(), d_wcd, 2 * (size_t)Q));
+  std::vector<double> hw(2 * D.calls);
+  HIPCHK(d2h(c, win.data(), D.win, D.calls));
+  HIPCHK(d2h(c, stage.data(), D.stage, D.batch));
+  HIPCHK(d2h(c, hw.data(), D.wcd, 2 * D.calls));
   HIPCHK(d2h(c, sst.data(), c->stats.as<int>(), sst.size()));
   HIPCHK(hipStreamSynchronize(c->stream));
-  if (cand)
+  if (R.cand)
     for (int b = 0; b < B; b++) {
-      int* e = cand + (((size_t)T.call[b] * 2 + t) * 8 + T.k[b]) * 4;
-      e[0] = stage[b]; e[1] = c->hN[b]; e[3] = c->hN[b] > 0 ? sst[(size_t)b * kStatsLen + 3] : 0;
+      int* e = cand_row(R.cand, T.call[b], t, T.k[b]);
+      e[TOPAY_PLAN_CAND_STAGE] = stage[b];
+      e[TOPAY_PLAN_CAND_N_PIECES] = c->hN[b];
+      e[TOPAY_PLAN_CAND_SOLVER_STATUS] = c->hN[b] > 0 ? sst[(size_t)b * kStatsLen + 3] : 0;
     }
-  // ---- the winners into the store: trajectories in the layout of k_gather_results, init paths after them
-  std::vector<int> widx, woff{0}, foff{0};
   for (int q = 0; q < Q; q++) {
     if (win[q] < 0) continue;
     const int p = qcall[q], b = win[q];
-    int* r = result + 8 * (size_t)p;
-    r[0] = 1; r[1] = t; r[4] = T.k[b]; r[5] = c->hN[b]; r[7] = b;
-    if (wcd) { wcd[2 * (size_t)p] = hw[2 * (size_t)q]; wcd[2 * (size_t)p + 1] = hw[2 * (size_t)q + 1]; }
-    topay_ctx::PlanStored& e = c->ps_calls[p];
-    e.n_pieces = c->hN[b];
-    e.piece0 = (int)c->ps_pieces + woff.back();
-    e.knot0 = (int)c->ps_pieces + (int)c->ps_winners + woff.back() + (int)widx.size();
-    e.front0 = (int)c->ps_states + foff.back();
-    e.front_len = T.len[b];
-    widx.push_back(b);
-    woff.push_back(woff.back() + c->hN[b]);
-    foff.push_back(foff.back() + T.len[b]);
+    int* r = result_row(R.result, p);
+    r[TOPAY_PLAN_RES_STATUS] = 1; r[TOPAY_PLAN_RES_TRY] = t; r[TOPAY_PLAN_RES_WINNER] = T.k[b]; r[TOPAY_PLAN_RES_N_PIECES] = c->hN[b];
+    r[TOPAY_PLAN_RES_WINNER_BATCH_INDEX] = b;
+    if (R.wcd) { R.wcd[2 * (size_t)p] = hw[2 * (size_t)q]; R.wcd[2 * (size_t)p + 1] = hw[2 * (size_t)q + 1]; }
+    W.add(p, b, c->hN[b], T.len[b]);
   }
-  const int W = (int)widx.size();
-  if (W == 0) return TOPAY_OK;
-  const size_t np = (size_t)woff.back(), P0 = c->ps_pieces, W0 = c->ps_winners, F0 = c->ps_states;
-  if ((s = grow_keep(c, c->ps_dur, (P0 + np) * 8, P0 * 8)) != TOPAY_OK || (s = grow_keep(c, c->ps_coef, (P0 + np) * kCoefPerPiece * 8, P0 * kCoefPerPiece * 8)) != TOPAY_OK ||
-      (s = grow_keep(c, c->ps_kn, 2 * (P0 + W0 + np + W) * 8, 2 * (P0 + W0) * 8)) != TOPAY_OK ||
-      (s = grow_keep(c, c->ps_front, (F0 + (size_t)foff.back()) * 80, F0 * 80)) != TOPAY_OK)
-    return s;
-  int *d_idx, *d_woff, *d_foff;
-  auto lay_sel = [&](Carver& k) { d_idx = k.take<int>((size_t)W); d_woff = k.take<int>((size_t)W + 1); d_foff = k.take<int>((size_t)W + 1); };
-  if ((s = c->pl_sel.carve(lay_sel)) != TOPAY_OK) return s;
-  HIPCHK(h2d(c, d_idx, widx.data(), (size_t)W));
-  HIPCHK(h2d(c, d_woff, woff.data(), (size_t)W + 1));
-  HIPCHK(h2d(c, d_foff, foff.data(), (size_t)W + 1));
-  id = clk.begin(7);
-  hipLaunchKernelGGL(k_gather_results, dim3(W), dim3(64), 0, c->stream, c->db, W, (const int*)d_idx, (const int*)d_woff, c->ps_dur.as<double>() + P0,
-                     c->ps_coef.as<double>() + kCoefPerPiece * P0, c->ps_kn.as<double>() + 2 * (P0 + W0));
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(topay::k_plan_gather_front, dim3(W), dim3(64), 0, c->stream, W, (const int*)d_idx, (const double*)c->paths.as<double>(),
-                     (const long long*)c->path_off.as<long long>(), (const int*)d_foff, c->ps_front.as<double>() + 10 * F0);
-  HIPCHK(hipGetLastError());
-  clk.end(id);
-  HIPCHK(hipStreamSynchronize(c->stream));
-  c->ps_pieces += np; c->ps_winners += (size_t)W; c->ps_states += (size_t)foff.back();
   return TOPAY_OK;
+}
+
+// ---- the winners into the store: trajectories in the layout of k_gather_results, init paths after them
+static topay_status plan_store_winners(PlanTry& T, const PlanStore::Winners& W) {
+  topay_ctx* c = T.c;
+  const int nw = (int)W.size();
+  topay_status s;
+  PlanStore::Dest dst;
+  if ((s = c->plan_store.reserve(c->stream, W, dst)) != TOPAY_OK) return s;
+  PlanStoreIdxBlock I;
+  I.n = W.size();
+  if ((s = c->plan.idx.place(I)) != TOPAY_OK) return s;
+  HIPCHK(h2d(c, I.idx, W.idx.data(), I.n));
+  HIPCHK(h2d(c, I.piece_off, W.piece_off.data(), I.n + 1));
+  HIPCHK(h2d(c, I.front_off, W.front_off.data(), I.n + 1));
+  const int ev = T.clk.begin(TOPAY_PLAN_MS_STORE);
+  hipLaunchKernelGGL(k_gather_results, dim3(nw), dim3(64), 0, c->stream, c->db, nw, (const int*)I.idx, (const int*)I.piece_off, dst.dur, dst.coef, dst.knots);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(topay::k_plan_gather_front, dim3(nw), dim3(64), 0, c->stream, nw, (const int*)I.idx, (const double*)c->paths.as<double>(),
+                     (const long long*)c->path_off.as<long long>(), (const int*)I.front_off, dst.front);
+  HIPCHK(hipGetLastError());
+  T.clk.end(ev);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->plan_store.appended(W);
+  return TOPAY_OK;
+}
+
+// One try for the calls `act`: the front-end in launches of kPlanChunk calls, one solve, winners into the store.  Fills the
+// calls' rows of R.result / R.cand / R.wcd.
+static topay_status plan_try(topay_ctx* c, int t, const std::vector<int>& act, PlanReq& R, PlanClock& clk) {
+  topay_status s;
+  PlanTry T{c, R, t, act, clk};
+  const size_t chunk = (size_t)(c->plan.chunk > 0 ? c->plan.chunk : kPlanChunk);
+  std::vector<int> wlen, mstat;
+  for (T.a0 = 0; T.a0 < act.size(); T.a0 += chunk) {
+    T.nc = (int)std::min<size_t>(chunk, act.size() - T.a0);
+    if ((s = plan_gather_calls(T)) != TOPAY_OK || (s = plan_roadmap_jps(T)) != TOPAY_OK || (s = plan_candidates(T)) != TOPAY_OK) return s;
+    if (T.sel.empty()) continue;
+    if ((s = plan_search(T, wlen, mstat)) != TOPAY_OK || (s = plan_handoff(T, wlen, mstat)) != TOPAY_OK) return s;
+  }
+  if (T.call.empty()) return TOPAY_OK;   // no candidate of any call survived to the solve: the try fails for all of them
+  PlanStore::Winners W;
+  if ((s = plan_solve(T, W)) != TOPAY_OK || W.size() == 0) return s;
+  return plan_store_winners(T, W);
 }
 
 extern "C" {
@@ -344,7 +425,10 @@ static topay_status plan_calls_impl(topay_ctx* c, int n, const int* map_ids, con
                                     const topay_plan_params_t* params, unsigned long long first_call, const unsigned long long* call_nos, int* result,
                                     int* candidates, double* winner_cost_duration) {
   if (!c || n <= 0 || !start || !end || !result) return TOPAY_ERR_INVALID_ARG;
-  topay_plan_params_t P;
+  PlanReq R;
+  R.start = start; R.end = end; R.start_v = start_v; R.first_call = first_call; R.call_nos = call_nos;
+  R.result = result; R.cand = candidates; R.wcd = winner_cost_duration;
+  topay_plan_params_t& P = R.P;
   if (params) P = *params;
   else topay_plan_default_params(&P);
   if (P.max_candidates < 1 || P.max_candidates > TOPAY_PLAN_MAX_CAND || !(P.dense_step > 0.0) || P.cancel_budget < 0 || !mcrrt_params_ok(P.mcrrt) ||
@@ -352,40 +436,40 @@ static topay_status plan_calls_impl(topay_ctx* c, int n, const int* map_ids, con
     set_err("topay_plan_calls: parameters out of range (max_candidates 1..8, dense_step > 0, cancel_budget >= 0)");
     return TOPAY_ERR_INVALID_ARG;
   }
-  std::vector<int> mids((size_t)n, 0);
+  R.mids.assign((size_t)n, 0);
   for (int p = 0; p < n; p++) {
-    mids[p] = map_ids ? map_ids[p] : 0;
-    if (mids[p] < 0 || mids[p] >= TOPAY_MAX_MAPS) return TOPAY_ERR_INVALID_ARG;
-    if (!c->have_map[mids[p]]) { set_err("map slot not set"); return TOPAY_ERR_NO_MAP; }
-    const DevMap& m = c->hmaps[mids[p]];
+    const int mid = R.mids[p] = map_ids ? map_ids[p] : 0;
+    if (mid < 0 || mid >= TOPAY_MAX_MAPS) return TOPAY_ERR_INVALID_ARG;
+    if (!c->have_map[mid]) { set_err("map slot not set"); return TOPAY_ERR_NO_MAP; }
+    const DevMap& m = c->hmaps[mid];
     if (!m.esdf2d_inflate || !m.esdf2d_critical) {
-      set_err("topay_plan_calls: map slot " + std::to_string(mids[p]) + " has no front-end fields: fill it with topay_build_esdf*, not topay_set_map");
+      set_err("topay_plan_calls: map slot " + std::to_string(mid) + " has no front-end fields: fill it with topay_build_esdf*, not topay_set_map");
       return TOPAY_ERR_NO_MAP;
     }
   }
   HIPCHK(hipSetDevice(c->device));
   if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }
-  c->ps_calls.assign((size_t)n, topay_ctx::PlanStored());
-  c->ps_pieces = c->ps_winners = c->ps_states = 0;
-  for (int k = 0; k < 8; k++) c->pl_stage_ms[k] = 0.0;
+  c->plan_store.reset(n);
+  for (int k = 0; k < TOPAY_PLAN_MS_LEN; k++) c->plan.stage_ms[k] = 0.0;
   for (int p = 0; p < n; p++) {
-    int* r = result + 8 * (size_t)p;
-    r[0] = 0; r[1] = -1; r[2] = 0; r[3] = 0; r[4] = -1; r[5] = 0; r[6] = 0; r[7] = -1;
+    int* r = result_row(result, p);
+    std::fill(r, r + TOPAY_PLAN_RES_LEN, 0);
+    r[TOPAY_PLAN_RES_TRY] = r[TOPAY_PLAN_RES_WINNER] = r[TOPAY_PLAN_RES_WINNER_BATCH_INDEX] = -1;
     if (winner_cost_duration) winner_cost_duration[2 * (size_t)p] = winner_cost_duration[2 * (size_t)p + 1] = 0.0 / 0.0;
   }
-  if (candidates) memset(candidates, 0, (size_t)n * 2 * 8 * 4 * sizeof(int));
+  if (candidates) memset(candidates, 0, (size_t)n * TOPAY_PLAN_CAND_ROW_LEN * sizeof(int));
   PlanClock clk(c);
   topay_status s = TOPAY_OK;
   for (int t = 0; t < 2 && s == TOPAY_OK; t++) {
     if (t == 1 && !P.critical_retry) break;
     std::vector<int> act;
     for (int p = 0; p < n; p++)
-      if (result[8 * (size_t)p] == 0) act.push_back(p);
+      if (result_row(result, p)[TOPAY_PLAN_RES_STATUS] == 0) act.push_back(p);
     if (act.empty()) break;
-    s = plan_try(c, t, act, mids, start, end, start_v, P, first_call, call_nos, result, candidates, winner_cost_duration, clk);
+    s = plan_try(c, t, act, R, clk);
   }
   clk.collect();
-  if (s != TOPAY_OK) { c->ps_calls.clear(); return s; }
+  if (s != TOPAY_OK) { c->plan_store.clear(); return s; }
   return TOPAY_OK;
 }
 
@@ -398,12 +482,13 @@ topay_status topay_plan_calls(topay_ctx* c, int n, const int* map_ids, const dou
 topay_status topay_plan_get_trajs(topay_ctx* c, int n, const int* call_idx, int cap_pieces, int* piece_off, double* durations, double* coeffs,
                                   double* knots_xy) {
   if (!c || n < 0 || (n > 0 && (!call_idx || !piece_off))) return TOPAY_ERR_INVALID_ARG;
-  if (c->ps_calls.empty()) { set_err("topay_plan_get_trajs: no planning call has been run"); return TOPAY_ERR_NO_TRAJ; }
+  PlanStore& S = c->plan_store;
+  if (S.empty()) { set_err("topay_plan_get_trajs: no planning call has been run"); return TOPAY_ERR_NO_TRAJ; }
   if (n == 0) return TOPAY_OK;
   std::vector<int> off((size_t)n + 1, 0), sp((size_t)n, 0), sk((size_t)n, 0);
   for (int k = 0; k < n; k++) {
-    if (call_idx[k] < 0 || call_idx[k] >= (int)c->ps_calls.size()) return TOPAY_ERR_INVALID_ARG;
-    const topay_ctx::PlanStored& e = c->ps_calls[call_idx[k]];
+    if (!S.has(call_idx[k])) return TOPAY_ERR_INVALID_ARG;
+    const PlanStore::Entry& e = S.entry(call_idx[k]);
     off[k + 1] = off[k] + e.n_pieces;
     sp[k] = e.piece0; sk[k] = e.knot0;
   }
@@ -425,7 +510,7 @@ topay_status topay_plan_get_trajs(topay_ctx* c, int n, const int* call_idx, int 
   HIPCHK(hipMemsetAsync(d_kn, 0, kn * sizeof(double), c->stream));   // a call without a winner still owns one knot pair: zeros
   if (np > 0) {
     hipLaunchKernelGGL(topay::k_plan_store_gather, dim3(n), dim3(64), 0, c->stream, n, (const int*)d_sp, (const int*)d_sk, (const int*)d_off,
-                       (const double*)c->ps_dur.as<double>(), (const double*)c->ps_coef.as<double>(), (const double*)c->ps_kn.as<double>(), d_dur, d_coef, d_kn);
+                       (const double*)S.durations(), (const double*)S.coeffs(), (const double*)S.knots(), d_dur, d_coef, d_kn);
     HIPCHK(hipGetLastError());
   }
   std::vector<double> host(dbl);
@@ -438,27 +523,28 @@ topay_status topay_plan_get_trajs(topay_ctx* c, int n, const int* call_idx, int 
 
 topay_status topay_plan_get_front_path(topay_ctx* c, int call, int cap_states, int* n_states, double* states) {
   if (!c || !n_states || cap_states < 0) return TOPAY_ERR_INVALID_ARG;
-  if (c->ps_calls.empty()) { set_err("topay_plan_get_front_path: no planning call has been run"); return TOPAY_ERR_NO_TRAJ; }
-  if (call < 0 || call >= (int)c->ps_calls.size()) return TOPAY_ERR_INVALID_ARG;
-  const topay_ctx::PlanStored& e = c->ps_calls[call];
+  PlanStore& S = c->plan_store;
+  if (S.empty()) { set_err("topay_plan_get_front_path: no planning call has been run"); return TOPAY_ERR_NO_TRAJ; }
+  if (!S.has(call)) return TOPAY_ERR_INVALID_ARG;
+  const PlanStore::Entry& e = S.entry(call);
   *n_states = e.front_len;
   const int w = std::min(e.front_len, cap_states);
   if (w > 0 && states) {
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(d2h_sync(c, states, c->ps_front.as<double>() + 10 * (size_t)e.front0, (size_t)w * 10));
+    HIPCHK(d2h_sync(c, states, S.fronts() + PlanStore::front_double0(e), (size_t)w * 10));
   }
   return TOPAY_OK;
 }
 
 topay_status topay_plan_test_chunk(topay_ctx* c, int calls) {
   if (!c || calls < 0) return TOPAY_ERR_INVALID_ARG;
-  c->pl_chunk = calls;
+  c->plan.chunk = calls;
   return TOPAY_OK;
 }
 
 topay_status topay_plan_stage_ms(topay_ctx* c, double* ms) {
   if (!c || !ms) return TOPAY_ERR_INVALID_ARG;
-  for (int k = 0; k < 8; k++) ms[k] = c->pl_stage_ms[k];
+  for (int k = 0; k < TOPAY_PLAN_MS_LEN; k++) ms[k] = c->plan.stage_ms[k];
   return TOPAY_OK;
 }
 

@@ -50,7 +50,7 @@ static topay_status track_commit_impl(topay_ctx* c, const std::vector<TrackPut>&
     sp[k] = p.src_piece; ss[k] = p.src_start;
   }
   topay_status s;
-  if ((s = grow_keep(c, c->tr_arena, used * 8, c->tr_used * 8)) != TOPAY_OK) return s;
+  if ((s = c->tr_arena.ensure_keep(c->stream, used * 8, c->tr_used * 8)) != TOPAY_OK) return s;
   topay::TrackDesc* d_dst; long long *d_sp, *d_ss;
   auto lay = [&](Carver& k) { d_sp = k.take<long long>(n); d_ss = k.take<long long>(n); d_dst = k.take<topay::TrackDesc>(n); };
   if ((s = c->tr_io.carve(lay)) != TOPAY_OK) return s;
@@ -172,21 +172,22 @@ static topay_status track_endpoints_impl(topay_ctx* c, int n, const int* robots,
 
 // Winners of the last planning call into the slots: device to device from the plan store.
 static topay_status track_commit_plan_impl(topay_ctx* c, int n, const int* robots, const int* call_idx, int which, int* committed) {
-  std::vector<double> hdur(std::max<size_t>(1, c->ps_pieces));
-  if (c->ps_pieces > 0) HIPCHK(d2h_sync(c, hdur.data(), c->ps_dur.as<double>(), c->ps_pieces));
+  PlanStore& S = c->plan_store;
+  std::vector<double> hdur(std::max<size_t>(1, S.n_pieces()));
+  if (S.n_pieces() > 0) HIPCHK(d2h_sync(c, hdur.data(), S.durations(), S.n_pieces()));
   std::vector<TrackPut> puts;
   for (int k = 0; k < n; k++) {
-    const topay_ctx::PlanStored& e = c->ps_calls[call_idx[k]];
+    const PlanStore::Entry& e = S.entry(call_idx[k]);
     if (committed) committed[k] = 0;
     if (e.n_pieces <= 0) continue;
     TrackPut p;
-    p.robot = robots[k]; p.N = e.n_pieces; p.src_piece = e.piece0; p.src_start = 10ll * e.front0;
+    p.robot = robots[k]; p.N = e.n_pieces; p.src_piece = e.piece0; p.src_start = PlanStore::front_double0(e);
     if (!track_duration_ok(&hdur[(size_t)e.piece0], e.n_pieces, p.T)) continue;
     for (int w = 0; w < 2; w++)
       if (which & (1 << w)) { p.w = w; puts.push_back(p); }
     if (committed) committed[k] = 1;
   }
-  return track_commit_impl(c, puts, c->ps_dur.as<double>(), c->ps_coef.as<double>(), c->ps_front.as<double>());
+  return track_commit_impl(c, puts, S.durations(), S.coeffs(), S.fronts());
 }
 
 extern "C" {
@@ -216,10 +217,10 @@ topay_status topay_track_set(topay_ctx* c, int robot, int which, const double* s
 topay_status topay_track_commit_plan(topay_ctx* c, int n, const int* robots, const int* call_idx, int which, int* committed) {
   if (!c || n < 0 || (n > 0 && (!robots || !call_idx))) return TOPAY_ERR_INVALID_ARG;
   if (which < 1 || which > 3) { set_err("topay_track_commit_plan: which must be 1, 2 or 3"); return TOPAY_ERR_INVALID_ARG; }
-  if (c->ps_calls.empty()) { set_err("topay_track_commit_plan: no planning call has been run"); return TOPAY_ERR_NO_TRAJ; }
+  if (c->plan_store.empty()) { set_err("topay_track_commit_plan: no planning call has been run"); return TOPAY_ERR_NO_TRAJ; }
   for (int k = 0; k < n; k++) {
     if (!track_robot_ok(robots[k])) { set_err("topay_track_commit_plan: robot slot out of range"); return TOPAY_ERR_INVALID_ARG; }
-    if (call_idx[k] < 0 || call_idx[k] >= (int)c->ps_calls.size()) return TOPAY_ERR_INVALID_ARG;
+    if (!c->plan_store.has(call_idx[k])) return TOPAY_ERR_INVALID_ARG;
   }
   if (!track_robots_distinct(n, robots)) { set_err("topay_track_commit_plan: a robot slot is named twice"); return TOPAY_ERR_INVALID_ARG; }
   HIPCHK(hipSetDevice(c->device));
@@ -299,17 +300,17 @@ topay_status topay_replan_calls(topay_ctx* c, int n, const int* robots, const in
   // ---- 2. trigger (replanCallback:649, 705-706)
   std::vector<int> trig;
   for (int r = 0; r < n; r++) {
-    int* st = status + 4 * (size_t)r;
-    st[0] = 0; st[1] = safe[r]; st[2] = -1; st[3] = -1;
+    int* st = status + TOPAY_REPLAN_ST_LEN * (size_t)r;
+    st[TOPAY_REPLAN_ST_OUTCOME] = 0; st[TOPAY_REPLAN_ST_SAFE] = safe[r]; st[TOPAY_REPLAN_ST_STORE_ROW] = -1; st[TOPAY_REPLAN_ST_GOAL_SOURCE] = -1;
     if (now_xy) {
       const double dx = now_xy[2 * (size_t)r] - global_goal[10 * (size_t)r], dy = now_xy[2 * (size_t)r + 1] - global_goal[10 * (size_t)r + 1];
-      if (std::sqrt(dx * dx + dy * dy) < 0.5) { st[0] = 3; continue; }
+      if (std::sqrt(dx * dx + dy * dy) < 0.5) { st[TOPAY_REPLAN_ST_OUTCOME] = 3; continue; }
     }
     if (t_since_replan[r] > replan_interval || !safe[r]) trig.push_back(r);
   }
   if (endpoints) std::fill(endpoints, endpoints + 30 * N, 0.0 / 0.0);
-  if (plan_result) std::fill(plan_result, plan_result + 8 * N, 0);
-  if (plan_candidates) std::fill(plan_candidates, plan_candidates + 64 * N, 0);
+  if (plan_result) std::fill(plan_result, plan_result + TOPAY_PLAN_RES_LEN * N, 0);
+  if (plan_candidates) std::fill(plan_candidates, plan_candidates + TOPAY_PLAN_CAND_ROW_LEN * N, 0);
   const int m = (int)trig.size();
   if (m == 0) return TOPAY_OK;
   // ---- 3. endpoints of the triggered robots
@@ -327,7 +328,7 @@ topay_status topay_replan_calls(topay_ctx* c, int n, const int* robots, const in
                                 src.data())) != TOPAY_OK)
     return s;
   // ---- 4. the planning call (planMomaParallel(local_start, local_goal, local_v))
-  std::vector<int> res(8 * M), cand(64 * M);
+  std::vector<int> res(TOPAY_PLAN_RES_LEN * M), cand(TOPAY_PLAN_CAND_ROW_LEN * M);
   if ((s = plan_calls_impl(c, m, mid.data(), st10.data(), go10.data(), sv10.data(), params, 0, call_no.data(), res.data(), cand.data(), nullptr)) != TOPAY_OK) return s;
   // ---- 5. winners become end_traj (planner.cpp:1010); global_traj stays
   std::vector<int> idx(M), done(M);
@@ -335,15 +336,16 @@ topay_status topay_replan_calls(topay_ctx* c, int n, const int* robots, const in
   if ((s = track_commit_plan_impl(c, m, rob.data(), idx.data(), 1, done.data())) != TOPAY_OK) return s;
   for (int j = 0; j < m; j++) {
     const int r = trig[j];
-    int* st = status + 4 * (size_t)r;
-    st[0] = done[j] ? 1 : 2; st[2] = j; st[3] = src[j];
+    int* st = status + TOPAY_REPLAN_ST_LEN * (size_t)r;
+    st[TOPAY_REPLAN_ST_OUTCOME] = done[j] ? 1 : 2; st[TOPAY_REPLAN_ST_STORE_ROW] = j; st[TOPAY_REPLAN_ST_GOAL_SOURCE] = src[j];
     if (endpoints) {
       memcpy(endpoints + 30 * (size_t)r, &st10[10 * (size_t)j], 80);
       memcpy(endpoints + 30 * (size_t)r + 10, &sv10[10 * (size_t)j], 80);
       memcpy(endpoints + 30 * (size_t)r + 20, &go10[10 * (size_t)j], 80);
     }
-    if (plan_result) memcpy(plan_result + 8 * (size_t)r, &res[8 * (size_t)j], 32);
-    if (plan_candidates) memcpy(plan_candidates + 64 * (size_t)r, &cand[64 * (size_t)j], 256);
+    if (plan_result) memcpy(plan_result + TOPAY_PLAN_RES_LEN * (size_t)r, &res[TOPAY_PLAN_RES_LEN * (size_t)j], TOPAY_PLAN_RES_LEN * sizeof(int));
+    if (plan_candidates)
+      memcpy(plan_candidates + TOPAY_PLAN_CAND_ROW_LEN * (size_t)r, &cand[TOPAY_PLAN_CAND_ROW_LEN * (size_t)j], TOPAY_PLAN_CAND_ROW_LEN * sizeof(int));
   }
   return TOPAY_OK;
 }

@@ -14,8 +14,6 @@
 
 namespace topay {
 
-#define TOPAY_PLAN_MAX_CAND 8   // traj_opters.size(), planner.cpp:59
-
 struct PlanCandArgs {
   int n;                      // calls of this launch
   int cap_paths, cap_points;  // layout of the roadmap's result: path (p, k) starts at point (p cap_paths + k) cap_points
@@ -105,9 +103,9 @@ __global__ void k_plan_pack_solver(int n, const int* src, const int* src_call, i
   for (int t = threadIdx.x; t < 20; t += blockDim.x) bv[t] = t < 10 ? (start_v ? start_v[10 * (size_t)src_call[j] + t] : 0.0) : 0.0;
 }
 
-// Stage of a solved candidate: 2 needs more pieces than the build solves, 3 solver failed, 4 gate failed, 5 interrupted,
-// 6 counts (optimizeTraj true AND printConstraintsSituations passed, planner.cpp:878-880).
-enum { PLAN_ABSENT = 0, PLAN_SEARCH_FAILED = 1, PLAN_TOO_MANY_PIECES = 2, PLAN_SOLVER_FAILED = 3, PLAN_GATE_FAILED = 4, PLAN_INTERRUPTED = 5, PLAN_COUNTS = 6 };
+// Stage of a solved candidate (TOPAY_PLAN_STAGE_* of include/topay.h, where TOPAY_PLAN_MAX_CAND is stated too): 2 needs more
+// pieces than the build solves, 3 solver failed, 4 gate failed, 5 interrupted, 6 counts (optimizeTraj true AND
+// printConstraintsSituations passed, planner.cpp:878-880).
 
 // One lane per call q of the solved batch: its candidates are the batch members [first[q], first[q] + count[q]), in
 // candidate order.  The winner is the first whose total duration is strictly the smallest (planner.cpp:999-1010); the
@@ -121,16 +119,16 @@ __global__ void k_plan_winner(DevBatch Bt, int n_calls, const int* first, const 
     const int N = Bt.N[b];
     int st;
     double dur = 0.0;
-    if (N <= 0) st = PLAN_TOO_MANY_PIECES;
+    if (N <= 0) st = TOPAY_PLAN_STAGE_TOO_MANY_PIECES;
     else {
       for (int i = 0; i < N; i++) dur += Bt.T_of(Bt.poff[b])[i];
-      if (Bt.interrupted[b]) st = PLAN_INTERRUPTED;
-      else if (!Bt.success[b]) st = PLAN_SOLVER_FAILED;
-      else if (!Bt.flags_of(b)[0]) st = PLAN_GATE_FAILED;
-      else st = PLAN_COUNTS;
+      if (Bt.interrupted[b]) st = TOPAY_PLAN_STAGE_INTERRUPTED;
+      else if (!Bt.success[b]) st = TOPAY_PLAN_STAGE_SOLVER_FAILED;
+      else if (!Bt.flags_of(b)[0]) st = TOPAY_PLAN_STAGE_GATE_FAILED;
+      else st = TOPAY_PLAN_STAGE_COUNTS;
     }
     stage[b] = st;
-    if (st == PLAN_COUNTS && (best < 0 || dur < best_dur)) { best = b; best_dur = dur; }
+    if (st == TOPAY_PLAN_STAGE_COUNTS && (best < 0 || dur < best_dur)) { best = b; best_dur = dur; }
   }
   win[q] = best;
   win_cost_dur[2 * (size_t)q] = best < 0 ? 0.0 / 0.0 : Bt.cost[best];
