@@ -5,6 +5,7 @@
 #include "jps.hpp"
 #include "topo_prm.hpp"
 #include "replan.hpp"
+#include "ee_goal.hpp"
 
 using namespace topay_wl;
 
@@ -185,6 +186,47 @@ int wl_replan_endpoints(void* end_traj, void* global_traj, double since_last_rep
                         double planning_budget, double planning_horizon, double* start, double* start_v, double* goal) {
   return replan_endpoints(*(ReplanTraj*)end_traj, (const ReplanTraj*)global_traj, since_last_replan, since_begin, global_goal, planning_budget,
                           planning_horizon, start, start_v, goal);
+}
+
+// ---- end-effector goals' restatement (harness/ee_goal.hpp) ------------------------------------------------------------
+void wl_ee_pose(int n, const double* states, double* pose) {
+  const topay_oracle::Robot robot;
+  for (int k = 0; k < n; k++) ee_goal::getFKPose(robot, states + 10 * (size_t)k, pose + 9 * (size_t)k);
+}
+static void ee_problem(ee_goal::Problem& p, topay_oracle::Map& m, const double* origin, double res, const int* dims, const double* min_b,
+                       const double* max_b, const double* esdf2d, const double* esdf3d, const double* ee_ref) {
+  m.set(origin, res, dims, esdf2d, esdf3d);
+  m.setBounds(min_b, max_b);
+  p.grid_map = &m;
+  p.relu_mu = topay_oracle::Params().relu_mu;
+  for (int a = 0; a < 9; a++) p.ee_pose[a] = ee_ref[a];
+}
+// eeCostCallback at the unconstrained x.  terms[4] = ee, environment, chassis top, pairs; counts[4] = active terms of the
+// last three kinds, spheres outside the map; kinks[3] = Breakdown's kink distances.  Returns f.
+double wl_ee_eval(const double* origin, double res, const int* dims, const double* min_b, const double* max_b, const double* esdf2d,
+                  const double* esdf3d, const double* x, const double* ee_ref, double* g, double* terms, int* counts, double* kinks) {
+  topay_oracle::Map m;
+  ee_goal::Problem p;
+  ee_problem(p, m, origin, res, dims, min_b, max_b, esdf2d, esdf3d, ee_ref);
+  ee_goal::Breakdown b;
+  const double f = p.cost(x, g, &b);
+  if (terms) { terms[0] = b.ee; terms[1] = b.mani; terms[2] = b.chassis; terms[3] = b.pairs; }
+  if (counts) { counts[0] = b.n_mani; counts[1] = b.n_chassis; counts[2] = b.n_pairs; counts[3] = b.n_outside; }
+  if (kinks) { kinks[0] = b.kink_penalty; kinks[1] = b.kink_cell; kinks[2] = b.kink_sigmoid; }
+  return f;
+}
+// optimizeEE of one problem; state10 in / out.  lbfgs[4] = mem_size, past, max_iterations, max_linesearch; g_epsilon, delta as given,
+// the other fields lbfgs_parameter_t's defaults.  out_int[2] = iterations, evaluations.  Returns the L-BFGS code.
+int wl_ee_optimize(const double* origin, double res, const int* dims, const double* min_b, const double* max_b, const double* esdf2d,
+                   const double* esdf3d, double* state10, const double* ee_ref, const int* lbfgs, double g_epsilon, double delta, double* cost,
+                   int* out_int) {
+  topay_oracle::Map m;
+  ee_goal::Problem p;
+  ee_problem(p, m, origin, res, dims, min_b, max_b, esdf2d, esdf3d, ee_ref);
+  topay_oracle::LbfgsParam lp;
+  lp.mem_size = lbfgs[0]; lp.past = lbfgs[1]; lp.max_iterations = lbfgs[2]; lp.max_linesearch = lbfgs[3];
+  lp.g_epsilon = g_epsilon; lp.delta = delta;
+  return p.optimize(state10, lp, cost, out_int, out_int + 1);
 }
 
 }  // extern "C"

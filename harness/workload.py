@@ -318,8 +318,58 @@ def mlib():
         L.wl_replan_state.restype = None
         L.wl_replan_safe.argtypes = [C.c_void_p, c_dp, C.c_double, c_ip, c_dp, c_dp, c_dp, c_dp, c_ip, c_dp, c_dp]
         L.wl_replan_endpoints.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, c_dp, C.c_double, C.c_double, c_dp, c_dp, c_dp]
+        map_args = [c_dp, C.c_double, c_ip, c_dp, c_dp, c_dp, c_dp]
+        L.wl_ee_pose.argtypes = [C.c_int, c_dp, c_dp]
+        L.wl_ee_pose.restype = None
+        L.wl_ee_eval.argtypes = map_args + [c_dp, c_dp, c_dp, c_dp, c_ip, c_dp]
+        L.wl_ee_eval.restype = C.c_double
+        L.wl_ee_optimize.argtypes = map_args + [c_dp, c_dp, c_ip, C.c_double, C.c_double, c_dp, c_ip]
         _MLIB = L
     return _MLIB
+
+
+class EeGoal:
+    """CPU restatement of getFKPose, eeCostCallback (gradient assigned) and optimizeEE on one map (harness/ee_goal.hpp)."""
+
+    def __init__(self, origin, res, dims, min_b, max_b, esdf2d, esdf3d):
+        self.L = mlib()
+        self.org = np.ascontiguousarray(origin, dtype=np.float64)
+        self.res = float(res)
+        self.dm = np.ascontiguousarray(dims, dtype=np.int32)
+        self.mn, self.mx = np.ascontiguousarray(min_b, dtype=np.float64), np.ascontiguousarray(max_b, dtype=np.float64)
+        self.e2, self.e3 = np.ascontiguousarray(esdf2d, dtype=np.float64), np.ascontiguousarray(esdf3d, dtype=np.float64)
+
+    def _map(self):
+        return (_dp(self.org), self.res, self.dm.ctypes.data_as(c_ip), _dp(self.mn), _dp(self.mx), _dp(self.e2), _dp(self.e3))
+
+    @staticmethod
+    def pose(states):
+        """getFKPose of [n, 10] states: [n, 9]."""
+        st = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 10)
+        out = np.zeros((len(st), 9))
+        mlib().wl_ee_pose(len(st), _dp(st), _dp(out))
+        return out
+
+    def eval(self, x, ee_ref):
+        """eeCostCallback at the unconstrained x: (f, g [10], dict(terms = ee / mani / chassis / pairs, n_mani, n_chassis, n_pairs,
+        n_outside, kink_penalty, kink_cell, kink_sigmoid))."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        ref = np.ascontiguousarray(ee_ref, dtype=np.float64)
+        g, terms, counts, kinks = np.zeros(10), np.zeros(4), np.zeros(4, dtype=np.int32), np.zeros(3)
+        f = self.L.wl_ee_eval(*self._map(), _dp(x), _dp(ref), _dp(g), _dp(terms), counts.ctypes.data_as(c_ip), _dp(kinks))
+        return float(f), g, dict(terms=dict(zip(("ee", "mani", "chassis", "pairs"), terms)), n_mani=int(counts[0]), n_chassis=int(counts[1]),
+                                 n_pairs=int(counts[2]), n_outside=int(counts[3]), kink_penalty=float(kinks[0]), kink_cell=float(kinks[1]),
+                                 kink_sigmoid=float(kinks[2]))
+
+    def optimize(self, seed_state, ee_ref, mem_size=64, past=3, max_iterations=10000, max_linesearch=64, g_epsilon=1e-5, delta=1e-4):
+        """optimizeEE: (state [10], cost, code, iters, evals); the seed comes back for a code outside the reference's success set."""
+        st = np.array(seed_state, dtype=np.float64)
+        ref = np.ascontiguousarray(ee_ref, dtype=np.float64)
+        lb = np.array([mem_size, past, max_iterations, max_linesearch], dtype=np.int32)
+        cost, oi = np.zeros(1), np.zeros(2, dtype=np.int32)
+        code = self.L.wl_ee_optimize(*self._map(), _dp(st), _dp(ref), lb.ctypes.data_as(c_ip), float(g_epsilon), float(delta), _dp(cost),
+                                     oi.ctypes.data_as(c_ip))
+        return st, float(cost[0]), int(code), int(oi[0]), int(oi[1])
 
 
 class ReplanTraj:

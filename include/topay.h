@@ -624,6 +624,52 @@ topay_status topay_replan_calls(topay_ctx* ctx, int n, const int* robots, const 
                                 double planning_budget, double planning_horizon, const topay_plan_params_t* params,
                                 unsigned long long first_call, int* status, double* endpoints, int* plan_result, int* plan_candidates);
 
+/* ---- End-effector goals: MomaTrajOpt::optimizeEE (moma_traj_opt.cpp:5-140) for n independent problems -----------------------
+ * A goal state (x, y, theta, q1..q7) from an end-effector pose: what Planner::planCallBack is written around for "target"
+ * goals (planner.cpp:188-199).  A pose is getFKPose's 9-vector (moma_param.h:339-373): position, row 0, row 1 of the rotation.
+ * One problem per GPU lane, so the natural call is seeds x targets: many seeds per target, topay_ee_select picks.
+ * What the reference leaves undefined is decided like this:
+ *   - eeCostCallback adds into a gradient that lbfgs_optimize never clears (moma_traj_opt.cpp:135-137; lbfgs.hpp:504, 523,
+ *     318); here the gradient is ASSIGNED.  (The reference's only call of optimizeEE is commented out.)
+ *   - success is the reference's set of codes (moma_traj_opt.cpp:30-31): TOPAY_LBFGS_CONVERGENCE, _STOP, _CANCELED and
+ *     TOPAY_LBFGSERR_MAXIMUMITERATION; the raw code is returned as well.
+ *   - a sphere outside the 3-D field has distance 0 and gradient 0 (getDisWithGradI3d); reparameterisations, penalty and
+ *     sin / cos are those of the trajectory solver (sigmoidC2, invSigmoidC2, getQtoVqGrad, smoothL1Penalty with relu_mu of
+ *     topay_params_t, deterministic sin / cos). */
+typedef struct {
+  topay_lbfgs_params_t lbfgs;     /* mem_size 64 (1..64 accepted), past 3 (0..8), g_epsilon 1e-5, delta 1e-4, max_iterations 10000;
+                                   * the other fields: lbfgs_parameter_t's defaults (lbfgs.hpp:15-129) */
+  double cost_scale;              /* 10   (moma_traj_opt.cpp:68) */
+  double mani_colli_weight;       /* 100  (69) */
+  double self_colli_weight;       /* 100  (70) */
+  double clearance_factor;        /* 1.1  (78) */
+  double pose_tol;                /* topay_ee_select: largest |getFKPose(state) - ee_ref| (9-vector, 2-norm) of a goal; 1e-2 */
+  int require_collision_free;     /* topay_ee_select: 1 = the goal must not be in isWholeBodyCollision on its map; 1 */
+  int reserved;
+} topay_ee_params_t;
+void topay_ee_default_params(topay_ee_params_t* p);
+/* getFKPose of n states: pose[n][9]. */
+topay_status topay_ee_pose(topay_ctx* ctx, int n, const double* states /* n x 10 */, double* pose /* n x 9 */);
+/* One eeCostCallback per problem at the UNCONSTRAINED x (x, y, theta, invSigmoidC2 of the joints), with the default weights:
+ * f[n], g[n][10].  map_ids NULL = slot 0.  The per-evaluation parity hook, as topay_eval is for the trajectory problem. */
+topay_status topay_ee_eval(topay_ctx* ctx, int n, const int* map_ids, const double* x /* n x 10 */, const double* ee_ref /* n x 9 */,
+                           double* f, double* g /* n x 10 */);
+/* optimizeEE of n problems.  seed_states[k] is the reference's moma_pos on entry; a seed joint at or beyond
+ * +-joint_pos_limit_max has no unconstrained image: TOPAY_ERR_INVALID_ARG, checked before any launch.  states[k] is the
+ * solution for a success code, else the seed; cost[k] the last evaluated cost; code[k] the raw L-BFGS code; iters[k], evals[k]
+ * the iterations and cost evaluations taken.  Outputs other than states may be NULL.  A problem's result does not depend on
+ * the others in the call or on its position among them.  topay_ee_ms: device time of the last call (HIP events). */
+topay_status topay_ee_goals(topay_ctx* ctx, int n, const int* map_ids, const double* seed_states /* n x 10 */, const double* ee_ref /* n x 9 */,
+                            const topay_ee_params_t* params, double* states /* n x 10 */, double* cost, int* code, int* iters, int* evals);
+topay_status topay_ee_ms(topay_ctx* ctx, double* ms);
+/* Seeds x targets into goals: per group g < n_groups the FIRST problem of smallest cost among those k with group_of[k] == g,
+ * a success code, |getFKPose(states[k]) - ee_ref[k]| <= pose_tol and, when require_collision_free, not isWholeBodyCollision
+ * on map_ids[k] (the check of topay_whole_body_collision).  winner[g] = its index and goal[g] = its state; winner[g] = -1 and
+ * goal[g] untouched where none qualifies.  goal is the array topay_plan_calls takes. */
+topay_status topay_ee_select(topay_ctx* ctx, int n, const int* map_ids, const int* group_of, int n_groups, const double* states /* n x 10 */,
+                             const double* cost, const int* code, const double* ee_ref /* n x 9 */, const topay_ee_params_t* params,
+                             int* winner, double* goal /* n_groups x 10 */);
+
 /* ompl::base::ReedsSheppStateSpace(rho) for n pose pairs (x, y, theta): distance[i] = distance(from_i, to_i), word[i] /
  * lengths[i][5] = the shortest path's segment word (0..17, OMPL's reedsSheppPathType numbering) and signed segment lengths
  * in units of rho, pose[i] = interpolate(from_i, to_i, t[i]) when t is given.  Output pointers may be NULL. */

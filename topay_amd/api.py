@@ -101,6 +101,12 @@ class WorldParams(C.Structure):
                 ("reserved", C.c_int)]
 
 
+class EeParams(C.Structure):
+    """topay_ee_params_t (include/topay.h): L-BFGS block, weights of eeCostCallback, what topay_ee_select asks of a goal."""
+    _fields_ = [("lbfgs", LbfgsParams), ("cost_scale", C.c_double), ("mani_colli_weight", C.c_double), ("self_colli_weight", C.c_double),
+                ("clearance_factor", C.c_double), ("pose_tol", C.c_double), ("require_collision_free", C.c_int), ("reserved", C.c_int)]
+
+
 c_u64p = C.POINTER(C.c_ulonglong)
 c_i8p = C.POINTER(C.c_int8)
 WORLD_STAGE_MS_KEYS = ["generation", "rasterisation", "fields", "sampling"]
@@ -182,6 +188,14 @@ def load(path=None):
         L.topay_replan_inputs.argtypes = [C.c_void_p, C.c_int, c_ip, c_dp, c_dp, c_dp, C.c_double, C.c_double, c_dp, c_dp, c_dp, c_ip]
         L.topay_replan_calls.argtypes = [C.c_void_p, C.c_int, c_ip, c_ip, c_dp, c_dp, c_dp, c_dp, C.c_double, C.c_double, C.c_double,
                                          C.POINTER(PlanParams), C.c_ulonglong, c_ip, c_dp, c_ip, c_ip]
+    if hasattr(L, "topay_ee_goals"):   # (older builds of the library under tools/libs, A/B runs)
+        L.topay_ee_default_params.argtypes = [C.POINTER(EeParams)]
+        L.topay_ee_default_params.restype = None
+        L.topay_ee_pose.argtypes = [C.c_void_p, C.c_int, c_dp, c_dp]
+        L.topay_ee_eval.argtypes = [C.c_void_p, C.c_int, c_ip, c_dp, c_dp, c_dp, c_dp]
+        L.topay_ee_goals.argtypes = [C.c_void_p, C.c_int, c_ip, c_dp, c_dp, C.POINTER(EeParams), c_dp, c_dp, c_ip, c_ip, c_ip]
+        L.topay_ee_ms.argtypes = [C.c_void_p, c_dp]
+        L.topay_ee_select.argtypes = [C.c_void_p, C.c_int, c_ip, c_ip, C.c_int, c_dp, c_dp, c_ip, c_dp, C.POINTER(EeParams), c_ip, c_dp]
     L.topay_reeds_shepp.argtypes = [C.c_void_p, C.c_int, c_dp, c_dp, c_dp, C.c_double, c_dp, c_ip, c_dp, c_dp]
     L.topay_dense_path.argtypes = [C.c_void_p, C.c_int, c_ip, c_dp, C.c_double, c_dp, c_dp, C.c_double, C.c_double, C.c_int, c_ip, c_dp]
     L.topay_connect_check_num.argtypes = [C.c_int, c_dp, c_dp, c_dp, C.c_double, c_ip]
@@ -1019,6 +1033,74 @@ class MomaTrajOptBatch:
                                                int(first_call), _ip(status), _dp(ends), _ip(res), _ip(cand)))
         self._note_plan_store(status[:, 2], res)
         return status, ends, res, cand
+
+    # ---- end-effector goals (MomaTrajOpt::optimizeEE) ----
+    def ee_params(self, **kw):
+        """EeParams with the defaults of topay_ee_default_params; lbfgs: a dict of fields of its L-BFGS block."""
+        p = EeParams()
+        self.L.topay_ee_default_params(C.byref(p))
+        for k, v in kw.items():
+            if k == "lbfgs":
+                for kk, vv in v.items():
+                    setattr(p.lbfgs, kk, vv)
+            else:
+                setattr(p, k, v)
+        return p
+
+    def ee_pose(self, states):
+        """getFKPose of [n, 10] states: [n, 9] = position, row 0, row 1 of the end effector's rotation."""
+        st = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 10)
+        out = np.zeros((len(st), 9))
+        _chk(self.L, self.L.topay_ee_pose(self.h, len(st), _dp(st), _dp(out)))
+        return out
+
+    @staticmethod
+    def _ee_mid(map_ids, n):
+        return None if map_ids is None else np.ascontiguousarray(np.broadcast_to(np.asarray(map_ids, dtype=np.int32), (n,)))
+
+    def ee_eval(self, x, ee_ref, map_ids=None):
+        """One eeCostCallback per problem at the unconstrained x [n, 10]: (f [n], g [n, 10])."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 10)
+        n = len(x)
+        ref = np.ascontiguousarray(ee_ref, dtype=np.float64).reshape(n, 9)
+        mid = self._ee_mid(map_ids, n)
+        f, g = np.zeros(n), np.zeros((n, 10))
+        _chk(self.L, self.L.topay_ee_eval(self.h, n, _ip(mid), _dp(x), _dp(ref), _dp(f), _dp(g)))
+        return f, g
+
+    def ee_goals(self, seed_states, ee_ref, map_ids=None, params=None):
+        """optimizeEE of n problems: (states [n, 10], cost [n], code [n], iters [n], evals [n])."""
+        seed = np.ascontiguousarray(seed_states, dtype=np.float64).reshape(-1, 10)
+        n = len(seed)
+        ref = np.ascontiguousarray(ee_ref, dtype=np.float64).reshape(n, 9)
+        mid = self._ee_mid(map_ids, n)
+        st, cost = np.zeros((n, 10)), np.zeros(n)
+        code, it, ev = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        _chk(self.L, self.L.topay_ee_goals(self.h, n, _ip(mid), _dp(seed), _dp(ref), None if params is None else C.byref(params), _dp(st), _dp(cost),
+                                           _ip(code), _ip(it), _ip(ev)))
+        return st, cost, code, it, ev
+
+    def ee_ms(self):
+        """Device time of the last ee_goals, milliseconds."""
+        ms = np.zeros(1)
+        _chk(self.L, self.L.topay_ee_ms(self.h, _dp(ms)))
+        return float(ms[0])
+
+    def ee_select(self, group_of, n_groups, states, cost, code, ee_ref, map_ids=None, params=None, goal=None):
+        """Per group the first qualified problem of smallest cost: (winner [n_groups], goal [n_groups, 10]); goal rows of groups
+        without a winner keep what `goal` held (zeros when not given)."""
+        st = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 10)
+        n = len(st)
+        grp = np.ascontiguousarray(group_of, dtype=np.int32)
+        co = np.ascontiguousarray(cost, dtype=np.float64)
+        cd = np.ascontiguousarray(code, dtype=np.int32)
+        ref = np.ascontiguousarray(ee_ref, dtype=np.float64).reshape(n, 9)
+        mid = self._ee_mid(map_ids, n)
+        win = np.zeros(n_groups, dtype=np.int32)
+        go = np.zeros((n_groups, 10)) if goal is None else np.array(goal, dtype=np.float64).reshape(n_groups, 10)
+        _chk(self.L, self.L.topay_ee_select(self.h, n, _ip(mid), _ip(grp), int(n_groups), _dp(st), _dp(co), _ip(cd), _dp(ref),
+                                            None if params is None else C.byref(params), _ip(win), _dp(go)))
+        return win, go
 
     def mcrrt_params(self, **kw):
         p = McrrtParams()

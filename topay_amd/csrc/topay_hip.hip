@@ -26,6 +26,7 @@
 #include "topay_topo.h"
 #include "topay_plan.h"
 #include "topay_track.h"
+#include "topay_ee.h"
 #include "topay_yaml.h"
 
 #include "topay_kernels.h"
@@ -41,3 +42,4 @@
 #include "topay_host_plan.h"
 #include "topay_host_world.h"
 #include "topay_host_track.h"
+#include "topay_host_ee.h"

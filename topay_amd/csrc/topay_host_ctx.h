@@ -297,6 +297,10 @@ struct topay_ctx {
   struct TrackSlot { topay::TrackDesc d[2] = {{0, 0, 0}, {0, 0, 0}}; long long cap[2] = {0, 0}; double T[2] = {0, 0}; };   // [0] end_traj, [1] global_traj
   std::vector<TrackSlot> tr_slots;
   double tr_safe_ms = 0.0;   // device time of the last k_track_safe launch
+  // end-effector goals (topay_host_ee.h): the L-BFGS history of the last topay_ee_goals (kept until the next call), the inputs /
+  // outputs of the ee kernels, the device time of the last topay_ee_goals
+  DevBuf ee_hist, ee_io;
+  double ee_ms = 0.0;
   DevBuf paths, path_off, path_len, bvel, bacc, scratch;
   DevBuf N, s1_past, map_id, head, tail, start_xy, goal_xy, init_xy, x0;
   DevBuf x, work, hist_s, hist_y, hist_ys, hist_alpha, lu;
