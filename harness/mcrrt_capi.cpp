@@ -6,6 +6,7 @@
 #include "topo_prm.hpp"
 #include "replan.hpp"
 #include "ee_goal.hpp"
+#include "prob_map.hpp"
 
 using namespace topay_wl;
 
@@ -227,6 +228,36 @@ int wl_ee_optimize(const double* origin, double res, const int* dims, const doub
   lp.mem_size = lbfgs[0]; lp.past = lbfgs[1]; lp.max_iterations = lbfgs[2]; lp.max_linesearch = lbfgs[3];
   lp.g_epsilon = g_epsilon; lp.delta = delta;
   return p.optimize(state10, lp, cost, out_int, out_int + 1);
+}
+
+// ---- sensor clouds' restatement (harness/prob_map.hpp) ----------------------------------------------------------------
+void* wl_pm_create(const double* origin, double res, const int* dims) {
+  prob_map::ProbMap* m = new prob_map::ProbMap();
+  m->reset(origin, res, dims);
+  return m;
+}
+void wl_pm_destroy(void* h) { delete (prob_map::ProbMap*)h; }
+// updateProbMap of one cloud (n points of x, y, z, intensity); returns 1 flushed, 0 batch open, -1 / -2 sensor above the ceiling / below the ground
+int wl_pm_update(void* h, int n, const float* xyzi, const double* sensor3, const prob_map::Params* params) {
+  return ((prob_map::ProbMap*)h)->update(xyzi, n, sensor3, *params);
+}
+void wl_pm_get(void* h, float* logodds, int* op_cnt, int* hit_cnt, int* batch_counter) {
+  const prob_map::ProbMap& m = *(prob_map::ProbMap*)h;
+  if (logodds) memcpy(logodds, m.occupancy_buffer.data(), m.occupancy_buffer.size() * sizeof(float));
+  if (op_cnt) memcpy(op_cnt, m.operation_cnt.data(), m.operation_cnt.size() * sizeof(int));
+  if (hit_cnt) memcpy(hit_cnt, m.hit_cnt.data(), m.hit_cnt.size() * sizeof(int));
+  if (batch_counter) *batch_counter = m.batch_update_counter;
+}
+void wl_pm_occupancy(void* h, const prob_map::Params* params, int8_t* occ2d, int8_t* occ2d_critical, int8_t* occ3d) {
+  ((prob_map::ProbMap*)h)->occupancy(prob_map::logit(params->p_occ), params->chassis_height, occ2d, occ2d_critical, occ3d);
+}
+void wl_pm_logodds(const prob_map::Params* p, float* l6) {
+  l6[0] = prob_map::logit(p->p_hit); l6[1] = prob_map::logit(p->p_miss); l6[2] = prob_map::logit(p->p_min);
+  l6[3] = prob_map::logit(p->p_max); l6[4] = prob_map::logit(p->p_occ); l6[5] = prob_map::logit(p->p_free);
+}
+void wl_pm_scan(const int8_t* occ3d, const double* origin, double res, const int* dims, const double* pose4, int n_az, int n_el, double fov,
+                double range, float* out) {
+  prob_map::scan(occ3d, origin, res, dims, pose4, n_az, n_el, fov, range, out);
 }
 
 }  // extern "C"

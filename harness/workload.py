@@ -324,8 +324,70 @@ def mlib():
         L.wl_ee_eval.argtypes = map_args + [c_dp, c_dp, c_dp, c_dp, c_ip, c_dp]
         L.wl_ee_eval.restype = C.c_double
         L.wl_ee_optimize.argtypes = map_args + [c_dp, c_dp, c_ip, C.c_double, C.c_double, c_dp, c_ip]
+        L.wl_pm_create.argtypes = [c_dp, C.c_double, c_ip]
+        L.wl_pm_create.restype = C.c_void_p
+        L.wl_pm_destroy.argtypes = [C.c_void_p]
+        L.wl_pm_destroy.restype = None
+        L.wl_pm_update.argtypes = [C.c_void_p, C.c_int, C.c_void_p, c_dp, C.c_void_p]
+        L.wl_pm_get.argtypes = [C.c_void_p, C.c_void_p, c_ip, c_ip, c_ip]
+        L.wl_pm_get.restype = None
+        L.wl_pm_occupancy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.wl_pm_occupancy.restype = None
+        L.wl_pm_logodds.argtypes = [C.c_void_p, C.c_void_p]
+        L.wl_pm_logodds.restype = None
+        L.wl_pm_scan.argtypes = [C.c_void_p, c_dp, C.c_double, c_ip, c_dp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]
+        L.wl_pm_scan.restype = None
         _MLIB = L
     return _MLIB
+
+
+class ProbMapCheck:
+    """The CPU checker of the sensor-cloud entries (harness/prob_map.hpp): one ProbMap on a grid.  params: a ctypes structure with
+    the layout of topay_sense_params_t (topay_amd.api.SenseParams)."""
+
+    def __init__(self, origin, res, dims):
+        self.origin = np.ascontiguousarray(origin, dtype=np.float64)
+        self.dims = np.ascontiguousarray(dims, dtype=np.int32)
+        self.res = float(res)
+        self.h = mlib().wl_pm_create(_dp(self.origin), self.res, self.dims.ctypes.data_as(c_ip))
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            mlib().wl_pm_destroy(self.h)
+            self.h = None
+
+    def update(self, cloud, sensor, params):
+        pts = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 4)
+        sp = np.ascontiguousarray(sensor, dtype=np.float64)
+        return mlib().wl_pm_update(self.h, len(pts), pts.ctypes.data, _dp(sp), C.addressof(params))
+
+    def get(self):
+        d = tuple(int(v) for v in self.dims)
+        lo, op, hit = np.zeros(d, dtype=np.float32), np.zeros(d, dtype=np.int32), np.zeros(d, dtype=np.int32)
+        bc = C.c_int(0)
+        mlib().wl_pm_get(self.h, lo.ctypes.data, op.ctypes.data_as(c_ip), hit.ctypes.data_as(c_ip), C.byref(bc))
+        return lo, op, hit, bc.value
+
+    def occupancy(self, params):
+        nx, ny, nz = (int(v) for v in self.dims)
+        o2, oc, o3 = np.zeros((nx, ny), dtype=np.int8), np.zeros((nx, ny), dtype=np.int8), np.zeros((nx, ny, nz), dtype=np.int8)
+        mlib().wl_pm_occupancy(self.h, C.addressof(params), o2.ctypes.data, oc.ctypes.data, o3.ctypes.data)
+        return o2, oc, o3
+
+
+def pm_logodds(params):
+    out = np.zeros(6, dtype=np.float32)
+    mlib().wl_pm_logodds(C.addressof(params), out.ctypes.data)
+    return out
+
+
+def pm_scan(occ3d, origin, res, dims, pose, n_az, n_el, fov, rng):
+    """The checker's range sensor for one pose (x, y, z, yaw): points float32[n_az * n_el, 4]."""
+    o3 = np.ascontiguousarray(occ3d, dtype=np.int8)
+    org, dm, ps = np.ascontiguousarray(origin, dtype=np.float64), np.ascontiguousarray(dims, dtype=np.int32), np.ascontiguousarray(pose, dtype=np.float64)
+    out = np.zeros((n_az * n_el, 4), dtype=np.float32)
+    mlib().wl_pm_scan(o3.ctypes.data, _dp(org), float(res), dm.ctypes.data_as(c_ip), _dp(ps), n_az, n_el, float(fov), float(rng), out.ctypes.data)
+    return out
 
 
 class EeGoal:

@@ -670,6 +670,82 @@ topay_status topay_ee_select(topay_ctx* ctx, int n, const int* map_ids, const in
                              const double* cost, const int* code, const double* ee_ref /* n x 9 */, const topay_ee_params_t* params,
                              int* winner, double* goal /* n_groups x 10 */);
 
+/* ---- Sensor clouds into the map: rog_map's ProbMap on the grid of a map slot ------------------------------------------------
+ * ProbMap::updateProbMap (src/rog_map/src/rog_map/prob_map.cpp:302-373) with raycastProcess (666-779), probabilisticMapFromCache
+ * (544-568), hitPointUpdate / missPointUpdate (570-664), insertUpdateCandidate / updateLocalBox (781-822), RayCaster
+ * (src/rog_map/include/utils/raycaster.cpp:65-192) and lineBoxIntersectPoint (include/utils/common_lib.hpp:148-170): the map
+ * real-robot mode plans on (grid_map.cpp:20-26), as a per-slot occupancy belief.  Clouds are inserted on the device, occupancy
+ * grids are derived from the belief and the slot's five fields rebuilt from them, so that the map can change under a committed
+ * trajectory (topay_track_safe) without the host touching a voxel.
+ * Configuration restated: raycasting/enable true, map_sliding/enable false, esdf/enable false, frontier_extraction_en false, no
+ * inflation map, no kd-tree.  Left out: the sliding window and its hash; the InfMap / CounterMap counters; ESDFMap::updateESDF3D
+ * (the slot's fields come from the exact builder of topay_build_esdf_fields); the first-frame block that clears a sphere of
+ * raycast_range_min around the robot (prob_map.cpp:356-372), a no-op at the shipped ray_range [0.0, 5]: ray_range[0] > 0 is
+ * refused with TOPAY_ERR_UNSUPPORTED.
+ * Grid: the slot's topay_map_desc_t, i.e. GridMap::init's origin, dims and resolution; points are in the map's world frame.  A
+ * position is moved into the grid's frame first, u = p - origin, and the reference's code runs on u: voxel floor(u / resolution),
+ * centre at + 0.5.  That is the reference's ORIGIN_AT_CORNER branch, the one its CMakeLists.txt:14 selects; its local map is the
+ * voxels 0 .. dims - 1 and its local-map bounds the centres of the first and last voxel (sliding_map.cpp:93-95).
+ * Belief: one float of log-odds per voxel.  A fresh voxel holds 0 (occupancy_buffer_.resize(map_size, 0), prob_map.cpp:78), which
+ * is unknown: l_free <= 0 < l_occ for p_free < 0.5 < p_occ.  isOccupied: l >= l_occ; isKnownFree: l < l_free; unknown between
+ * (prob_map.h:125-135).  l_x = logit(p_x) as config.hpp:229-235 computes it from the float p_x: the quotient x / (1 - x) in float,
+ * the logarithm of that float in double, rounded to float.
+ * Counts: per voxel and batch an operation count and a hit count (16 bits each); the flush adds l_hit * hits where there are hits
+ * ("hit wins", prob_map.cpp:558-564), else l_miss * operations, once, and clamps: the belief does not depend on the order of the
+ * points beyond what point_filt_num makes of it.  A batch may count at most 32767 rays per slot (a ray counts a voxel at most
+ * twice; ceil(points / point_filt_num) per cloud is what is added up): TOPAY_ERR_INVALID_ARG for a cloud that could exceed it.
+ * The intensity filter is the reference's: applied only when intensity_thresh > 0 (prob_map.cpp:688), and point_filt_num counts
+ * the points that passed it.  point_filt_num and batch_update_size below 1 are 1 (config.hpp:180-194).  A point with a NaN or an
+ * infinite coordinate is counted by the filters and casts no ray. */
+typedef struct {
+  float p_min, p_miss, p_free, p_occ, p_hit, p_max;            /* .12 .49 .499 .85 .9 .98  (params/rog_map.yaml, raycasting/) */
+  double ray_range[2];                                         /* 0, 5 */
+  int point_filt_num, batch_update_size, intensity_thresh;     /* 15, 1, -10 */
+  int reserved;
+  double virtual_ceil_height, virtual_ground_height;           /* 9999, -9999 */
+  double local_update_box[3];                                  /* 50, 50, 5 */
+  double chassis_height;                                       /* 0.155 (MomaParam): the 2-D rule of topay_sense_commit */
+} topay_sense_params_t;
+topay_status topay_sense_default_params(topay_sense_params_t* p);
+/* The six log-odds of a parameter block, as the library computes them: l_hit, l_miss, l_min, l_max, l_occ, l_free. */
+topay_status topay_sense_logodds(const topay_sense_params_t* p, float* l6);
+/* Allocates or clears the beliefs of the n slots map_ids[k] on the grid `desc`: every voxel unknown, counts zero, batch counter
+ * zero.  The slot's fields (if any) are not touched: a belief is state beside the map until topay_sense_commit. */
+topay_status topay_sense_reset(topay_ctx* ctx, int n, const int* map_ids, const topay_map_desc_t* desc);
+/* One updateProbMap per slot, all clouds of the call in one set of launches.  Slot k's cloud is points cloud_off[k] ..
+ * cloud_off[k + 1] - 1 of points_xyzi (x, y, z, intensity as four floats per point; empty clouds are legal), seen from
+ * sensor_pos[k] (3 doubles).  points_xyzi may be TOPAY_SENSE_LAST_SCAN: the points of the context's last topay_sense_scan, which
+ * are on the device already (cloud_off then indexes that call's output).
+ *   status[k] (may be NULL)  1 inserted and flushed, 0 inserted, the batch is still open (batch_update_size), -1 / -2 the sensor is
+ *                            above the virtual ceiling / below the virtual ground: nothing changes (prob_map.cpp:313-322)
+ * TOPAY_ERR_INVALID_ARG: a slot named twice (the batch counter is per slot), offsets that decrease, parameters out of range, a
+ * sensor that is not finite or more than 1e6 m from the map's origin; TOPAY_ERR_NO_MAP: a slot without a belief. */
+#define TOPAY_SENSE_LAST_SCAN ((const float*)(uintptr_t)1)
+topay_status topay_sense_insert(topay_ctx* ctx, int n, const int* map_ids, const int* cloud_off /* n + 1 */, const float* points_xyzi,
+                                const double* sensor_pos /* n x 3 */, const topay_sense_params_t* params, int* status /* n, optional */);
+/* The belief into the map: occ3d = isOccupied (unknown counts as free, as ProbMap's own query does), occ2d_critical its
+ * projection over z, occ2d = 1 where an occupied voxel's centre is below chassis_height (GridMap::cloudCallback, grid_map.cpp:
+ * 554-568, with the voxel centre as the point); l_occ and chassis_height are those of the slot's last insert (the defaults before
+ * the first).  Then the five fields through the code of topay_build_esdf_fields, device to device: the slot reads as if that
+ * entry had been called with these grids, sharers of the slot are invalidated as for any refill (topay_share_maps), and
+ * topay_get_occupancy serves the slots of the last topay_sense_commit.  A slot may be named once. */
+topay_status topay_sense_commit(topay_ctx* ctx, int n, const int* map_ids);
+/* The parity hook: the belief of a slot as it is, [nx][ny][nz] each.  Any pointer may be NULL. */
+topay_status topay_sense_get(topay_ctx* ctx, int map_id, float* logodds, int* op_cnt, int* hit_cnt, int* batch_counter);
+/* A range sensor on the device, so that an episode can be driven without the host: NOT a restatement (the reference's
+ * pointcloud_render_node needs PCL).  Per pose (x, y, z, yaw) n_az x n_el rays through the resident occ3d of truth_map_ids[k] (a
+ * slot topay_get_occupancy serves): ray i * n_el + j has azimuth 2 pi i / n_az + yaw and elevation fov ((j + 0.5) / n_el - 0.5)
+ * (the library's deterministic sin / cos) and is traversed over `range` with the inserter's RayCaster.  Its point is the centre of
+ * the first occupied voxel, the pose's own included; a ray that leaves the map or ends without one gives the point at 1.5 range
+ * along it, so that an inserter with ray_range[1] <= range clamps it and records misses only.  Intensity 0.  Point k of pose p is
+ * written at p * n_az * n_el + k, without compaction: cloud_off[p] = p * n_az * n_el (n + 1 entries, may be NULL).  The points
+ * stay on the device for topay_sense_insert (TOPAY_SENSE_LAST_SCAN); points (cloud_cap points of 4 floats, may be NULL) receives
+ * a copy. */
+topay_status topay_sense_scan(topay_ctx* ctx, int n, const int* truth_map_ids, const double* poses /* n x 4 */, int n_az, int n_el, double fov,
+                              double range, int cloud_cap, int* cloud_off, float* points);
+/* Device time (HIP events) of the last scan, insert (selection and rays), flush, and commit with its fields, in ms. */
+topay_status topay_sense_ms(topay_ctx* ctx, double ms[4]);
+
 /* ompl::base::ReedsSheppStateSpace(rho) for n pose pairs (x, y, theta): distance[i] = distance(from_i, to_i), word[i] /
  * lengths[i][5] = the shortest path's segment word (0..17, OMPL's reedsSheppPathType numbering) and signed segment lengths
  * in units of rho, pose[i] = interpolate(from_i, to_i, t[i]) when t is given.  Output pointers may be NULL. */

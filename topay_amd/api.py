@@ -107,6 +107,17 @@ class EeParams(C.Structure):
                 ("clearance_factor", C.c_double), ("pose_tol", C.c_double), ("require_collision_free", C.c_int), ("reserved", C.c_int)]
 
 
+class SenseParams(C.Structure):
+    """topay_sense_params_t (include/topay.h): ProbMap's parameters (params/rog_map.yaml) and the chassis height of the 2-D rule."""
+    _fields_ = [("p_min", C.c_float), ("p_miss", C.c_float), ("p_free", C.c_float), ("p_occ", C.c_float), ("p_hit", C.c_float),
+                ("p_max", C.c_float), ("ray_range", C.c_double * 2), ("point_filt_num", C.c_int), ("batch_update_size", C.c_int),
+                ("intensity_thresh", C.c_int), ("reserved", C.c_int), ("virtual_ceil_height", C.c_double),
+                ("virtual_ground_height", C.c_double), ("local_update_box", C.c_double * 3), ("chassis_height", C.c_double)]
+
+
+c_fp = C.POINTER(C.c_float)
+SENSE_LAST_SCAN = "last_scan"   # sense_insert: the points of the last sense_scan, on the device (TOPAY_SENSE_LAST_SCAN)
+SENSE_MS_KEYS = ["scan", "insert", "flush", "commit"]
 c_u64p = C.POINTER(C.c_ulonglong)
 c_i8p = C.POINTER(C.c_int8)
 WORLD_STAGE_MS_KEYS = ["generation", "rasterisation", "fields", "sampling"]
@@ -224,6 +235,15 @@ def load(path=None):
         L.topay_sample_scenarios.argtypes = [C.c_void_p, C.c_int, c_ip, c_u64p, c_dp, c_dp, c_ip]
         L.topay_generate_episodes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(WorldParams), c_u64p, c_ip, c_dp, c_dp, c_ip]
         L.topay_test_mt64.argtypes = [C.c_ulonglong, C.c_int, C.c_int, c_u64p]
+    if hasattr(L, "topay_sense_insert"):   # (older builds of the library under tools/libs, A/B runs)
+        L.topay_sense_default_params.argtypes = [C.POINTER(SenseParams)]
+        L.topay_sense_logodds.argtypes = [C.POINTER(SenseParams), c_fp]
+        L.topay_sense_reset.argtypes = [C.c_void_p, C.c_int, c_ip, C.POINTER(MapDesc)]
+        L.topay_sense_insert.argtypes = [C.c_void_p, C.c_int, c_ip, c_ip, C.c_void_p, c_dp, C.POINTER(SenseParams), c_ip]
+        L.topay_sense_commit.argtypes = [C.c_void_p, C.c_int, c_ip]
+        L.topay_sense_get.argtypes = [C.c_void_p, C.c_int, c_fp, c_ip, c_ip, c_ip]
+        L.topay_sense_scan.argtypes = [C.c_void_p, C.c_int, c_ip, c_dp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, c_ip, c_fp]
+        L.topay_sense_ms.argtypes = [C.c_void_p, c_dp]
     L.topay_get_total_durations.argtypes = [C.c_void_p, c_dp]
     L.topay_check_feasible.argtypes = [C.c_void_p, c_ip]
     L.topay_feasibility_report.argtypes = [C.c_void_p, c_ip, c_ip, c_dp]
@@ -755,6 +775,93 @@ class MomaTrajOptBatch:
                 break
             att[todo] += 1
         return start, goal, status, att
+
+    # ---- sensor clouds into the map (topay_sense_*: rog_map's ProbMap on a slot's grid) -------------------------------
+    def sense_params(self, **kw):
+        """topay_sense_default_params (params/rog_map.yaml) with the given fields replaced."""
+        p = SenseParams()
+        _chk(self.L, self.L.topay_sense_default_params(C.byref(p)))
+        for k, v in kw.items():
+            if isinstance(v, (list, tuple, np.ndarray)):
+                for i, x in enumerate(v):
+                    getattr(p, k)[i] = x
+            else:
+                setattr(p, k, v)
+        return p
+
+    def sense_logodds(self, params=None):
+        """l_hit, l_miss, l_min, l_max, l_occ, l_free of a parameter block as the library computes them (float32[6])."""
+        out = np.zeros(6, dtype=np.float32)
+        _chk(self.L, self.L.topay_sense_logodds(C.byref(params or self.sense_params()), out.ctypes.data_as(c_fp)))
+        return out
+
+    def sense_reset(self, map_ids, origin, res, dims, min_b, max_b):
+        """topay_sense_reset: the beliefs of the slots map_ids on one grid, all unknown."""
+        d = MapDesc()
+        for i in range(3):
+            d.origin[i], d.dims[i], d.min_boundary[i], d.max_boundary[i] = origin[i], int(dims[i]), min_b[i], max_b[i]
+        d.resolution = res
+        ids = np.ascontiguousarray(map_ids, dtype=np.int32).reshape(-1)
+        _chk(self.L, self.L.topay_sense_reset(self.h, len(ids), _ip(ids), C.byref(d)))
+        if not hasattr(self, "_sense_dims"):
+            self._sense_dims = {}
+        for m in ids:
+            self._sense_dims[int(m)] = tuple(int(v) for v in dims)
+
+    def sense_insert(self, map_ids, clouds, sensor_pos, params=None, cloud_off=None):
+        """topay_sense_insert: one updateProbMap per slot.  clouds: a list of [k, 4] float32 arrays (x, y, z, intensity), one per
+        slot, or SENSE_LAST_SCAN with the cloud_off sense_scan returned.  Returns status[n]: 1 flushed, 0 batch open, -1 / -2 the
+        sensor is above the ceiling / below the ground."""
+        ids = np.ascontiguousarray(map_ids, dtype=np.int32).reshape(-1)
+        n = len(ids)
+        sp = np.ascontiguousarray(sensor_pos, dtype=np.float64).reshape(n, 3)
+        if isinstance(clouds, str) and clouds == SENSE_LAST_SCAN:
+            off = np.ascontiguousarray(cloud_off, dtype=np.int32)
+            ptr = C.c_void_p(1)
+        else:
+            cl = [np.ascontiguousarray(c, dtype=np.float32).reshape(-1, 4) for c in clouds]
+            off = np.concatenate([[0], np.cumsum([len(c) for c in cl])]).astype(np.int32)
+            pts = np.ascontiguousarray(np.concatenate(cl) if cl else np.zeros((0, 4)), dtype=np.float32)
+            ptr = C.c_void_p(pts.ctypes.data) if len(pts) else C.c_void_p(None)
+        assert len(off) == n + 1
+        st = np.zeros(n, dtype=np.int32)
+        _chk(self.L, self.L.topay_sense_insert(self.h, n, _ip(ids), _ip(off), ptr, _dp(sp), C.byref(params or self.sense_params()), _ip(st)))
+        return st
+
+    def sense_commit(self, map_ids):
+        """topay_sense_commit: occupancy grids from the beliefs, then the five fields of each slot, on the device."""
+        ids = np.ascontiguousarray(map_ids, dtype=np.int32).reshape(-1)
+        _chk(self.L, self.L.topay_sense_commit(self.h, len(ids), _ip(ids)))
+        for m in ids:
+            self._map_dims[int(m)] = self._sense_dims[int(m)]
+
+    def sense_get(self, map_id):
+        """The belief of a slot: (logodds float32, op_cnt, hit_cnt int32, each [nx, ny, nz], batch_counter)."""
+        dims = self._sense_dims[int(map_id)]
+        lo = np.zeros(dims, dtype=np.float32)
+        op, hit = np.zeros(dims, dtype=np.int32), np.zeros(dims, dtype=np.int32)
+        bc = C.c_int(0)
+        _chk(self.L, self.L.topay_sense_get(self.h, int(map_id), lo.ctypes.data_as(c_fp), _ip(op), _ip(hit), C.byref(bc)))
+        return lo, op, hit, bc.value
+
+    def sense_scan(self, truth_map_ids, poses, n_az, n_el, fov, rng, copy_back=True):
+        """topay_sense_scan: n_az x n_el rays per pose (x, y, z, yaw) through the resident occ3d of the truth slots.  Returns
+        (cloud_off int32[n + 1], points float32[n, n_az * n_el, 4] or None); the points stay on the device for
+        sense_insert(..., SENSE_LAST_SCAN, cloud_off=cloud_off)."""
+        ids = np.ascontiguousarray(truth_map_ids, dtype=np.int32).reshape(-1)
+        n = len(ids)
+        ps = np.ascontiguousarray(poses, dtype=np.float64).reshape(n, 4)
+        off = np.zeros(n + 1, dtype=np.int32)
+        pts = np.zeros((n, n_az * n_el, 4), dtype=np.float32) if copy_back else None
+        _chk(self.L, self.L.topay_sense_scan(self.h, n, _ip(ids), _dp(ps), int(n_az), int(n_el), float(fov), float(rng), n * n_az * n_el, _ip(off),
+                                             pts.ctypes.data_as(c_fp) if copy_back else None))
+        return off, pts
+
+    def sense_ms(self):
+        """Device time of the last scan, insert, flush and commit (with its fields) in ms."""
+        ms = np.zeros(4)
+        _chk(self.L, self.L.topay_sense_ms(self.h, _dp(ms)))
+        return dict(zip(SENSE_MS_KEYS, ms.tolist()))
 
     def playback(self, i, times):
         """MomaTraj playback of candidate i: (states[len(times), 10], car_seq[n, 4])."""

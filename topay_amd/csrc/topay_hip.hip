@@ -31,6 +31,7 @@
 
 #include "topay_kernels.h"
 #include "topay_world.h"
+#include "topay_sense.h"
 
 // host side, in this order: each header uses what the ones before it define
 #include "topay_host_ctx.h"
@@ -43,3 +44,4 @@
 #include "topay_host_world.h"
 #include "topay_host_track.h"
 #include "topay_host_ee.h"
+#include "topay_host_sense.h"

@@ -314,6 +314,24 @@ struct topay_ctx {
   int world_force_path = 0, world_max_tries = 0;   // test hooks: 2 = byte stores whatever the map; tries per arm of an episode (0: 2000)
   hipEvent_t world_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // stage bounds 0..3, the sampler's launch 4, 5
   double world_ms[4] = {0, 0, 0, 0};
+  // sensor clouds (topay_host_sense.h): per map slot the belief (log-odds, packed counts and cache box in one block), the batch
+  // counter, the rays counted since the last flush and the parameters of the last
+  // insert (topay_sense_commit reads l_occ and chassis_height from them); the uploads of a call; the points of the last
+  // topay_sense_scan; the occupancy grids of the last topay_sense_commit and where each slot's lie in them (topay_get_occupancy)
+  struct SenseBelief {
+    DevBuf buf;
+    float* logodds = nullptr; int* cnt = nullptr; int* box = nullptr;
+    topay_map_desc_t desc;
+    topay_sense_params_t prm;
+    int batch_counter = 0, pending_rays = 0;
+    size_t occ3_off = 0, occ2_off = 0, occ2c_off = 0;
+    bool have = false, have_occ = false;
+  };
+  std::vector<SenseBelief> sense;   // sized by the first topay_sense_reset
+  DevBuf sense_pts, sense_io, sense_scan, sense_occ;
+  size_t sense_scan_points = 0;
+  hipEvent_t sense_ev[2] = {nullptr, nullptr};
+  double sense_ms[4] = {0, 0, 0, 0};   // scan, insert, flush, commit with the fields
   int trace_cap = 0;
   DevBatch db;
   bool have_traj = false, solved = false;
@@ -533,6 +551,7 @@ static void drop_shared_slots(topay_ctx* c, int first, int n) {
 
 // slots [first, first + n) are refilled by something else than the world generator: its occupancy grids no longer describe them
 static void world_forget(topay_ctx* c, int first, int n) {
+  for (int m = first; m < first + n && m < (int)c->sense.size(); m++) c->sense[m].have_occ = false;   // ... nor do the last commit's
   if (c->world_n > 0 && first < c->world_first + c->world_n && c->world_first < first + n) {
     c->world_n = 0;
     c->world_occ.release();
@@ -671,6 +690,8 @@ void topay_destroy(topay_ctx* c) {
   (void)hipSetDevice(c->device);
   for (hipEvent_t e : c->plan.events) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->world_ev)
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->sense_ev)
     if (e) (void)hipEventDestroy(e);
   for (int k = 0; k < topay_ctx::NBUCKET; k++) {
     if (c->bevent[k]) (void)hipEventDestroy(c->bevent[k]);

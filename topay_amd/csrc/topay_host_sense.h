@@ -1,0 +1,407 @@
+// Host side of the C-ABI, part 11: sensor clouds into the map (topay_sense.h) -- the beliefs of the map slots, insertion, the
+// hand-over of the derived occupancy grids to the field construction (topay_host_maps.h), the range sensor.
+
+#pragma once
+
+// logit of config.hpp:229: the quotient in float, its logarithm in double, rounded to float
+static float sense_logit(float x) { return (float)std::log((double)(x / (1.0f - x))); }
+
+static topay_status sense_make_params(const topay_sense_params_t* p, SenseP& P) {
+  const float pr[6] = {p->p_hit, p->p_miss, p->p_min, p->p_max, p->p_occ, p->p_free};
+  for (float v : pr)
+    if (!(v > 0.0f && v < 1.0f)) { set_err("topay_sense: a probability outside (0, 1)"); return TOPAY_ERR_INVALID_ARG; }
+  if (!(p->ray_range[0] >= 0.0) || !(p->ray_range[1] > 0.0) || !(p->ray_range[1] <= 1.0e6) || !(p->ray_range[0] <= p->ray_range[1])) {
+    set_err("topay_sense: ray_range must be 0 <= min <= max, 0 < max <= 1e6");
+    return TOPAY_ERR_INVALID_ARG;
+  }
+  if (p->ray_range[0] > 0.0) {
+    set_err("topay_sense: ray_range[0] > 0 needs the first-frame clearing of prob_map.cpp:356-372, which is not restated");
+    return TOPAY_ERR_UNSUPPORTED;
+  }
+  if (!(p->virtual_ground_height <= p->virtual_ceil_height) || !(p->chassis_height == p->chassis_height)) return TOPAY_ERR_INVALID_ARG;
+  memset(&P, 0, sizeof(P));
+  P.l_hit = sense_logit(p->p_hit); P.l_miss = sense_logit(p->p_miss); P.l_min = sense_logit(p->p_min);
+  P.l_max = sense_logit(p->p_max); P.l_occ = sense_logit(p->p_occ); P.l_free = sense_logit(p->p_free);
+  P.range_min = p->ray_range[0]; P.range_max = p->ray_range[1];
+  P.sqr_range_max = P.range_max * P.range_max;   // config.hpp:212
+  P.ceil_height = p->virtual_ceil_height; P.ground_height = p->virtual_ground_height;
+  P.filt = p->point_filt_num > 0 ? p->point_filt_num : 1;   // config.hpp:180-184
+  P.thresh = p->intensity_thresh;
+  return TOPAY_OK;
+}
+// half_local_update_box_i = (local_update_box_d / 2 / resolution).cast<int>() (config.hpp:378-379)
+static topay_status sense_half_box(const topay_sense_params_t* p, double res, SenseP& P) {
+  for (int a = 0; a < 3; a++) {
+    const double h = p->local_update_box[a] / 2 / res;
+    if (!(h >= 0.0) || !(h < 1.0e9)) { set_err("topay_sense: local_update_box out of range"); return TOPAY_ERR_INVALID_ARG; }
+    P.half_box[a] = (int)h;
+  }
+  return TOPAY_OK;
+}
+static topay_status sense_events(topay_ctx* c) {
+  for (hipEvent_t& e : c->sense_ev)
+    if (!e) HIPCHK(hipEventCreate(&e));
+  return TOPAY_OK;
+}
+static topay_status sense_elapsed(topay_ctx* c, int which) {
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, c->sense_ev[0], c->sense_ev[1]));
+  c->sense_ms[which] = ms;
+  return TOPAY_OK;
+}
+// the slots of a call: in range, each once
+static topay_status sense_check_ids(int n, const int* map_ids) {
+  std::vector<char> seen(TOPAY_MAX_MAPS, 0);
+  for (int k = 0; k < n; k++) {
+    const int m = map_ids[k];
+    if (m < 0 || m >= TOPAY_MAX_MAPS) return TOPAY_ERR_INVALID_ARG;
+    if (seen[m]) { set_err("topay_sense: map slot " + std::to_string(m) + " named twice in one call"); return TOPAY_ERR_INVALID_ARG; }
+    seen[m] = 1;
+  }
+  return TOPAY_OK;
+}
+// the occupancy grid a scan reads: a slot of the last topay_sense_commit or of the last world generation
+static const signed char* sense_truth_occ3(topay_ctx* c, int m, int* dims) {
+  if (m >= 0 && m < (int)c->sense.size() && c->sense[m].have_occ) {
+    for (int a = 0; a < 3; a++) dims[a] = c->sense[m].desc.dims[a];
+    return c->sense_occ.as<signed char>() + c->sense[m].occ3_off;
+  }
+  if (c->world_n > 0 && m >= c->world_first && m < c->world_first + c->world_n && c->world_occ.p) {
+    for (int a = 0; a < 3; a++) dims[a] = c->world_dims[a];
+    const size_t n3 = (size_t)dims[0] * dims[1] * dims[2];
+    return c->world_occ.as<signed char>() + (size_t)(m - c->world_first) * n3;
+  }
+  return nullptr;
+}
+
+extern "C" {
+
+topay_status topay_sense_default_params(topay_sense_params_t* p) {
+  if (!p) return TOPAY_ERR_INVALID_ARG;
+  memset(p, 0, sizeof(*p));
+  // src/planner/params/rog_map.yaml
+  p->p_min = 0.12f; p->p_miss = 0.49f; p->p_free = 0.499f; p->p_occ = 0.85f; p->p_hit = 0.9f; p->p_max = 0.98f;
+  p->ray_range[0] = 0.0; p->ray_range[1] = 5.0;
+  p->point_filt_num = 15; p->batch_update_size = 1; p->intensity_thresh = -10;
+  p->virtual_ceil_height = 9999.0; p->virtual_ground_height = -9999.0;
+  p->local_update_box[0] = 50.0; p->local_update_box[1] = 50.0; p->local_update_box[2] = 5.0;
+  p->chassis_height = 0.155;   // moma_param.h
+  return TOPAY_OK;
+}
+
+topay_status topay_sense_logodds(const topay_sense_params_t* p, float* l6) {
+  if (!p || !l6) return TOPAY_ERR_INVALID_ARG;
+  SenseP P;
+  if (topay_status s = sense_make_params(p, P)) return s;
+  l6[0] = P.l_hit; l6[1] = P.l_miss; l6[2] = P.l_min; l6[3] = P.l_max; l6[4] = P.l_occ; l6[5] = P.l_free;
+  return TOPAY_OK;
+}
+
+topay_status topay_sense_reset(topay_ctx* c, int n, const int* map_ids, const topay_map_desc_t* desc) {
+  if (!c || n <= 0 || !map_ids || !desc || !(desc->resolution > 0.0)) return TOPAY_ERR_INVALID_ARG;
+  if (topay_status s = sense_check_ids(n, map_ids)) return s;
+  if (topay_status s = map_dims_check(desc)) return s;
+  HIPCHK(hipSetDevice(c->device));
+  if (c->sense.empty()) c->sense.resize(TOPAY_MAX_MAPS);
+  const size_t n3 = (size_t)desc->dims[0] * desc->dims[1] * desc->dims[2];
+  const int empty_box[6] = {0x7f7f7f7f, 0x7f7f7f7f, 0x7f7f7f7f, 0x7f7f7f7f, 0x7f7f7f7f, 0x7f7f7f7f};
+  for (int k = 0; k < n; k++) {
+    topay_ctx::SenseBelief& b = c->sense[map_ids[k]];
+    b.have = false;
+    auto lay = [&](Carver& q) { b.logodds = q.take<float>(n3); b.cnt = q.take<int>(n3); b.box = q.take<int>(8); };
+    if (topay_status s = b.buf.carve(lay)) return s;
+    HIPCHK(hipMemsetAsync(b.logodds, 0, n3 * 8, c->stream));   // log-odds 0 (prob_map.cpp:78) and the counts behind them
+    HIPCHK(h2d(c, b.box, empty_box, 6));
+    b.desc = *desc;
+    topay_sense_default_params(&b.prm);
+    b.prm.chassis_height = c->hp.chassis_height;
+    b.batch_counter = 0; b.pending_rays = 0;
+    b.have = true;
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));   // (empty_box is on this stack)
+  return TOPAY_OK;
+}
+
+topay_status topay_sense_insert(topay_ctx* c, int n, const int* map_ids, const int* cloud_off, const float* points_xyzi, const double* sensor_pos,
+                                const topay_sense_params_t* params, int* status) {
+  if (!c || n <= 0 || !map_ids || !cloud_off || !sensor_pos || !params) return TOPAY_ERR_INVALID_ARG;
+  topay_status s;
+  if ((s = sense_check_ids(n, map_ids)) != TOPAY_OK) return s;
+  SenseP P;
+  if ((s = sense_make_params(params, P)) != TOPAY_OK) return s;
+  const int batch_size = params->batch_update_size > 0 ? params->batch_update_size : 1;   // config.hpp:190-194
+  const bool from_scan = points_xyzi == TOPAY_SENSE_LAST_SCAN;
+  if (cloud_off[0] < 0) return TOPAY_ERR_INVALID_ARG;
+  for (int k = 0; k < n; k++)
+    if (cloud_off[k + 1] < cloud_off[k]) return TOPAY_ERR_INVALID_ARG;
+  const size_t total = (size_t)cloud_off[n];
+  if (total > 0 && !points_xyzi) return TOPAY_ERR_INVALID_ARG;
+  if (from_scan && total > c->sense_scan_points) { set_err("topay_sense_insert: offsets beyond the points of the last topay_sense_scan"); return TOPAY_ERR_INVALID_ARG; }
+  for (int k = 0; k < n; k++)
+    if (map_ids[k] >= (int)c->sense.size() || !c->sense[map_ids[k]].have) { set_err("topay_sense_insert: slot without a belief (topay_sense_reset)"); return TOPAY_ERR_NO_MAP; }
+  // per slot: the descriptor, the rays this cloud can add to the batch, the voxel box a flush has to cover
+  std::vector<SenseSlot> hs((size_t)n);
+  std::vector<int> h_nsurv((size_t)n), st((size_t)n, 0);
+  int max_rays = 0, max_len = 0;
+  long long max_fvol = 0;
+  bool any_flush = false;
+  for (int k = 0; k < n; k++) {
+    topay_ctx::SenseBelief& b = c->sense[map_ids[k]];
+    SenseSlot& S = hs[(size_t)k];
+    memset(&S, 0, sizeof(S));
+    if (k == 0) { if ((s = sense_half_box(params, b.desc.resolution, P)) != TOPAY_OK) return s; }
+    else if (b.desc.resolution != c->sense[map_ids[0]].desc.resolution) { set_err("topay_sense_insert: the slots of a call share one resolution"); return TOPAY_ERR_INVALID_ARG; }
+    const double* sp = sensor_pos + 3 * (size_t)k;
+    for (int a = 0; a < 3; a++) {
+      if (!(std::fabs(sp[a] - b.desc.origin[a]) <= 1.0e6)) { set_err("topay_sense_insert: sensor position not finite or more than 1e6 m from the map"); return TOPAY_ERR_INVALID_ARG; }
+      S.origin[a] = b.desc.origin[a]; S.dims[a] = b.desc.dims[a]; S.sensor[a] = sp[a];
+    }
+    S.res = b.desc.resolution; S.res_inv = 1.0 / b.desc.resolution;
+    S.logodds = b.logodds; S.cnt = b.cnt; S.box = b.box;
+    S.cloud_begin = cloud_off[k]; S.cloud_len = cloud_off[k + 1] - cloud_off[k];
+    if (sp[2] > params->virtual_ceil_height) st[(size_t)k] = -1;
+    else if (sp[2] < params->virtual_ground_height) st[(size_t)k] = -2;
+    S.skip = st[(size_t)k] < 0;
+    const int rays = S.skip ? 0 : (S.cloud_len + P.filt - 1) / P.filt;
+    if (b.pending_rays + rays > TOPAY_SENSE_MAX_BATCH_RAYS) {
+      set_err("topay_sense_insert: slot " + std::to_string(map_ids[k]) + " would count more than " + std::to_string(TOPAY_SENSE_MAX_BATCH_RAYS) +
+              " rays in one batch (16-bit counts per voxel)");
+      return TOPAY_ERR_INVALID_ARG;
+    }
+    h_nsurv[(size_t)k] = rays;
+    max_rays = std::max(max_rays, rays);
+    max_len = std::max(max_len, S.skip ? 0 : S.cloud_len);
+  }
+  // What the call does to each slot's host state, worked out beside it: nothing of a slot moves before every check, allocation
+  // and upload of the call has succeeded.
+  struct Next { int batch_counter, pending_rays; };
+  std::vector<Next> nx((size_t)n);
+  long long max_vol = 0;   // the largest grid of the call: no cache box is larger
+  for (int k = 0; k < n; k++) {
+    const topay_ctx::SenseBelief& b = c->sense[map_ids[k]];
+    SenseSlot& S = hs[(size_t)k];
+    Next& N = nx[(size_t)k];
+    N.batch_counter = b.batch_counter; N.pending_rays = b.pending_rays;
+    if (S.skip) continue;
+    N.pending_rays += h_nsurv[(size_t)k];
+    N.batch_counter++;
+    if (N.batch_counter >= batch_size) {   // prob_map.cpp:340-341
+      N.batch_counter = 0;
+      N.pending_rays = 0;
+      S.flush = 1;
+      st[(size_t)k] = 1;
+      max_vol = std::max(max_vol, (long long)S.dims[0] * S.dims[1] * S.dims[2]);
+      any_flush = true;
+    }
+  }
+  if ((long long)n * ((max_vol + TOPAY_SENSE_BLOCK - 1) / TOPAY_SENSE_BLOCK) >= (1ll << 31)) { set_err("topay_sense_insert: flush launch too large"); return TOPAY_ERR_UNSUPPORTED; }
+  HIPCHK(hipSetDevice(c->device));
+  if ((s = sense_events(c)) != TOPAY_OK) return s;
+  const bool select = P.thresh > 0 && max_len > 0;
+  SenseSlot* d_slots; int *d_nsurv, *d_surv, *d_boxes;
+  auto lay = [&](Carver& q) {
+    d_slots = q.take<SenseSlot>((size_t)n); d_nsurv = q.take<int>((size_t)n); d_boxes = q.take<int>(6 * (size_t)n); d_surv = q.take<int>(select ? total : 1);
+  };
+  if ((s = c->sense_io.carve(lay)) != TOPAY_OK) return s;
+  const SensePoint* d_pts = nullptr;
+  if (from_scan) d_pts = c->sense_scan.as<SensePoint>();
+  else if (total > 0) {
+    if ((s = c->sense_pts.ensure(total * sizeof(SensePoint))) != TOPAY_OK) return s;
+    HIPCHK(h2d(c, c->sense_pts.as<float>(), points_xyzi, total * 4));
+    d_pts = c->sense_pts.as<SensePoint>();
+  }
+  HIPCHK(h2d(c, d_slots, (const SenseSlot*)hs.data(), (size_t)n));
+  HIPCHK(h2d(c, d_nsurv, (const int*)h_nsurv.data(), (size_t)n));
+  HIPCHK(hipEventRecord(c->sense_ev[0], c->stream));
+  for (int k = 0; k < n; k++) {   // the launches follow: the slots' host state moves with them
+    if (hs[(size_t)k].skip) continue;
+    topay_ctx::SenseBelief& b = c->sense[map_ids[k]];
+    const Next& N = nx[(size_t)k];
+    b.prm = *params;
+    b.batch_counter = N.batch_counter; b.pending_rays = N.pending_rays;
+  }
+  if (max_rays > 0) {
+    if (select) hipLaunchKernelGGL(k_sense_select, dim3((unsigned)n), dim3(TOPAY_SENSE_BLOCK), 0, c->stream, P, (const SenseSlot*)d_slots, d_pts, d_surv, d_nsurv);
+    const int bps = (max_rays + TOPAY_SENSE_BLOCK - 1) / TOPAY_SENSE_BLOCK;
+    hipLaunchKernelGGL(k_sense_rays, dim3((unsigned)((size_t)n * bps)), dim3(TOPAY_SENSE_BLOCK), 0, c->stream, P, (const SenseSlot*)d_slots, bps, d_pts,
+                       select ? (const int*)d_surv : (const int*)nullptr, (const int*)d_nsurv);
+  }
+  // The voxels a flush has to cover are the batch's cache box, which the rays of this and the batch's earlier calls have reduced on
+  // the device: whatever path a ray took (a traversal that steps past its end voxel on a tie runs on to the map's edge, as the
+  // reference's does), a voxel with a count lies in it.  The boxes come back with the wait that ends the insert stage.
+  std::vector<int> h_boxes(6 * (size_t)n, 0x7f7f7f7f);
+  if (any_flush) {
+    hipLaunchKernelGGL(k_sense_box_gather, dim3((unsigned)((n * 6 + 255) / 256)), dim3(256), 0, c->stream, (const SenseSlot*)d_slots, n, d_boxes);
+    HIPCHK(d2h(c, h_boxes.data(), (const int*)d_boxes, 6 * (size_t)n));
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->sense_ev[1], c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if ((s = sense_elapsed(c, 1)) != TOPAY_OK) return s;
+  for (int k = 0; k < n; k++) {
+    const int* bx = h_boxes.data() + 6 * (size_t)k;
+    if (!hs[(size_t)k].flush || bx[0] == 0x7f7f7f7f) continue;
+    long long vol = 1;
+    for (int a = 0; a < 3; a++) vol *= (long long)(-bx[3 + a]) - bx[a] + 1;
+    max_fvol = std::max(max_fvol, vol);
+  }
+  max_fvol = std::min(max_fvol, max_vol);   // (a box lies inside its grid: the launch size checked above holds)
+  const long long fbps = (max_fvol + TOPAY_SENSE_BLOCK - 1) / TOPAY_SENSE_BLOCK;
+  HIPCHK(hipEventRecord(c->sense_ev[0], c->stream));
+  if (any_flush) {
+    if (max_fvol > 0) {
+      hipLaunchKernelGGL(k_sense_flush, dim3((unsigned)((long long)n * fbps)), dim3(TOPAY_SENSE_BLOCK), 0, c->stream, P, (const SenseSlot*)d_slots, (int)fbps);
+    }
+    hipLaunchKernelGGL(k_sense_box_reset, dim3((unsigned)((n * 6 + 255) / 256)), dim3(256), 0, c->stream, (const SenseSlot*)d_slots, n);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->sense_ev[1], c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if ((s = sense_elapsed(c, 2)) != TOPAY_OK) return s;
+  if (status) memcpy(status, st.data(), sizeof(int) * (size_t)n);
+  return TOPAY_OK;
+}
+
+topay_status topay_sense_commit(topay_ctx* c, int n, const int* map_ids) {
+  if (!c || n <= 0 || !map_ids) return TOPAY_ERR_INVALID_ARG;
+  topay_status s;
+  if ((s = sense_check_ids(n, map_ids)) != TOPAY_OK) return s;
+  for (int k = 0; k < n; k++)
+    if (map_ids[k] >= (int)c->sense.size() || !c->sense[map_ids[k]].have) { set_err("topay_sense_commit: slot without a belief (topay_sense_reset)"); return TOPAY_ERR_NO_MAP; }
+  HIPCHK(hipSetDevice(c->device));
+  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }   // inputs of a solve in flight stay untouched
+  if ((s = sense_events(c)) != TOPAY_OK) return s;
+  // Runs of consecutive slots on one grid go through the field construction together (its launches take a batch of maps).  The lane
+  // emulator runs the blocks of a launch along x only (blockIdx.y = map stays 0), so there a run is one slot.
+#ifdef TOPAY_CPU_EMU
+  const int max_run = 1;
+#else
+  const int max_run = TOPAY_MAX_MAPS;
+#endif
+  std::vector<int> ids(map_ids, map_ids + n);
+  std::sort(ids.begin(), ids.end());
+  struct Run { int first, n; size_t o3, o2, o2c; };
+  std::vector<Run> runs;
+  size_t bytes = 0;
+  auto same_grid = [](const topay_map_desc_t& a, const topay_map_desc_t& b) {
+    bool eq = a.resolution == b.resolution;
+    for (int i = 0; i < 3; i++)
+      eq = eq && a.origin[i] == b.origin[i] && a.dims[i] == b.dims[i] && a.min_boundary[i] == b.min_boundary[i] && a.max_boundary[i] == b.max_boundary[i];
+    return eq;
+  };
+  for (int k = 0; k < n;) {
+    int e = k + 1;
+    while (e < n && e - k < max_run && ids[e] == ids[e - 1] + 1 && same_grid(c->sense[ids[e]].desc, c->sense[ids[k]].desc)) e++;
+    const topay_map_desc_t& d = c->sense[ids[k]].desc;
+    const size_t n2 = (size_t)d.dims[0] * d.dims[1], n3 = n2 * d.dims[2], R = (size_t)(e - k);
+    Run r{ids[k], e - k, bytes, 0, 0};
+    bytes += (R * n3 + 15) & ~(size_t)15;   // (each grid starts on a 16-byte boundary: k_sense_occupancy's 16-byte stores)
+    r.o2 = bytes; bytes += (R * n2 + 15) & ~(size_t)15;
+    r.o2c = bytes; bytes += (R * n2 + 15) & ~(size_t)15;
+    runs.push_back(r);
+    k = e;
+  }
+  for (auto& b : c->sense) b.have_occ = false;   // the grids of the last commit are overwritten
+  if ((s = c->sense_occ.ensure(bytes)) != TOPAY_OK) return s;
+  signed char* base = c->sense_occ.as<signed char>();
+  std::vector<SenseOccSlot> ho((size_t)n);
+  int max_cols = 0, at = 0;
+  for (const Run& r : runs)
+    for (int i = 0; i < r.n; i++, at++) {
+      topay_ctx::SenseBelief& b = c->sense[r.first + i];
+      const size_t n2 = (size_t)b.desc.dims[0] * b.desc.dims[1], n3 = n2 * b.desc.dims[2];
+      SenseP P;
+      if ((s = sense_make_params(&b.prm, P)) != TOPAY_OK) return s;
+      b.occ3_off = r.o3 + (size_t)i * n3; b.occ2_off = r.o2 + (size_t)i * n2; b.occ2c_off = r.o2c + (size_t)i * n2;
+      SenseOccSlot& S = ho[(size_t)at];
+      S.logodds = b.logodds; S.occ3 = base + b.occ3_off; S.occ2 = base + b.occ2_off; S.occ2c = base + b.occ2c_off;
+      S.z0 = b.desc.origin[2]; S.res = b.desc.resolution; S.chassis_height = b.prm.chassis_height; S.l_occ = P.l_occ;
+      for (int a = 0; a < 3; a++) S.dims[a] = b.desc.dims[a];
+      max_cols = std::max(max_cols, (int)n2);
+    }
+  if ((s = c->sense_io.ensure(sizeof(SenseOccSlot) * (size_t)n)) != TOPAY_OK) return s;
+  HIPCHK(h2d(c, c->sense_io.as<SenseOccSlot>(), (const SenseOccSlot*)ho.data(), (size_t)n));
+  HIPCHK(hipEventRecord(c->sense_ev[0], c->stream));
+  const int bps = (max_cols + TOPAY_SENSE_BLOCK - 1) / TOPAY_SENSE_BLOCK;
+  hipLaunchKernelGGL(k_sense_occupancy, dim3((unsigned)((size_t)n * bps)), dim3(TOPAY_SENSE_BLOCK), 0, c->stream, (const SenseOccSlot*)c->sense_io.as<SenseOccSlot>(), bps);
+  HIPCHK(hipGetLastError());
+  for (const Run& r : runs) {
+    world_forget(c, r.first, r.n);
+    if ((s = build_fields_from_device(c, r.n, r.first, &c->sense[r.first].desc, base + r.o3, base + r.o2, base + r.o2c, false)) != TOPAY_OK) return s;
+    for (int i = 0; i < r.n; i++) c->sense[r.first + i].have_occ = true;
+  }
+  HIPCHK(hipEventRecord(c->sense_ev[1], c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return sense_elapsed(c, 3);
+}
+
+topay_status topay_sense_get(topay_ctx* c, int map_id, float* logodds, int* op_cnt, int* hit_cnt, int* batch_counter) {
+  if (!c || map_id < 0 || map_id >= TOPAY_MAX_MAPS) return TOPAY_ERR_INVALID_ARG;
+  if (map_id >= (int)c->sense.size() || !c->sense[map_id].have) return TOPAY_ERR_NO_MAP;
+  HIPCHK(hipSetDevice(c->device));
+  const topay_ctx::SenseBelief& b = c->sense[map_id];
+  const size_t n3 = (size_t)b.desc.dims[0] * b.desc.dims[1] * b.desc.dims[2];
+  if (logodds) HIPCHK(d2h_sync(c, logodds, (const float*)b.logodds, n3));
+  if (op_cnt || hit_cnt) {
+    std::vector<int> packed(n3);
+    HIPCHK(d2h_sync(c, packed.data(), (const int*)b.cnt, n3));
+    for (size_t i = 0; i < n3; i++) {
+      if (op_cnt) op_cnt[i] = (int)((unsigned)packed[i] & 0xffffu);
+      if (hit_cnt) hit_cnt[i] = (int)((unsigned)packed[i] >> 16);
+    }
+  }
+  if (batch_counter) *batch_counter = b.batch_counter;
+  return TOPAY_OK;
+}
+
+topay_status topay_sense_scan(topay_ctx* c, int n, const int* truth_map_ids, const double* poses, int n_az, int n_el, double fov, double range,
+                              int cloud_cap, int* cloud_off, float* points) {
+  if (!c || n <= 0 || !truth_map_ids || !poses || n_az <= 0 || n_el <= 0 || !(range > 0.0) || !(range <= 1.0e6) || !(std::fabs(fov) <= 3.2))
+    return TOPAY_ERR_INVALID_ARG;
+  const long long rays = (long long)n_az * n_el, total = rays * n;
+  if (rays > (1 << 24) || total >= (1ll << 31) / 16) { set_err("topay_sense_scan: too many rays"); return TOPAY_ERR_INVALID_ARG; }
+  if (points && (long long)cloud_cap < total) { set_err("topay_sense_scan: cloud_cap below n * n_az * n_el"); return TOPAY_ERR_INVALID_ARG; }
+  std::vector<SenseScanSlot> hs((size_t)n);
+  for (int k = 0; k < n; k++) {
+    const int m = truth_map_ids[k];
+    if (m < 0 || m >= TOPAY_MAX_MAPS) return TOPAY_ERR_INVALID_ARG;
+    SenseScanSlot& S = hs[(size_t)k];
+    memset(&S, 0, sizeof(S));
+    S.occ3 = sense_truth_occ3(c, m, S.dims);
+    if (!S.occ3 || !c->have_map[m]) { set_err("topay_sense_scan: slot " + std::to_string(m) + " has no resident occupancy (topay_get_occupancy)"); return TOPAY_ERR_NO_MAP; }
+    const DevMap& M = c->hmaps[m];
+    for (int a = 0; a < 3; a++) S.origin[a] = M.origin[a];
+    S.res = M.res;
+    for (int a = 0; a < 4; a++) {
+      S.pose[a] = poses[4 * (size_t)k + a];
+      if (!(std::fabs(S.pose[a] - (a < 3 ? S.origin[a] : 0.0)) <= 1.0e6)) { set_err("topay_sense_scan: pose not finite or more than 1e6 m from the map"); return TOPAY_ERR_INVALID_ARG; }
+    }
+  }
+  HIPCHK(hipSetDevice(c->device));
+  topay_status s;
+  if ((s = sense_events(c)) != TOPAY_OK) return s;
+  c->sense_scan_points = 0;
+  if ((s = c->sense_scan.ensure((size_t)total * sizeof(SensePoint))) != TOPAY_OK) return s;
+  if ((s = c->sense_io.ensure(sizeof(SenseScanSlot) * (size_t)n)) != TOPAY_OK) return s;
+  HIPCHK(h2d(c, c->sense_io.as<SenseScanSlot>(), (const SenseScanSlot*)hs.data(), (size_t)n));
+  HIPCHK(hipEventRecord(c->sense_ev[0], c->stream));
+  const int bps = (int)((rays + TOPAY_SENSE_BLOCK - 1) / TOPAY_SENSE_BLOCK);
+  hipLaunchKernelGGL(k_sense_scan, dim3((unsigned)((size_t)n * bps)), dim3(TOPAY_SENSE_BLOCK), 0, c->stream, (const SenseScanSlot*)c->sense_io.as<SenseScanSlot>(), bps,
+                     n_az, n_el, fov, range, c->sense_scan.as<SensePoint>());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->sense_ev[1], c->stream));
+  if (points) HIPCHK(d2h(c, points, (const float*)c->sense_scan.as<float>(), (size_t)total * 4));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->sense_scan_points = (size_t)total;
+  if (cloud_off)
+    for (int k = 0; k <= n; k++) cloud_off[k] = (int)(rays * k);
+  return sense_elapsed(c, 0);
+}
+
+topay_status topay_sense_ms(topay_ctx* c, double ms[4]) {
+  if (!c || !ms) return TOPAY_ERR_INVALID_ARG;
+  for (int k = 0; k < 4; k++) ms[k] = c->sense_ms[k];
+  return TOPAY_OK;
+}
+
+}  // extern "C"

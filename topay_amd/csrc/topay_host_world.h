@@ -101,6 +101,7 @@ static topay_status world_generate(topay_ctx* c, int n, int first_map_id, const 
   signed char *d_occ3, *d_occ2, *d_occ2c;
   // (each grid starts on a 16-byte boundary: the first path stores 16 bytes at a time)
   const size_t b3 = (M * n3 + 15) & ~(size_t)15, b2 = (M * n2 + 15) & ~(size_t)15;
+  for (int m = first_map_id; m < first_map_id + n && m < (int)c->sense.size(); m++) c->sense[m].have_occ = false;   // (topay_sense_commit's grids)
   c->world_n = 0;
   if ((s = c->world_occ.ensure(b3 + 2 * b2)) != TOPAY_OK) return s;
   d_occ3 = c->world_occ.as<signed char>();
@@ -240,6 +241,16 @@ topay_status topay_generate_worlds(topay_ctx* c, int n, int first_map_id, const 
 
 topay_status topay_get_occupancy(topay_ctx* c, int map_id, signed char* occ2d, signed char* occ2d_critical, signed char* occ3d) {
   if (!c) return TOPAY_ERR_INVALID_ARG;
+  if (map_id >= 0 && map_id < (int)c->sense.size() && c->sense[map_id].have_occ) {   // a slot of the last topay_sense_commit
+    const topay_ctx::SenseBelief& b = c->sense[map_id];
+    HIPCHK(hipSetDevice(c->device));
+    const size_t n2 = (size_t)b.desc.dims[0] * b.desc.dims[1], n3 = n2 * b.desc.dims[2];
+    const signed char* base = c->sense_occ.as<signed char>();
+    if (occ3d) HIPCHK(d2h_sync(c, occ3d, base + b.occ3_off, n3));
+    if (occ2d) HIPCHK(d2h_sync(c, occ2d, base + b.occ2_off, n2));
+    if (occ2d_critical) HIPCHK(d2h_sync(c, occ2d_critical, base + b.occ2c_off, n2));
+    return TOPAY_OK;
+  }
   if (map_id < c->world_first || map_id >= c->world_first + c->world_n || !c->world_occ.p) return TOPAY_ERR_NO_MAP;
   HIPCHK(hipSetDevice(c->device));
   const size_t n2 = (size_t)c->world_dims[0] * c->world_dims[1], n3 = n2 * c->world_dims[2], M = (size_t)c->world_n, k = (size_t)(map_id - c->world_first);
