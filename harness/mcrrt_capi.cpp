@@ -261,3 +261,52 @@ void wl_pm_scan(const int8_t* occ3d, const double* origin, double res, const int
 }
 
 }  // extern "C"
+
+#include "ompc.hpp"
+
+extern "C" {
+
+// ---- the tracking controller's and the fake robot's restatement (harness/ompc.hpp) -------------------------------------
+void* wl_ompc_create(const ompc::Params* p) { return new ompc::OMPC(*p); }
+void wl_ompc_destroy(void* h) { delete (ompc::OMPC*)h; }
+void wl_ompc_set_direct(void* h, int on, const double* pos3) {
+  ompc::OMPC* m = (ompc::OMPC*)h;
+  m->control_state = on ? 1 : 0;
+  for (int a = 0; a < 3; a++) m->direct_pos[a] = on ? pos3[a] : 0.0;
+}
+// getCmd; rows [T][3], arm_q / arm_dq [7] from the caller's trajectory; xopt [(T + 1)][3] may be null
+void wl_ompc_cmd(void* h, int has_traj, double t_cur, double T_total, const double* now10, const double* rows, const double* arm_q, const double* arm_dq,
+                 double* cmd16, int* status4, double* xopt) {
+  ((ompc::OMPC*)h)->getCmd(has_traj != 0, t_cur, T_total, now10, rows, arm_q, arm_dq, cmd16, status4, xopt);
+}
+// output [2][T], output_buff [maxd][2]
+void wl_ompc_get(void* h, double* output, double* fifo) {
+  const ompc::OMPC& m = *(ompc::OMPC*)h;
+  if (output) memcpy(output, m.output.data(), m.output.size() * sizeof(double));
+  if (fifo) memcpy(fifo, m.output_buff.data(), m.output_buff.size() * sizeof(double));
+}
+// The first QP of getCmd, the controller's state untouched: solveMPCDiff's matrices as the reference fills them, and the
+// solution of the stage-order solver in that order.  info[2] = steps, solved.  Returns 0 when getCmd does not reach the QP.
+int wl_ompc_probe(void* h, int has_traj, double t_cur, double T_total, const double* now10, const double* rows, double* P, double* q, double* A,
+                  double* l, double* u, double* x, double* y, double* z, int* info) {
+  ompc::OMPC* m = (ompc::OMPC*)h;
+  ompc::Dense D;
+  double cmd[16], arm[7] = {0, 0, 0, 0, 0, 0, 0};
+  int st[4];
+  m->getCmd(has_traj != 0, t_cur, T_total, now10, rows, arm, arm, cmd, st, nullptr, &D);
+  if (D.nx == 0) return 0;
+  memcpy(P, D.P.data(), D.P.size() * 8); memcpy(q, D.q.data(), D.q.size() * 8); memcpy(A, D.A.data(), D.A.size() * 8);
+  memcpy(l, D.l.data(), D.l.size() * 8); memcpy(u, D.u.data(), D.u.size() * 8);
+  memcpy(x, D.x.data(), D.x.size() * 8); memcpy(y, D.y.data(), D.y.size() * 8); memcpy(z, D.z.data(), D.z.size() * 8);
+  info[0] = D.iters; info[1] = D.solved;
+  return 1;
+}
+void* wl_sim_create(const double* state10, int delay_cmds) { return new ompc::Sim(state10, delay_cmds); }
+void wl_sim_destroy(void* h) { delete (ompc::Sim*)h; }
+void wl_sim_step(void* h, const double* cmd16, int ticks, double* state10) {
+  ompc::Sim* s = (ompc::Sim*)h;
+  s->step(cmd16, ticks);
+  for (int a = 0; a < 10; a++) state10[a] = s->st[a];
+}
+
+}  // extern "C"

@@ -337,6 +337,23 @@ def mlib():
         L.wl_pm_logodds.restype = None
         L.wl_pm_scan.argtypes = [C.c_void_p, c_dp, C.c_double, c_ip, c_dp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]
         L.wl_pm_scan.restype = None
+        L.wl_ompc_create.argtypes = [C.c_void_p]
+        L.wl_ompc_create.restype = C.c_void_p
+        L.wl_ompc_destroy.argtypes = [C.c_void_p]
+        L.wl_ompc_destroy.restype = None
+        L.wl_ompc_set_direct.argtypes = [C.c_void_p, C.c_int, c_dp]
+        L.wl_ompc_set_direct.restype = None
+        L.wl_ompc_cmd.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, c_dp, c_dp, c_dp, c_dp, c_dp, c_ip, c_dp]
+        L.wl_ompc_cmd.restype = None
+        L.wl_ompc_get.argtypes = [C.c_void_p, c_dp, c_dp]
+        L.wl_ompc_get.restype = None
+        L.wl_ompc_probe.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double] + [c_dp] * 10 + [c_ip]
+        L.wl_sim_create.argtypes = [c_dp, C.c_int]
+        L.wl_sim_create.restype = C.c_void_p
+        L.wl_sim_destroy.argtypes = [C.c_void_p]
+        L.wl_sim_destroy.restype = None
+        L.wl_sim_step.argtypes = [C.c_void_p, c_dp, C.c_int, c_dp]
+        L.wl_sim_step.restype = None
         _MLIB = L
     return _MLIB
 
@@ -635,3 +652,74 @@ def topo_samples_in(world, start, goal, seconds=0.01, params=None, inst=0):
     a = np.ascontiguousarray(np.asarray(start, dtype=np.float64)[:2])
     b = np.ascontiguousarray(np.asarray(goal, dtype=np.float64)[:2])
     return int(L.wl_topo_samples_in(world.h, _dp(np.ascontiguousarray(inf)), _dp(np.ascontiguousarray(cr)), _dp(a), _dp(b), C.byref(prm), int(inst), float(seconds)))
+
+
+class OmpcCheck:
+    """The CPU checker of the tracking controller (harness/ompc.hpp): one OMPC.  params: a ctypes structure with the layout of
+    topay_mpc_params_t (topay_amd.api.MpcParams).  The trajectory is the caller's: rows [T, 3] = getState(t)[:3] at t = t_cur + dt,
+    += dt; arm_q / arm_dq [7] = getState / getDState(t_cur + 1 / ctrl_freq)[3:]."""
+
+    def __init__(self, params):
+        self.T = int(params.predict_steps)
+        self.maxd = max(int(params.delay_num_v), int(params.delay_num_w))
+        self.nx = 3 * (self.T - params.delay_num_w) + (self.T - params.delay_num_v) + (self.T - params.delay_num_w)
+        self.nc = self.nx + (self.T - params.delay_num_v) + (self.T - params.delay_num_w) - 2
+        self.h = mlib().wl_ompc_create(C.addressof(params))
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            mlib().wl_ompc_destroy(self.h)
+            self.h = None
+
+    def set_direct(self, pos3=None):
+        p = np.zeros(3) if pos3 is None else np.ascontiguousarray(pos3, dtype=np.float64)
+        mlib().wl_ompc_set_direct(self.h, 0 if pos3 is None else 1, _dp(p))
+
+    def cmd(self, t_cur, now_state, rows=None, arm_q=None, arm_dq=None, T_total=0.0, has_traj=True):
+        """(cmd [16], status [4], xopt [T + 1, 3])"""
+        ns = np.ascontiguousarray(now_state, dtype=np.float64)
+        rw = np.zeros((self.T, 3)) if rows is None else np.ascontiguousarray(rows, dtype=np.float64)
+        q = np.zeros(7) if arm_q is None else np.ascontiguousarray(arm_q, dtype=np.float64)
+        dq = np.zeros(7) if arm_dq is None else np.ascontiguousarray(arm_dq, dtype=np.float64)
+        cmd, st, xo = np.zeros(16), np.zeros(4, dtype=np.int32), np.zeros((self.T + 1, 3))
+        mlib().wl_ompc_cmd(self.h, 1 if has_traj else 0, float(t_cur), float(T_total), _dp(ns), _dp(rw), _dp(q), _dp(dq), _dp(cmd),
+                           st.ctypes.data_as(c_ip), _dp(xo))
+        return cmd, st, xo
+
+    def get(self):
+        out, ff = np.zeros((2, self.T)), np.zeros((self.maxd, 2))
+        mlib().wl_ompc_get(self.h, _dp(out), _dp(ff))
+        return out, ff
+
+    def probe(self, t_cur, now_state, rows=None, T_total=0.0, has_traj=True):
+        ns = np.ascontiguousarray(now_state, dtype=np.float64)
+        rw = np.zeros((self.T, 3)) if rows is None else np.ascontiguousarray(rows, dtype=np.float64)
+        nx, nc = self.nx, self.nc
+        o = dict(P=np.zeros((nx, nx)), q=np.zeros(nx), A=np.zeros((nc, nx)), l=np.zeros(nc), u=np.zeros(nc), x=np.zeros(nx), y=np.zeros(nc),
+                 z=np.zeros(nc))
+        info = np.zeros(2, dtype=np.int32)
+        ok = mlib().wl_ompc_probe(self.h, 1 if has_traj else 0, float(t_cur), float(T_total), _dp(ns), _dp(rw), _dp(o["P"]), _dp(o["q"]),
+                                  _dp(o["A"]), _dp(o["l"]), _dp(o["u"]), _dp(o["x"]), _dp(o["y"]), _dp(o["z"]), info.ctypes.data_as(c_ip))
+        if not ok:
+            return None
+        o["iters"], o["solved"] = int(info[0]), int(info[1])
+        return o
+
+
+class SimCheck:
+    """The CPU checker of the fake robot (harness/ompc.hpp)."""
+
+    def __init__(self, state0, delay_cmds=20):
+        s0 = np.ascontiguousarray(state0, dtype=np.float64)
+        self.h = mlib().wl_sim_create(_dp(s0), int(delay_cmds))
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            mlib().wl_sim_destroy(self.h)
+            self.h = None
+
+    def step(self, cmd, ticks):
+        st = np.zeros(10)
+        cm = None if cmd is None else np.ascontiguousarray(cmd, dtype=np.float64)
+        mlib().wl_sim_step(self.h, None if cm is None else _dp(cm), int(ticks), _dp(st))
+        return st

@@ -746,6 +746,94 @@ topay_status topay_sense_scan(topay_ctx* ctx, int n, const int* truth_map_ids, c
 /* Device time (HIP events) of the last scan, insert (selection and rays), flush, and commit with its fields, in ms. */
 topay_status topay_sense_ms(topay_ctx* ctx, double ms[4]);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The tracking controller and the fake robot: what Planner::cmdCallback (planner.cpp:158-178) runs between two replans.
+ * topay_mpc_*: OMPC (planner/src/ompc.cpp, include/planner/ompc.h), the chassis tracking MPC around a slot's end_traj;
+ * topay_sim_*: moma_sim (simulator/fake_moma/src/moma_sim.cpp:208-229, 251-308); topay_track_follow: both, period after period,
+ * without the host.  Robot slots are those of topay_track_*.  One wave per robot.
+ * Clock: the library keeps none.  Every call takes t_cur[k] = the reference's now - begin_time; after a replan that is the
+ * wait_time of setTraj(end_traj, wait_time).  at_goal is therefore a function of the call, t_cur >= T_total + 1.0 (1.0 s after
+ * topay_mpc_set_direct in direct mode, whose begin_time is the clock's zero too), not a flag that stays set.
+ * Restated as it stands: the arm command getState / getDState(t_cur + 1 / ctrl_freq); the reference rows by the running sum
+ * t = t_cur + dt, t += dt; smooth_yaw with its >= pi / 2 loops; predictMotion with stateTrans's clamps; du summed as the
+ * reference sums it; the QP of solveMPCDiff entry for entry, in both of its branches (delay_num_v == delay_num_w, delay_num_v >
+ * delay_num_w); output left as it was when the QP is not solved; predictMotion(xopt); the command output(0, delay_num_v),
+ * output(1, delay_num_w) and the FIFO shift.  The controller state survives a new end_traj (setTraj clears nothing).
+ * Deviations:
+ *   - The wall-clock break of the outer loop (ompc.cpp:630, 1 / ctrl_freq) is not restated: max_iter is the only cap.
+ *   - OSQP is not restated.  The QP has one minimiser (its Hessian's diagonal is positive); the solver returns x, y, z that meet
+ *     OSQP's termination criterion on the unscaled problem at qp_eps_abs = qp_eps_rel = 1e-6:
+ *       |A x - z|_inf <= eps_abs + eps_rel max(|A x|, |z|),   |P x + q + A' y|_inf <= eps_abs + eps_rel max(|P x|, |A' y|, |q|),
+ *     l <= z <= u, and y in the normal cone of [l, u] at z (y_i > 0 only where z_i = u_i, y_i < 0 only where z_i = l_i), exactly.
+ *     Method: OSQP's ADMM step with a fixed rho (no adaptation: that depends on timings; 10, not OSQP's initial 0.1, at which the
+ *     shipped QP does not reach the criterion in 30000 steps, docs/EXPERIMENTS.md), equality rows at 1e3 rho, variables
+ *     ordered by stage (v_j, w_j, x_j, y_j, theta_j) so that P + sigma I + A' R A has half-bandwidth 5; it is factored (L D L') once
+ *     per QP in LDS, every step is one banded solve plus stage-local products.  The criterion is tested every 10th step and at
+ *     qp_max_iter.  The first QP of a command starts from zero, every later one from the x, y of the one before.  Every sum has one
+ *     fixed order: device, emulator and harness/ompc.hpp agree bit for bit.
+ *   - sin / cos are the library's deterministic ones.
+ * Left out: the CasADi MPC class of mpc.h, the drawing functions, gripper_state, the lidar pose, normlize_theta (unused).
+ * Refused before any launch: TOPAY_ERR_UNSUPPORTED for delay_num_v < delay_num_w (the reference's code for it is commented out,
+ * its matrix would be incomplete) and for max(delay_num_v, delay_num_w) == 0 (the reference reads output_buff.back() of an empty
+ * vector); TOPAY_ERR_INVALID_ARG for predict_steps - delay_num_v < 2 (the dQ corrections and mz assume two inputs of each kind),
+ * more than 64 stages (predict_steps - delay_num_w), predict_steps > 128, max_iter < 1, clocks, states or positions that are not
+ * finite or reach 1e9 in magnitude (parameters: 1e12), a slot named twice, a slot that was never reset.
+ * A new end_traj does not change the slot's mode (the library does not tie the two stores together): where the reference's setTraj
+ * sets control_state = 0, a caller in direct mode calls topay_mpc_set_direct(..., NULL). */
+#define TOPAY_MPC_MAX_STEPS 128
+#define TOPAY_MPC_MAX_STAGES 64
+typedef struct {
+  double du_threshold, dt, ctrl_freq;                 /* 0.001, 0.02, 50   (params/mpc.yaml, ompc/) */
+  int max_iter, predict_steps, delay_num_v, delay_num_w;   /* 150, 50, 20, 20 */
+  double max_omega, max_domega, max_speed, min_speed, max_accel;   /* 0.9, 1.0, 1.0, -1.0, 0.8 */
+  double matrix_q[3], matrix_r[2], matrix_rd[2];      /* 10 10 3, 0.01 0.01, 15 1.5 */
+  double qp_eps_abs, qp_eps_rel;                      /* 1e-6, 1e-6 */
+  double qp_rho, qp_sigma, qp_alpha;                  /* 10, 1e-6, 1.6 */
+  int qp_max_iter, reserved;                          /* 30000 */
+} topay_mpc_params_t;
+topay_status topay_mpc_default_params(topay_mpc_params_t* p);
+/* Variables and constraint rows of the QP at these parameters (the reference's nx and nc); the checks above. */
+topay_status topay_mpc_qp_dims(const topay_mpc_params_t* p, int* nx, int* nc);
+/* What OMPC::init creates, for the n slots robots[k]: output (2 x predict_steps) zero, the command FIFO output_buff of
+ * max(delay_num_v, delay_num_w) zero entries, mode 0.  The parameters hold for the slot until its next reset. */
+topay_status topay_mpc_reset(topay_ctx* ctx, int n, const int* robots, const topay_mpc_params_t* params);
+/* OMPC::setDirect: control_state 1 with the constant reference direct_pos[k] (x, y, theta), arm held at now_state, at goal after
+ * 1.0 s.  direct_pos NULL: back to trajectory mode. */
+topay_status topay_mpc_set_direct(topay_ctx* ctx, int n, const int* robots, const double* direct_pos /* n x 3 or NULL */);
+/* One OMPC::getCmd per robot.  cmd[k][16] = speed, angular_velocity, q[7], dq[7].  status[k][TOPAY_MPC_ST_LEN]: outcome (0
+ * command, 1 at goal: zero chassis command, nothing else changes, 2 no trajectory: zero command, arm held at now_state, 3 a
+ * command, but the QP was not solved in some outer iteration), outer iterations taken, QP steps summed, mode.  xopt (may be NULL):
+ * [k][TOPAY_MPC_MAX_STEPS + 1][3], rows 0 .. predict_steps of predictMotion(xopt), the others zero. */
+enum { TOPAY_MPC_ST_OUTCOME, TOPAY_MPC_ST_OUTER, TOPAY_MPC_ST_QP_ITERS, TOPAY_MPC_ST_MODE, TOPAY_MPC_ST_LEN };
+topay_status topay_mpc_cmds(topay_ctx* ctx, int n, const int* robots, const double* t_cur, const double* now_state /* n x 10 */,
+                            double* cmd /* n x 16 */, int* status /* n x 4, optional */, double* xopt /* optional */);
+/* The parity hook: the first outer iteration of topay_mpc_cmds for one robot, the slot's state untouched.  The QP dense and in the
+ * reference's order (variables: states, v, w; rows: box v, box w, dynamics, rate v, rate w): P [nx][nx], q [nx], A [nc][nx], l, u
+ * [nc]; its solution x [nx], y, z [nc]; info[2] = QP steps, solved.  Any output may be NULL.  TOPAY_ERR_NO_TRAJ when the call does
+ * not reach the QP (no trajectory, at goal): the kernel decides that, as for topay_mpc_cmds, and the outputs are left alone. */
+topay_status topay_mpc_probe(topay_ctx* ctx, int robot, double t_cur, const double* now_state, double* P, double* q, double* A, double* l,
+                             double* u, double* x, double* y, double* z, int* info);
+/* The slot's state: output [2][TOPAY_MPC_MAX_STEPS], fifo [TOPAY_MPC_MAX_STEPS][2] (the first max(delay_num_v, delay_num_w) rows
+ * are output_buff, oldest first), mode.  Any pointer may be NULL. */
+topay_status topay_mpc_get_state(topay_ctx* ctx, int robot, double* output, double* fifo, int* mode);
+/* Device time (HIP events) of the last topay_mpc_cmds or topay_track_follow, in ms. */
+topay_status topay_mpc_ms(topay_ctx* ctx, double* ms);
+
+/* moma_sim with the clock made explicit.  topay_sim_reset: the robot at state0[k] (x, y, theta, q[7]), no command received, an empty
+ * actuator FIFO of delay_cmds commands (1 .. 128; 20 = the reference's time_delay 0.4 s at 50 Hz).  The reference's test "ROS time
+ * since the first command > time_delay" is restated as a count: the chassis command is zero until delay_cmds commands have been
+ * received, after that the oldest entry is taken, so command k acts from the receipt of command k + delay_cmds.
+ * topay_sim_step: cmd[k] (may be NULL: no command this step) through rcvVelCmdCallBack, then `ticks` ticks of simCallBack at 0.01 s
+ * (x += v 0.01 cos(theta), y likewise, theta += w 0.01, normyaw's single wrap, the arm set to cmd.q); nothing moves before the
+ * first command.  state (n x 10, may be NULL) receives the robots' states. */
+topay_status topay_sim_reset(topay_ctx* ctx, int n, const int* robots, const double* state0 /* n x 10 */, int delay_cmds);
+topay_status topay_sim_step(topay_ctx* ctx, int n, const int* robots, const double* cmd /* n x 16 or NULL */, int ticks, double* state);
+/* `periods` control periods in one launch: per period one topay_mpc_cmds from the simulator's own state at t, one topay_sim_step
+ * of ticks_per_period ticks, t = t + 1 / ctrl_freq (t starts at t0[k]).  Equal bit for bit to that sequence of single calls.
+ * states_out [n][periods][10] (after the step), cmds_out [n][periods][16], status_out [n][periods][TOPAY_MPC_ST_LEN]: optional. */
+topay_status topay_track_follow(topay_ctx* ctx, int n, const int* robots, const double* t0, int periods, int ticks_per_period,
+                                double* states_out, double* cmds_out, int* status_out);
+
 /* ompl::base::ReedsSheppStateSpace(rho) for n pose pairs (x, y, theta): distance[i] = distance(from_i, to_i), word[i] /
  * lengths[i][5] = the shortest path's segment word (0..17, OMPL's reedsSheppPathType numbering) and signed segment lengths
  * in units of rho, pose[i] = interpolate(from_i, to_i, t[i]) when t is given.  Output pointers may be NULL. */

@@ -115,6 +115,18 @@ class SenseParams(C.Structure):
                 ("virtual_ground_height", C.c_double), ("local_update_box", C.c_double * 3), ("chassis_height", C.c_double)]
 
 
+class MpcParams(C.Structure):
+    """topay_mpc_params_t (include/topay.h): the ompc/ keys of params/mpc.yaml and the QP solver's knobs."""
+    _fields_ = [("du_threshold", C.c_double), ("dt", C.c_double), ("ctrl_freq", C.c_double), ("max_iter", C.c_int),
+                ("predict_steps", C.c_int), ("delay_num_v", C.c_int), ("delay_num_w", C.c_int), ("max_omega", C.c_double),
+                ("max_domega", C.c_double), ("max_speed", C.c_double), ("min_speed", C.c_double), ("max_accel", C.c_double),
+                ("matrix_q", C.c_double * 3), ("matrix_r", C.c_double * 2), ("matrix_rd", C.c_double * 2), ("qp_eps_abs", C.c_double),
+                ("qp_eps_rel", C.c_double), ("qp_rho", C.c_double), ("qp_sigma", C.c_double), ("qp_alpha", C.c_double),
+                ("qp_max_iter", C.c_int), ("reserved", C.c_int)]
+
+
+MPC_MAX_STEPS = 128          # TOPAY_MPC_MAX_STEPS
+MPC_ST_KEYS = ["outcome", "outer", "qp_iters", "mode"]   # TOPAY_MPC_ST_*
 c_fp = C.POINTER(C.c_float)
 SENSE_LAST_SCAN = "last_scan"   # sense_insert: the points of the last sense_scan, on the device (TOPAY_SENSE_LAST_SCAN)
 SENSE_MS_KEYS = ["scan", "insert", "flush", "commit"]
@@ -244,6 +256,18 @@ def load(path=None):
         L.topay_sense_get.argtypes = [C.c_void_p, C.c_int, c_fp, c_ip, c_ip, c_ip]
         L.topay_sense_scan.argtypes = [C.c_void_p, C.c_int, c_ip, c_dp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, c_ip, c_fp]
         L.topay_sense_ms.argtypes = [C.c_void_p, c_dp]
+    if hasattr(L, "topay_mpc_cmds"):   # (older builds of the library under tools/libs, A/B runs)
+        L.topay_mpc_default_params.argtypes = [C.POINTER(MpcParams)]
+        L.topay_mpc_qp_dims.argtypes = [C.POINTER(MpcParams), c_ip, c_ip]
+        L.topay_mpc_reset.argtypes = [C.c_void_p, C.c_int, c_ip, C.POINTER(MpcParams)]
+        L.topay_mpc_set_direct.argtypes = [C.c_void_p, C.c_int, c_ip, c_dp]
+        L.topay_mpc_cmds.argtypes = [C.c_void_p, C.c_int, c_ip, c_dp, c_dp, c_dp, c_ip, c_dp]
+        L.topay_mpc_probe.argtypes = [C.c_void_p, C.c_int, C.c_double, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_ip]
+        L.topay_mpc_get_state.argtypes = [C.c_void_p, C.c_int, c_dp, c_dp, c_ip]
+        L.topay_mpc_ms.argtypes = [C.c_void_p, c_dp]
+        L.topay_sim_reset.argtypes = [C.c_void_p, C.c_int, c_ip, c_dp, C.c_int]
+        L.topay_sim_step.argtypes = [C.c_void_p, C.c_int, c_ip, c_dp, C.c_int, c_dp]
+        L.topay_track_follow.argtypes = [C.c_void_p, C.c_int, c_ip, c_dp, C.c_int, C.c_int, c_dp, c_dp, c_ip]
     L.topay_get_total_durations.argtypes = [C.c_void_p, c_dp]
     L.topay_check_feasible.argtypes = [C.c_void_p, c_ip]
     L.topay_feasibility_report.argtypes = [C.c_void_p, c_ip, c_ip, c_dp]
@@ -1109,6 +1133,97 @@ class MomaTrajOptBatch:
         ms = np.zeros(1)
         _chk(self.L, self.L.topay_track_safe_ms(self.h, _dp(ms)))
         return float(ms[0])
+
+    # ---- the tracking controller and the fake robot (topay_host_mpc.h)
+    def mpc_params(self, **kw):
+        """topay_mpc_default_params with the given fields replaced (arrays as sequences)."""
+        p = MpcParams()
+        _chk(self.L, self.L.topay_mpc_default_params(C.byref(p)))
+        for k, v in kw.items():
+            if k in ("matrix_q", "matrix_r", "matrix_rd"):
+                for i, x in enumerate(v):
+                    getattr(p, k)[i] = float(x)
+            else:
+                setattr(p, k, v)
+        return p
+
+    def mpc_qp_dims(self, params):
+        nx, nc = C.c_int(0), C.c_int(0)
+        _chk(self.L, self.L.topay_mpc_qp_dims(C.byref(params), C.byref(nx), C.byref(nc)))
+        return nx.value, nc.value
+
+    def mpc_reset(self, robots, params=None):
+        """OMPC::init for the robot slots: output and FIFO zero, trajectory mode; the parameters hold until the next reset."""
+        rb = np.ascontiguousarray(robots, dtype=np.int32).reshape(-1)
+        p = params if params is not None else self.mpc_params()
+        _chk(self.L, self.L.topay_mpc_reset(self.h, len(rb), _ip(rb), C.byref(p)))
+
+    def mpc_set_direct(self, robots, direct_pos=None):
+        """OMPC::setDirect with direct_pos [n, 3]; None: back to trajectory mode."""
+        rb = np.ascontiguousarray(robots, dtype=np.int32).reshape(-1)
+        dp = None if direct_pos is None else np.ascontiguousarray(direct_pos, dtype=np.float64).reshape(len(rb), 3)
+        _chk(self.L, self.L.topay_mpc_set_direct(self.h, len(rb), _ip(rb), None if dp is None else _dp(dp)))
+
+    def mpc_cmds(self, robots, t_cur, now_state, want_xopt=False):
+        """One OMPC::getCmd per robot.  Returns (cmd [n, 16] = speed, angular_velocity, q[7], dq[7]; status [n, 4], columns
+        MPC_ST_KEYS; xopt [n, 129, 3] or None)."""
+        rb = np.ascontiguousarray(robots, dtype=np.int32).reshape(-1)
+        n = len(rb)
+        tc = np.ascontiguousarray(np.broadcast_to(np.asarray(t_cur, dtype=np.float64), (n,)))
+        ns = np.ascontiguousarray(now_state, dtype=np.float64).reshape(n, 10)
+        cmd, st = np.zeros((n, 16)), np.zeros((n, 4), dtype=np.int32)
+        xo = np.zeros((n, MPC_MAX_STEPS + 1, 3)) if want_xopt else None
+        _chk(self.L, self.L.topay_mpc_cmds(self.h, n, _ip(rb), _dp(tc), _dp(ns), _dp(cmd), _ip(st), None if xo is None else _dp(xo)))
+        return cmd, st, xo
+
+    def mpc_probe(self, robot, t_cur, now_state, params):
+        """The first QP of mpc_cmds for one robot, the slot untouched: dict with P, q, A, l, u (dense, the reference's order), x, y,
+        z, iters, solved."""
+        nx, nc = self.mpc_qp_dims(params)
+        ns = np.ascontiguousarray(now_state, dtype=np.float64).reshape(10)
+        o = dict(P=np.zeros((nx, nx)), q=np.zeros(nx), A=np.zeros((nc, nx)), l=np.zeros(nc), u=np.zeros(nc), x=np.zeros(nx), y=np.zeros(nc),
+                 z=np.zeros(nc))
+        info = np.zeros(2, dtype=np.int32)
+        _chk(self.L, self.L.topay_mpc_probe(self.h, int(robot), float(t_cur), _dp(ns), _dp(o["P"]), _dp(o["q"]), _dp(o["A"]), _dp(o["l"]),
+                                            _dp(o["u"]), _dp(o["x"]), _dp(o["y"]), _dp(o["z"]), _ip(info)))
+        o["iters"], o["solved"] = int(info[0]), int(info[1])
+        return o
+
+    def mpc_get_state(self, robot):
+        """(output [2, 128], fifo [128, 2], mode) of the slot."""
+        out, ff, mode = np.zeros((2, MPC_MAX_STEPS)), np.zeros((MPC_MAX_STEPS, 2)), C.c_int(0)
+        _chk(self.L, self.L.topay_mpc_get_state(self.h, int(robot), _dp(out), _dp(ff), C.byref(mode)))
+        return out, ff, mode.value
+
+    def mpc_ms(self):
+        """Device time of the last mpc_cmds / track_follow, milliseconds."""
+        ms = np.zeros(1)
+        _chk(self.L, self.L.topay_mpc_ms(self.h, _dp(ms)))
+        return float(ms[0])
+
+    def sim_reset(self, robots, state0, delay_cmds=20):
+        rb = np.ascontiguousarray(robots, dtype=np.int32).reshape(-1)
+        s0 = np.ascontiguousarray(state0, dtype=np.float64).reshape(len(rb), 10)
+        _chk(self.L, self.L.topay_sim_reset(self.h, len(rb), _ip(rb), _dp(s0), int(delay_cmds)))
+
+    def sim_step(self, robots, cmd, ticks):
+        """One command (cmd [n, 16] or None) into every robot's actuator FIFO, then `ticks` ticks of 0.01 s.  Returns states [n, 10]."""
+        rb = np.ascontiguousarray(robots, dtype=np.int32).reshape(-1)
+        n = len(rb)
+        cm = None if cmd is None else np.ascontiguousarray(cmd, dtype=np.float64).reshape(n, 16)
+        st = np.zeros((n, 10))
+        _chk(self.L, self.L.topay_sim_step(self.h, n, _ip(rb), None if cm is None else _dp(cm), int(ticks), _dp(st)))
+        return st
+
+    def track_follow(self, robots, t0, periods, ticks_per_period=2):
+        """`periods` control periods on the device: command, simulator step, t += 1 / ctrl_freq.  Returns (states [n, periods, 10],
+        cmds [n, periods, 16], status [n, periods, 4])."""
+        rb = np.ascontiguousarray(robots, dtype=np.int32).reshape(-1)
+        n = len(rb)
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, dtype=np.float64), (n,)))
+        st, cm, ss = np.zeros((n, periods, 10)), np.zeros((n, periods, 16)), np.zeros((n, periods, 4), dtype=np.int32)
+        _chk(self.L, self.L.topay_track_follow(self.h, n, _ip(rb), _dp(t), int(periods), int(ticks_per_period), _dp(st), _dp(cm), _ip(ss)))
+        return st, cm, ss
 
     def replan_inputs(self, robots, t_since_replan, t_since_begin, global_goal, planning_budget, planning_horizon):
         """The endpoints of Planner::replanCallback: (start [n, 10], start_v [n, 10], goal [n, 10], goal_source [n])."""

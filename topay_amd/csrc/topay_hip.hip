@@ -32,6 +32,7 @@
 #include "topay_kernels.h"
 #include "topay_world.h"
 #include "topay_sense.h"
+#include "topay_mpc.h"
 
 // host side, in this order: each header uses what the ones before it define
 #include "topay_host_ctx.h"
@@ -45,3 +46,4 @@
 #include "topay_host_track.h"
 #include "topay_host_ee.h"
 #include "topay_host_sense.h"
+#include "topay_host_mpc.h"

@@ -332,6 +332,13 @@ struct topay_ctx {
   size_t sense_scan_points = 0;
   hipEvent_t sense_ev[2] = {nullptr, nullptr};
   double sense_ms[4] = {0, 0, 0, 0};   // scan, insert, flush, commit with the fields
+  // the tracking controller and the fake robot (topay_host_mpc.h): OMPC's and moma_sim's state per robot slot (allocated by the
+  // first reset, zero = never reset), the host's copy of each slot's parameters, the uploads / outputs of a call, the dense QP
+  // of topay_mpc_probe, the device time of the last topay_mpc_cmds / topay_track_follow
+  DevBuf mpc_slots, mpc_sims, mpc_io, mpc_dense;
+  std::vector<topay_mpc_params_t> mpc_prm;
+  std::vector<char> mpc_have, sim_have;
+  double mpc_ms = 0.0;
   int trace_cap = 0;
   DevBatch db;
   bool have_traj = false, solved = false;
