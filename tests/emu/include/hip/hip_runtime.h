@@ -315,10 +315,15 @@ inline hipError_t hipMemcpyToSymbolAsync(void* sym, const void* src, size_t n, s
   memcpy((char*)sym + off, src, n);
   return 0;
 }
-inline hipError_t hipStreamCreate(hipStream_t* s) { *s = nullptr; return 0; }
+// Live streams and events, exported like the allocations.  A stream is a handle of its own (never null, never another stream's),
+// so that the library's comparisons of streams mean what they mean on the device.
+inline long g_emu_live_streams = 0, g_emu_live_events = 0;
+extern "C" __attribute__((used, visibility("default"))) inline long topay_emu_live_streams() { return g_emu_live_streams; }
+extern "C" __attribute__((used, visibility("default"))) inline long topay_emu_live_events() { return g_emu_live_events; }
+inline hipError_t hipStreamCreate(hipStream_t* s) { *s = new char(0); g_emu_live_streams++; return 0; }
 #define hipStreamNonBlocking 1
-inline hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned, int) { *s = nullptr; return 0; }
-inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = nullptr; return 0; }
+inline hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned, int) { return hipStreamCreate(s); }
+inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { return hipStreamCreate(s); }
 enum { hipHostMallocMapped = 2, hipHostMallocCoherent = 0x40000000 };
 inline hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = calloc(n ? n : 1, 1); g_emu_live_allocs += *p != nullptr; return *p ? 0 : 2; }
 inline hipError_t hipHostFree(void* p) { g_emu_live_allocs -= p != nullptr; free(p); return 0; }
@@ -327,10 +332,10 @@ enum { hipErrorNotReady = 600 };
 inline hipError_t hipStreamQuery(hipStream_t) { return 0; }
 struct hipDeviceProp_t { int multiProcessorCount = 2; };   // two 'CUs': the persistent launches of the tests really loop
 inline hipError_t hipGetDeviceProperties(hipDeviceProp_t* p, int) { *p = hipDeviceProp_t(); return 0; }
-inline hipError_t hipStreamDestroy(hipStream_t) { return 0; }
+inline hipError_t hipStreamDestroy(hipStream_t s) { g_emu_live_streams -= s != nullptr; delete (char*)s; return 0; }
 inline hipError_t hipStreamSynchronize(hipStream_t) { return 0; }
-inline hipError_t hipEventCreate(hipEvent_t* e) { *e = new hipEvent_emu(); return 0; }
-inline hipError_t hipEventDestroy(hipEvent_t e) { delete e; return 0; }
+inline hipError_t hipEventCreate(hipEvent_t* e) { *e = new hipEvent_emu(); g_emu_live_events++; return 0; }
+inline hipError_t hipEventDestroy(hipEvent_t e) { g_emu_live_events -= e != nullptr; delete e; return 0; }
 inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t) { e->t = std::chrono::steady_clock::now(); return 0; }
 inline hipError_t hipEventSynchronize(hipEvent_t) { return 0; }
 inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return 0; }

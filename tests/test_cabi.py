@@ -330,8 +330,11 @@ def test_a_destroyed_context_has_given_back_every_allocation():
     """Device buffers own their memory (DevBuf frees in its destructor, topay_destroy frees the members by `delete`): the
     emulator's count of live hipMalloc / hipHostMalloc allocations is the same after topay_destroy as before topay_create,
     for a context that went through a map build, set_init_traj, a solve, the gate, a getter, the front-end entries with
-    function-local buffers (dense path, connect collision, Reeds-Shepp, JPS), the roadmap, the joint-space search and a
-    planning call.  The single entries are also balanced one by one while the context lives: a local buffer is freed by scope.
+    function-local buffers (dense path, connect collision, Reeds-Shepp, JPS), the roadmap, the joint-space search, a
+    planning call, a world generation, a sensor cloud inserted and committed, a tracked trajectory swept, an end-effector goal
+    and one control period of the tracking controller.  The single entries are also balanced one by one while the context
+    lives: a local buffer is freed by scope.  The same holds for events and streams: every stage's stopwatch owns its pair of
+    events (DevTimer), so the emulator's counts of live events and live streams are back where they were too.
 
     topay_dense_path has no input that fails after its allocations without faking an error: every argument check comes
     before them, and what follows can only fail through a HIP call, which the emulator never fails.  So that path is
@@ -344,9 +347,12 @@ def test_a_destroyed_context_has_given_back_every_allocation():
     L = api.load(EMU_LIB)
     L.topay_emu_live_allocations.restype = C.c_long
     live = L.topay_emu_live_allocations
+    L.topay_emu_live_events.restype = C.c_long
+    L.topay_emu_live_streams.restype = C.c_long
     tb = wl.TablesBatch(2, 2, base_seed=2024, nthreads=8)
     gc.collect()                                   # (contexts of earlier tests that are garbage go now, not in between)
     before = live()
+    events_before, streams_before = L.topay_emu_live_events(), L.topay_emu_live_streams()
     p = api.default_params(L)
     p.s1_lbfgs.max_iterations = 20
     p.s2_lbfgs.max_iterations = 20
@@ -384,9 +390,24 @@ def test_a_destroyed_context_has_given_back_every_allocation():
     first = [int(np.nonzero(tb.scen == s_)[0][0]) for s_ in tb.scenarios]
     opt.plan_calls(start[first], end[first], map_ids=mid[first], params=opt.plan_params(topo=dict(max_sample_num=200), mcrrt=dict(max_iter=50)))
     opt.plan_trajs([0, 1])
-    assert live() > before
+    # the subjects with stopwatches and state of their own, each on the smallest map its tests use: a 2.4 x 2.4 x 1.6 m
+    # tables world (24 x 24 x 16 cells) in slot 8, a belief on 24 x 24 x 12 voxels in slot 7
+    assert opt.generate_worlds(api.world_params(0, size_xy=2.4, size_z=1.6, lib=L), [5], first_map_id=8)[0] != 0
+    opt.sense_reset([7], origin=(-1.2, -1.2, 0.0), res=0.1, dims=(24, 24, 12), min_b=(-1.2, -1.2, 0.0), max_b=(1.2, 1.2, 1.2))
+    opt.sense_insert([7], [np.array([[0.85, 0.05, 0.55, 0.0]], dtype=np.float32)], [(0.05, 0.05, 0.55)], opt.sense_params(point_filt_num=1))
+    opt.sense_commit([7])
+    co = np.zeros((1, 9, 6))
+    co[0, 1, 4] = 0.5                              # one piece, 0.5 m along x in 1 s
+    opt.track_set(3, 1, [-0.5, 0.0, 0.0], [1.0], co)
+    opt.track_safe([3], [8])
+    opt.ee_goals(np.zeros((1, 10)), opt.ee_pose(np.full((1, 10), 0.1)), map_ids=[8], params=opt.ee_params(lbfgs=dict(max_iterations=2)))
+    opt.mpc_reset([3])
+    opt.sim_reset([3], np.zeros((1, 10)))
+    opt.track_follow([3], 0.0, 1)
+    assert live() > before and L.topay_emu_live_events() > events_before
     opt.close()
     assert live() == before
+    assert L.topay_emu_live_events() == events_before and L.topay_emu_live_streams() == streams_before
     tb.close()
 
 
@@ -443,3 +464,138 @@ def test_candidate_views_agree_across_getters_and_gates(three_class_batch):
     f, st, rep = emu.check_feasible(report=True)
     assert list(f) == [True, False, False] and list(st) == [True, False, False]
     assert rep.tobytes() == gold[1].tobytes()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Status codes of the slot checks: every entry that takes map slots or robot slots, on the lane emulator
+# ---------------------------------------------------------------------------------------------------------------------
+MAX_MAPS, TRACK_SLOTS = 4096, 4096      # TOPAY_MAX_MAPS, TOPAY_TRACK_SLOTS
+EMPTY_MAP, ROBOT = 9, 3                 # a map slot that is never filled; the robot slot with an end_traj, a controller, a simulator
+
+
+@pytest.fixture(scope="module")
+def slot_ctx():
+    """One emulator context: map slot 0 set by topay_set_map (8 x 8 x 2 cells, every distance 1 m), robot slot ROBOT with a
+    one-piece end_traj, a controller and a simulator; a second context for topay_share_maps."""
+    from conftest import EMU_LIB
+
+    o = api.MomaTrajOptBatch(lib_path=EMU_LIB)
+    o.set_map([0, 0, 0], 0.5, [8, 8, 2], [0, 0, 0], [4, 4, 1], np.ones(64), np.ones(128), 0)
+    co = np.zeros((1, 9, 6))
+    co[0, 1, 4] = 0.5
+    o.track_set(ROBOT, 1, [1.0, 1.0, 0.0], [1.0], co)
+    o.mpc_reset([ROBOT])
+    o.sim_reset([ROBOT], np.zeros((1, 10)))
+    other = api.MomaTrajOptBatch(lib_path=EMU_LIB)
+    yield o, other
+    other.close()
+    o.close()
+
+
+def _tiny_world(o):
+    return api.world_params(0, size_xy=10.0, lib=o.L)
+
+
+def _z(*shape):
+    return np.zeros(shape)
+
+
+# entry -> the call with map slot m in the place of its map_id / only element of its map_ids
+_MAP_ENTRIES = {
+    "topay_set_init_traj": lambda o, x, m: o.set_init_traj([2], _z(2, 10), map_ids=[m]),
+    "topay_get_map": lambda o, x, m: o.L.topay_get_map(o.h, m, None, None, None),
+    "topay_get_map_fields": lambda o, x, m: o.L.topay_get_map_fields(o.h, m, None, None),
+    "topay_get_occupancy": lambda o, x, m: o.L.topay_get_occupancy(o.h, m, None, None, None),
+    "topay_share_maps": lambda o, x, m: x.share_maps(o, m, 1),
+    "topay_whole_body_collision": lambda o, x, m: o.whole_body_collision(_z(1, 10), map_id=m),
+    "topay_connect_collision": lambda o, x, m: o.L.topay_connect_collision(o.h, m, 1, api._ip(np.array([3], dtype=np.int32)), api._dp(_z(9)), api._dp(_z(7)),
+                                                                          api._dp(_z(7)), api._ip(np.zeros(1, dtype=np.int32))),
+    "topay_plan2d_jps": lambda o, x, m: o.plan2d_jps(_z(1, 2) + 1.0, _z(1, 2) + 2.0, map_ids=[m]),
+    "topay_topo_paths": lambda o, x, m: o.topo_paths(_z(1, 2) + 1.0, _z(1, 2) + 2.0, map_ids=[m]),
+    "topay_mcrrt_plan": lambda o, x, m: o.mcrrt_plan([2], _z(2, 4), _z(1, 10), _z(1, 10), map_ids=[m]),
+    "topay_plan_calls": lambda o, x, m: o.plan_calls(_z(1, 10) + 1.0, _z(1, 10) + 2.0, map_ids=[m]),
+    "topay_sample_arm": lambda o, x, m: o.sample_arm(_z(1, 10), [1], map_ids=[m]),
+    "topay_sample_scenarios": lambda o, x, m: o.sample_scenarios([1], map_ids=[m]),
+    "topay_track_safe": lambda o, x, m: o.track_safe([ROBOT], [m]),
+    "topay_replan_calls": lambda o, x, m: o.replan_calls([ROBOT], [m], 0.0, 0.0, _z(1, 10), 1.0, 0.1, 5.0),
+    "topay_ee_eval": lambda o, x, m: o.ee_eval(_z(1, 10), _z(1, 9), map_ids=[m]),
+    "topay_ee_goals": lambda o, x, m: o.ee_goals(_z(1, 10), _z(1, 9), map_ids=[m]),
+    "topay_ee_select": lambda o, x, m: o.ee_select([0], 1, _z(1, 10), _z(1), [0], _z(1, 9), map_ids=[m]),
+    "topay_sense_insert": lambda o, x, m: o.sense_insert([m], [np.zeros((0, 4), dtype=np.float32)], [[0.0, 0.0, 0.0]]),
+    "topay_sense_commit": lambda o, x, m: o.sense_commit([m]),
+    "topay_sense_get": lambda o, x, m: o.L.topay_sense_get(o.h, m, None, None, None, None),
+    "topay_sense_scan": lambda o, x, m: o.sense_scan([m], _z(1, 4), 2, 2, 1.0, 1.0),
+    # entries that fill slots: an empty slot is what they are for, so only the two slots out of range
+    "topay_set_map": lambda o, x, m: o.set_map([0, 0, 0], 0.5, [8, 8, 2], [0, 0, 0], [4, 4, 1], np.ones(64), np.ones(128), m),
+    "topay_build_esdf_fields": lambda o, x, m: o.build_esdf_fields([0, 0, 0], 0.5, [8, 8, 2], [0, 0, 0], [4, 4, 1], np.zeros(64, dtype=np.int8), None,
+                                                                   np.zeros(128, dtype=np.int8), map_id=m),
+    "topay_generate_worlds": lambda o, x, m: o.generate_worlds(_tiny_world(o), [1], first_map_id=m),
+    "topay_generate_episodes": lambda o, x, m: o.generate_episodes(_tiny_world(o), [1], first_map_id=m),
+    "topay_sense_reset": lambda o, x, m: o.sense_reset([m], (0, 0, 0), 0.5, (8, 8, 2), (0, 0, 0), (4, 4, 1)),
+}
+_FILLERS = ("topay_set_map", "topay_build_esdf_fields", "topay_generate_worlds", "topay_generate_episodes", "topay_sense_reset")
+# entry -> the call with the robot slots r (a list; the entries of one robot take r[0])
+_ROBOT_ENTRIES = {
+    "topay_track_set": lambda o, r: o.track_set(r[0], 1, [1.0, 1.0, 0.0], [1.0], _z(1, 9, 6)),
+    "topay_track_commit_plan": lambda o, r: o.track_commit_plan(r, [0] * len(r)),
+    "topay_track_get": lambda o, r: o.track_get(r[0]),
+    "topay_track_clear": lambda o, r: o.track_clear(r[0]),
+    "topay_track_safe": lambda o, r: o.track_safe(r, [0] * len(r)),
+    "topay_replan_inputs": lambda o, r: o.replan_inputs(r, 0.0, 0.0, _z(len(r), 10), 0.1, 5.0),
+    "topay_replan_calls": lambda o, r: o.replan_calls(r, [0] * len(r), 0.0, 0.0, _z(len(r), 10), 1.0, 0.1, 5.0),
+    "topay_mpc_reset": lambda o, r: o.mpc_reset(r),
+    "topay_mpc_set_direct": lambda o, r: o.mpc_set_direct(r),
+    "topay_mpc_cmds": lambda o, r: o.mpc_cmds(r, 0.0, _z(len(r), 10)),
+    "topay_mpc_probe": lambda o, r: o.mpc_probe(r[0], 0.0, _z(10), o.mpc_params()),
+    "topay_mpc_get_state": lambda o, r: o.mpc_get_state(r[0]),
+    "topay_sim_reset": lambda o, r: o.sim_reset(r, _z(len(r), 10)),
+    "topay_sim_step": lambda o, r: o.sim_step(r, None, 0),
+    "topay_track_follow": lambda o, r: o.track_follow(r, 0.0, 1),
+}
+_ONE_ROBOT = ("topay_track_set", "topay_track_get", "topay_track_clear", "topay_mpc_probe", "topay_mpc_get_state")
+
+
+def _slot_cases():
+    out = []
+    for e in _MAP_ENTRIES:
+        out += [(e, "map", "below"), (e, "map", "above")] + ([] if e in _FILLERS else [(e, "map", "empty")])
+    for e in _ROBOT_ENTRIES:
+        out += [(e, "robot", "below"), (e, "robot", "above")] + ([] if e in _ONE_ROBOT else [(e, "robot", "twice")])
+    return out
+
+
+def _run_slot_case(ctx, entry, kind, case):
+    """(status, error text) of the call; a status of 0 comes with an empty text."""
+    o, other = ctx
+    try:
+        if kind == "map":
+            st = _MAP_ENTRIES[entry](o, other, {"below": -1, "above": MAX_MAPS, "empty": EMPTY_MAP}[case])
+        else:
+            st = _ROBOT_ENTRIES[entry](o, {"below": [-1], "above": [TRACK_SLOTS], "twice": [ROBOT, ROBOT]}[case])
+    except api.TopayError as e:
+        m = re.match(r"topay status (-?\d+): (.*)", str(e), flags=re.S)
+        return int(m.group(1)), m.group(2)
+    if isinstance(st, int) and st != 0:
+        return st, o.L.topay_last_error().decode()
+    return 0, ""
+
+
+# The record: the status every case returned on commit 4d8ea03, the last one before the slot checks were gathered into
+# check_map_slots and check_robot_slots, taken by running _run_slot_case there.  -1 INVALID_ARG, -3 NO_MAP, -4 NO_TRAJ.  Most
+# entries answer a slot out of range with INVALID_ARG, an empty map slot with NO_MAP and a robot named twice with INVALID_ARG ...
+_SLOT_STATUS = {c: {"below": -1, "above": -1, "empty": -3, "twice": -1}[c[2]] for c in _slot_cases()}
+# ... and these do not: the batch upload and the map getters say NO_MAP for any slot they cannot serve; topay_track_commit_plan
+# looks at the plan store first (this context has run no planning call: NO_TRAJ); the sweep and the endpoints take a robot twice.
+for _e in ("topay_set_init_traj", "topay_get_map", "topay_get_map_fields", "topay_get_occupancy"):
+    _SLOT_STATUS[(_e, "map", "below")] = _SLOT_STATUS[(_e, "map", "above")] = -3
+for _c in ("below", "above", "twice"):
+    _SLOT_STATUS[("topay_track_commit_plan", "robot", _c)] = -4
+_SLOT_STATUS[("topay_track_safe", "robot", "twice")] = _SLOT_STATUS[("topay_replan_inputs", "robot", "twice")] = 0
+
+
+@pytest.mark.parametrize("entry,kind,case", _slot_cases(), ids=lambda v: str(v))
+def test_slot_checks_keep_their_status_codes(slot_ctx, entry, kind, case):
+    status, text = _run_slot_case(slot_ctx, entry, kind, case)
+    assert status == _SLOT_STATUS[(entry, kind, case)], (status, text)
+    if status != 0:
+        assert text and entry in text, (status, text)

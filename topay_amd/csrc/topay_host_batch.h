@@ -22,7 +22,7 @@ static topay_status set_init_traj_impl(topay_ctx* c, int batch, const int* path_
                                        const double* boundary_acc, const int* map_ids, hipMemcpyKind kind) {
   if (!c || batch <= 0 || !path_len || !init_paths) return TOPAY_ERR_INVALID_ARG;
   HIPCHK(hipSetDevice(c->device));
-  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }   // inputs of a solve in flight stay untouched
+  if (topay_status ws = wait_pending(c)) return ws;   // inputs of a solve in flight stay untouched
   c->have_traj = false;
   c->solved = false;
   std::vector<long long> off(batch + 1, 0);
@@ -32,11 +32,9 @@ static topay_status set_init_traj_impl(topay_ctx* c, int batch, const int* path_
     off[b + 1] = off[b] + path_len[b];
     Pmax = std::max(Pmax, path_len[b]);
   }
+  if (check_map_slots(c, batch, map_ids, kMapResident, "topay_set_init_traj") != TOPAY_OK) return TOPAY_ERR_NO_MAP;   // (out of range too)
   std::vector<int> mids(batch, 0);
-  for (int b = 0; b < batch; b++) {
-    if (map_ids) mids[b] = map_ids[b];
-    if (mids[b] < 0 || mids[b] >= TOPAY_MAX_MAPS || !c->have_map[mids[b]]) { set_err("map slot not set"); return TOPAY_ERR_NO_MAP; }
-  }
+  if (map_ids) mids.assign(map_ids, map_ids + batch);
   c->B = batch;
   c->Pmax = Pmax;
   c->h_map_id = mids;
@@ -257,7 +255,7 @@ template <bool EVAL, typename... Args>
 static topay_status launch_classes(topay_ctx* c, bool persistent, Args... args) {
   // One launch per N-bucket, each on its own stream so that the tail of one bucket overlaps the others.
   // Longest jobs first.  The context's main stream waits for all of them (events), so the caller's
-  // ev0/ev1 pair on the main stream brackets the whole solve.
+  // stopwatch on the main stream brackets the whole solve.
   const ClassDef* ct = kClassTable;
   int launches = 0, helper_launches = 0, off = 0;
   topay_status ps = push_params(c);
@@ -363,7 +361,7 @@ topay_status topay_set_init_traj(topay_ctx* c, int batch, const int* path_len, c
 topay_status topay_reset(topay_ctx* c) {
   if (!c || !c->have_traj) return TOPAY_ERR_NO_TRAJ;
   HIPCHK(hipSetDevice(c->device));
-  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }   // inputs of a solve in flight stay untouched
+  if (topay_status ws = wait_pending(c)) return ws;   // inputs of a solve in flight stay untouched
   c->solved = false;
   return run_init(c);
 }
@@ -371,10 +369,7 @@ topay_status topay_reset(topay_ctx* c) {
 topay_status topay_optimize_async(topay_ctx* c) {
   if (!c || !c->have_traj) return TOPAY_ERR_NO_TRAJ;
   HIPCHK(hipSetDevice(c->device));
-  if (c->pending) {  // a second solve on a context whose first has not been waited for: finish that one first
-    topay_status s0 = topay_synchronize(c);
-    if (s0 != TOPAY_OK) return s0;
-  }
+  if (topay_status s0 = wait_pending(c)) return s0;   // a second solve on a context whose first has not been waited for: finish that one first
   {
     // Dispatch gate.  Batches of different contexts run on different streams; issued at the same time their waves
     // would be dispatched alternately and both would end in the same long tail.  Holding the new batch back until
@@ -414,7 +409,7 @@ topay_status topay_optimize_async(topay_ctx* c) {
     c->db.started = (int*)dp;
     g_last_issued = c;
   }
-  HIPCHK(hipEventRecord(c->ev0, c->stream));
+  HIPCHK(c->solve_timer.start(c->stream));
   // cancellation state of this solve: nobody has succeeded yet (clock "infinity"), nothing is interrupted
   c->h_cancel[0] = 0;
   {
@@ -444,7 +439,7 @@ topay_status topay_optimize_async(topay_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     return s;
   }
-  HIPCHK(hipEventRecord(c->ev1, c->stream));
+  HIPCHK(c->solve_timer.stop(c->stream));
   c->pending = true;
   return TOPAY_OK;
 }
@@ -454,9 +449,7 @@ topay_status topay_synchronize(topay_ctx* c) {
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipStreamSynchronize(c->stream));
   if (c->pending) {
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    c->last_ms = ms;
+    HIPCHK(c->solve_timer.read(&c->last_ms));
     c->solved = true;
     c->pending = false;
     // (a candidate whose history block could not hold the gate's scratch -- a small mem_size -- was left ungated by its
@@ -506,7 +499,7 @@ topay_status topay_set_groups(topay_ctx* c, const int* group_id, int cancel_budg
   if (!c || !c->have_traj) return TOPAY_ERR_NO_TRAJ;
   if (cancel_budget < 0) return TOPAY_ERR_INVALID_ARG;
   HIPCHK(hipSetDevice(c->device));
-  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }
+  if (topay_status ws = wait_pending(c)) return ws;
   const bool had_groups = c->n_groups > 0;
   c->h_group.clear();
   c->n_groups = 0;
@@ -573,7 +566,7 @@ topay_status topay_cancel(topay_ctx* c) {
 topay_status topay_get_interrupted(topay_ctx* c, int* interrupted) {
   if (!c || !c->have_traj || !interrupted) return TOPAY_ERR_NO_TRAJ;
   HIPCHK(hipSetDevice(c->device));
-  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }
+  if (topay_status ws = wait_pending(c)) return ws;
   HIPCHK(d2h_sync(c, interrupted, c->interrupted.as<int>(), (size_t)c->B));
   return TOPAY_OK;
 }

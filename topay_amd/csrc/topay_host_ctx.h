@@ -1,6 +1,6 @@
-// Host side of the C-ABI, part 1: the error text, owning device buffers (grow-and-discard, grow-and-keep) and the carver of
-// packed blocks, the launch-class table, the state of the planning call by subject (PlanStore: the winners of the last call
-// and the layout of its buffers; PlanWork: the buffers of a try and the stage clock), the context, parameters, create and destroy.
+// Host side of the C-ABI, part 1: the error text, owning device buffers (grow-and-discard, grow-and-keep), the carver of packed
+// blocks and the stopwatch (DevTimer), the launch-class table, the state of every subject as one struct each (PlanStore, PlanWork,
+// FrontState, TrackState, EeState, WorldState, SenseState, MpcState, EdtState), the context, parameters, create and destroy.
 
 #pragma once
 
@@ -88,6 +88,45 @@ struct DevBuf {
   }
   template <typename B> topay_status place(B& block) {   // ... whose layout is the block's own lay(Carver&)
     return carve([&](Carver& k) { block.lay(k); });
+  }
+};
+
+// A stopwatch on a stream: a pair of events that it owns, created on first use and destroyed with it.  Move-only, like DevBuf.
+// Every timed stage has one of its own, so no stage's time is overwritten by another's records.
+struct DevTimer {
+  hipEvent_t a = nullptr, b = nullptr;
+  bool stopped = false;   // stop() has been recorded since the last start()
+  DevTimer() = default;
+  DevTimer(const DevTimer&) = delete; DevTimer& operator=(const DevTimer&) = delete;
+  DevTimer(DevTimer&& o) noexcept { *this = std::move(o); }
+  DevTimer& operator=(DevTimer&& o) noexcept {
+    if (this != &o) { release(); a = o.a; b = o.b; stopped = o.stopped; o.a = o.b = nullptr; o.stopped = false; }
+    return *this;
+  }
+  ~DevTimer() { release(); }
+  hipError_t start(hipStream_t stream) {
+    stopped = false;
+    hipError_t e = a ? hipSuccess : hipEventCreate(&a);
+    if (e == hipSuccess && !b) e = hipEventCreate(&b);
+    return e == hipSuccess ? hipEventRecord(a, stream) : e;
+  }
+  hipError_t stop(hipStream_t stream) {
+    const hipError_t e = hipEventRecord(b, stream);
+    stopped = e == hipSuccess;
+    return e;
+  }
+  // milliseconds between start and stop, once the stream has been waited for; an error when this start was never stopped
+  hipError_t read(double* ms) const {
+    float f = 0.f;
+    const hipError_t e = stopped ? hipEventElapsedTime(&f, a, b) : hipErrorNotReady;
+    if (e == hipSuccess) *ms = f;
+    return e;
+  }
+  void release() {
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+    a = b = nullptr;
+    stopped = false;
   }
 };
 
@@ -219,11 +258,137 @@ struct PlanWork {
   DevBuf io, tab, mc;     // per front-end launch: the calls, candidate table + dense paths, search inputs / outputs
   DevBuf paths, bvel;     // the try's init paths and boundary velocities, appended launch by launch
   DevBuf idx, win;        // index block of the hand-off to the solver, then of the store; winner block
-  std::vector<hipEvent_t> events;   // PlanClock: pairs of events, and per pair its stage and whether its end was recorded in this call
-  std::vector<int> event_stage;
-  std::vector<char> event_done;
+  std::vector<DevTimer> timers;   // PlanClock: one stopwatch per timed stretch of a call, and the stage each one counts for
+  std::vector<int> timer_stage;
   double stage_ms[TOPAY_PLAN_MS_LEN] = {0};
   int chunk = 0;   // topay_plan_test_chunk: calls per front-end launch, 0 = the constant
+};
+
+// The joint-space search and the roadmap (topay_host_front.h): node tables, Reeds-Shepp words and inputs of the last
+// topay_mcrrt_plan (topay_mcrrt_nodes); graphs, raw paths and point buffers of the last topay_topo_paths (topay_topo_graph /
+// _raw_paths) with what sized them, and the stopwatch of k_topo when the planning call does not bring its own.
+struct FrontState {
+  DevBuf mc_i, mc_d, mc_k, mc_rs, mc_in;
+  int mc_n = 0, mc_node_cap = 0;
+  DevBuf tp_i, tp_d, tp_raw, tp_pts, tp_io;
+  int tp_n = 0, tp_pt_cap = 0, tp_nbuf = 0;
+  topay_topo_params_t tp_P;
+  DevTimer tp_timer;
+};
+
+// Tracked trajectories (topay_host_track.h): the arena, the slots' descriptors (host: what the kernels are handed per call),
+// the upload block of topay_track_set, the inputs / outputs of the sweep and endpoint kernels, the device time of the last
+// k_track_safe launch.
+struct TrackSlot { topay::TrackDesc d[2] = {{0, 0, 0}, {0, 0, 0}}; long long cap[2] = {0, 0}; double T[2] = {0, 0}; };   // [0] end_traj, [1] global_traj
+struct TrackState {
+  DevBuf arena, stage, io;
+  size_t used = 0;   // doubles of the arena handed out
+  std::vector<TrackSlot> slots;
+  DevTimer safe_timer;
+  double safe_ms = 0.0;
+  const topay::TrackDesc* find(int robot, int w) const { return slots.empty() || slots[robot].d[w].N <= 0 ? nullptr : &slots[robot].d[w]; }
+};
+
+// End-effector goals (topay_host_ee.h): the L-BFGS history of the last topay_ee_goals (kept until the next call), the inputs /
+// outputs of the ee kernels, the device time of the last topay_ee_goals.
+struct EeState {
+  DevBuf hist, io;
+  DevTimer timer;
+  double ms = 0.0;
+};
+
+// topay_generate_worlds / topay_generate_episodes (topay_host_world.h): the occupancy grids of the last call stay for
+// topay_get_occupancy (slots [first, first + n) of dimensions dims), its primitive lists and its inputs / outputs; the rasteriser
+// path it took (1: masks in LDS, 2: byte stores) and its device time by stage (generation, rasterisation, fields, sampling).
+struct WorldState {
+  DevBuf occ, prims, io;
+  int first = 0, n = 0, dims[3] = {0, 0, 0}, path = 0;
+  int force_path = 0, max_tries = 0;   // test hooks: 2 = byte stores whatever the map; tries per arm of an episode (0: 2000)
+  enum { kGen, kRaster, kFields, kSample };
+  DevTimer timer[4];
+  double ms[4] = {0, 0, 0, 0};
+  // the three grids of the call lie one after the other, each on a 16-byte boundary (the first path stores 16 bytes at a time)
+  static size_t pad16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+  const signed char* occ3_of(int slot, int* d) const {
+    if (n <= 0 || slot < first || slot >= first + n || !occ.p) return nullptr;
+    for (int a = 0; a < 3; a++) d[a] = dims[a];
+    return (const signed char*)occ.p + (size_t)(slot - first) * dims[0] * dims[1] * dims[2];
+  }
+  const signed char* occ2_of(int slot, bool critical) const {   // (of a slot that has an occ3_of: after the 3-D grids, then the 2-D ones)
+    const size_t n2 = (size_t)dims[0] * dims[1], b3 = pad16((size_t)n * n2 * dims[2]), b2 = pad16((size_t)n * n2);
+    return (const signed char*)occ.p + b3 + (critical ? b2 : 0) + (size_t)(slot - first) * n2;
+  }
+  // slots [first_, first_ + n_) are refilled by something else than the world generator: its grids no longer describe them
+  void forget(int first_, int n_) {
+    if (n > 0 && first_ < first + n && first < first_ + n_) { n = 0; occ.release(); }
+  }
+};
+
+// Sensor clouds (topay_host_sense.h): per map slot the belief (log-odds, packed counts and cache box in one block), the batch
+// counter, the rays counted since the last flush and the parameters of the last insert (topay_sense_commit reads l_occ and
+// chassis_height from them); the uploads of a call; the points of the last topay_sense_scan; the occupancy grids of the last
+// topay_sense_commit and where each slot's lie in them (topay_get_occupancy); the device time of the last scan, insert, flush
+// and commit with the fields.
+struct SenseBelief {
+  DevBuf buf;
+  float* logodds = nullptr; int* cnt = nullptr; int* box = nullptr;
+  topay_map_desc_t desc;
+  topay_sense_params_t prm;
+  int batch_counter = 0, pending_rays = 0;
+  size_t occ3_off = 0, occ2_off = 0, occ2c_off = 0;
+  bool have = false, have_occ = false;
+};
+struct SenseState {
+  std::vector<SenseBelief> slot;   // sized by the first topay_sense_reset
+  DevBuf pts, io, scan, occ;
+  size_t scan_points = 0;
+  enum { kScan, kInsert, kFlush, kCommit };
+  DevTimer timer[4];
+  double ms[4] = {0, 0, 0, 0};
+  bool has_belief(int m) const { return m >= 0 && m < (int)slot.size() && slot[m].have; }
+  bool has_occ(int m) const { return m >= 0 && m < (int)slot.size() && slot[m].have_occ; }
+  const signed char* occ3_of(int m, int* d) const {
+    if (!has_occ(m)) return nullptr;
+    for (int a = 0; a < 3; a++) d[a] = slot[m].desc.dims[a];
+    return (const signed char*)occ.p + slot[m].occ3_off;
+  }
+  const signed char* occ2_of(int m, bool critical) const { return (const signed char*)occ.p + (critical ? slot[m].occ2c_off : slot[m].occ2_off); }
+  // slots [first, first + n) are refilled: the grids of the last commit no longer describe them
+  void forget(int first, int n) {
+    for (int m = first; m < first + n && m < (int)slot.size(); m++) slot[m].have_occ = false;
+  }
+};
+
+// The tracking controller and the fake robot (topay_host_mpc.h): OMPC's and moma_sim's state per robot slot (allocated by the
+// first reset, zero = never reset), the host's copy of each slot's parameters, the uploads / outputs of a call, the dense QP
+// of topay_mpc_probe, the device time of the last topay_mpc_cmds / topay_track_follow.
+struct MpcState {
+  DevBuf slots, sims, io, dense;
+  std::vector<topay_mpc_params_t> prm;
+  std::vector<char> have, sim_have;
+  DevTimer timer;
+  double ms = 0.0;
+  topay_status alloc(hipStream_t stream) {   // the two slot arrays, zeroed, by the first reset
+    if (slots.p) return TOPAY_OK;
+    topay_status s;
+    if ((s = slots.ensure(sizeof(topay::MpcSlot) * TOPAY_TRACK_SLOTS)) != TOPAY_OK) return s;
+    if ((s = sims.ensure(sizeof(topay::SimSlot) * TOPAY_TRACK_SLOTS)) != TOPAY_OK) return s;
+    HIPCHK(hipMemsetAsync(slots.p, 0, slots.bytes, stream));
+    HIPCHK(hipMemsetAsync(sims.p, 0, sims.bytes, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    prm.resize(TOPAY_TRACK_SLOTS);
+    have.assign(TOPAY_TRACK_SLOTS, 0);
+    sim_have.assign(TOPAY_TRACK_SLOTS, 0);
+    return TOPAY_OK;
+  }
+};
+
+// The ESDF construction (topay_host_maps.h): the uploaded occupancy grids, its workspace (released once the fields sit in
+// their slots) and the device time of the last build.
+struct EdtState {
+  DevBuf occ, thr, tmp1, tmp2, v, z, out2;
+  DevTimer timer;
+  double ms = 0.0;
 };
 
 struct topay_ctx {
@@ -231,7 +396,6 @@ struct topay_ctx {
   topay_params_t hp;
   DevParams dp;
   hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // maps
   std::vector<DevMap> hmaps = std::vector<DevMap>(TOPAY_MAX_MAPS);
   std::vector<DevBuf> map2d = std::vector<DevBuf>(TOPAY_MAX_MAPS), map3d = std::vector<DevBuf>(TOPAY_MAX_MAPS);
@@ -283,68 +447,43 @@ struct topay_ctx {
   bool steal = true;         // ... and draining the smaller classes' queues once its own is empty (TOPAY_STEAL=0: profiling)
   int simd_slots = 1024;
   DevBuf qnext;
-  DevBuf mc_i, mc_d, mc_k, mc_rs, mc_in;   // node tables, Reeds-Shepp words and inputs of the last topay_mcrrt_plan
-  int mc_n = 0, mc_node_cap = 0;
-  DevBuf tp_i, tp_d, tp_raw, tp_pts, tp_io;   // graphs, raw paths and point buffers of the last topay_topo_paths (topay_topo_graph / _raw_paths)
-  int tp_n = 0, tp_pt_cap = 0, tp_nbuf = 0;
-  topay_topo_params_t tp_P;
-  PlanWork plan;          // topay_plan_calls: what a try works in, the stage clock
-  PlanStore plan_store;   // ... and the winners of the last call
-  // tracked trajectories (topay_host_track.h): the arena, the slots' descriptors (host: what the kernels are handed per call),
-  // the upload block of topay_track_set and the inputs / outputs of the sweep and endpoint kernels
-  DevBuf tr_arena, tr_stage, tr_io;
-  size_t tr_used = 0;   // doubles of the arena handed out
-  struct TrackSlot { topay::TrackDesc d[2] = {{0, 0, 0}, {0, 0, 0}}; long long cap[2] = {0, 0}; double T[2] = {0, 0}; };   // [0] end_traj, [1] global_traj
-  std::vector<TrackSlot> tr_slots;
-  double tr_safe_ms = 0.0;   // device time of the last k_track_safe launch
-  // end-effector goals (topay_host_ee.h): the L-BFGS history of the last topay_ee_goals (kept until the next call), the inputs /
-  // outputs of the ee kernels, the device time of the last topay_ee_goals
-  DevBuf ee_hist, ee_io;
-  double ee_ms = 0.0;
   DevBuf paths, path_off, path_len, bvel, bacc, scratch;
   DevBuf N, s1_past, map_id, head, tail, start_xy, goal_xy, init_xy, x0;
   DevBuf x, work, hist_s, hist_y, hist_ys, hist_alpha, lu;
-  DevBuf success, cost, stats, xyerr, coef, T, knots, alm, fout, order, trace, elapsed, startus, hwid, sbuf, mstash, feas_cseq, feas_tk, feas_report, feas_flags, edt_occ, edt_thr, edt_tmp1, edt_tmp2, edt_v, edt_z, edt_out2, pb_io;
-  float last_edt_ms = 0.f;
-  // topay_generate_worlds / topay_generate_episodes (topay_host_world.h): the occupancy grids of the last call stay for
-  // topay_get_occupancy (slots [world_first, world_first + world_n) of dimensions world_dims), its primitive lists and its
-  // inputs / outputs; the rasteriser path it took (1: masks in LDS, 2: byte stores) and its device time by stage
-  DevBuf world_occ, world_prims, world_io;
-  int world_first = 0, world_n = 0, world_dims[3] = {0, 0, 0}, world_path = 0;
-  int world_force_path = 0, world_max_tries = 0;   // test hooks: 2 = byte stores whatever the map; tries per arm of an episode (0: 2000)
-  hipEvent_t world_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // stage bounds 0..3, the sampler's launch 4, 5
-  double world_ms[4] = {0, 0, 0, 0};
-  // sensor clouds (topay_host_sense.h): per map slot the belief (log-odds, packed counts and cache box in one block), the batch
-  // counter, the rays counted since the last flush and the parameters of the last
-  // insert (topay_sense_commit reads l_occ and chassis_height from them); the uploads of a call; the points of the last
-  // topay_sense_scan; the occupancy grids of the last topay_sense_commit and where each slot's lie in them (topay_get_occupancy)
-  struct SenseBelief {
-    DevBuf buf;
-    float* logodds = nullptr; int* cnt = nullptr; int* box = nullptr;
-    topay_map_desc_t desc;
-    topay_sense_params_t prm;
-    int batch_counter = 0, pending_rays = 0;
-    size_t occ3_off = 0, occ2_off = 0, occ2c_off = 0;
-    bool have = false, have_occ = false;
-  };
-  std::vector<SenseBelief> sense;   // sized by the first topay_sense_reset
-  DevBuf sense_pts, sense_io, sense_scan, sense_occ;
-  size_t sense_scan_points = 0;
-  hipEvent_t sense_ev[2] = {nullptr, nullptr};
-  double sense_ms[4] = {0, 0, 0, 0};   // scan, insert, flush, commit with the fields
-  // the tracking controller and the fake robot (topay_host_mpc.h): OMPC's and moma_sim's state per robot slot (allocated by the
-  // first reset, zero = never reset), the host's copy of each slot's parameters, the uploads / outputs of a call, the dense QP
-  // of topay_mpc_probe, the device time of the last topay_mpc_cmds / topay_track_follow
-  DevBuf mpc_slots, mpc_sims, mpc_io, mpc_dense;
-  std::vector<topay_mpc_params_t> mpc_prm;
-  std::vector<char> mpc_have, sim_have;
-  double mpc_ms = 0.0;
+  DevBuf success, cost, stats, xyerr, coef, T, knots, alm, fout, order, trace, elapsed, startus, hwid, sbuf, mstash, feas_cseq, feas_tk, feas_report, feas_flags, pb_io;
+  DevTimer solve_timer, eval_timer;   // the solve (topay_optimize_async ... topay_synchronize) and topay_eval_batch
+  // the subjects beside the resident batch and the solver, one struct each (above)
+  FrontState front;
+  PlanWork plan;          // topay_plan_calls: what a try works in, the stage clock
+  PlanStore plan_store;   // ... and the winners of the last call
+  TrackState track;
+  EeState ee;
+  WorldState world;
+  SenseState sense;
+  MpcState mpc;
+  EdtState edt;
   int trace_cap = 0;
   DevBatch db;
   bool have_traj = false, solved = false;
   double last_ms = 0.0;
   int last_launches = 0, last_helper_launches = 0;
 };
+
+static DevLbfgs to_dev_lbfgs(const topay_lbfgs_params_t& a) {
+  DevLbfgs b;
+  b.mem_size = a.mem_size; b.past = a.past; b.max_iterations = a.max_iterations; b.max_linesearch = a.max_linesearch;
+  b.g_epsilon = a.g_epsilon; b.delta = a.delta; b.min_step = a.min_step; b.max_step = a.max_step;
+  b.f_dec_coeff = a.f_dec_coeff; b.s_curv_coeff = a.s_curv_coeff; b.cautious_factor = a.cautious_factor;
+  b.machine_prec = a.machine_prec;
+  return b;
+}
+
+// finite and below `bound` in magnitude (include/topay.h states the bound of every entry that checks its inputs with this)
+static bool all_finite(const double* v, size_t n, double bound = 1.0e9) {
+  for (size_t i = 0; i < n; i++)
+    if (!(std::fabs(v[i]) < bound)) return false;
+  return true;
+}
 
 static void make_dev_params(const topay_params_t& p, DevParams& d) {
   memset(&d, 0, sizeof(d));
@@ -376,14 +515,8 @@ static void make_dev_params(const topay_params_t& p, DevParams& d) {
   d.sample_interval = p.sample_interval;
   d.s1_normal_past = p.s1_normal_past; d.s1_shot_path_past = p.s1_shot_path_past;
   d.s1_shot_path_horizon = p.s1_shot_path_horizon;
-  auto cp = [](const topay_lbfgs_params_t& a, DevLbfgs& b) {
-    b.mem_size = a.mem_size; b.past = a.past; b.max_iterations = a.max_iterations; b.max_linesearch = a.max_linesearch;
-    b.g_epsilon = a.g_epsilon; b.delta = a.delta; b.min_step = a.min_step; b.max_step = a.max_step;
-    b.f_dec_coeff = a.f_dec_coeff; b.s_curv_coeff = a.s_curv_coeff; b.cautious_factor = a.cautious_factor;
-    b.machine_prec = a.machine_prec;
-  };
-  cp(p.s1_lbfgs, d.s1_lbfgs);
-  cp(p.s2_lbfgs, d.s2_lbfgs);
+  d.s1_lbfgs = to_dev_lbfgs(p.s1_lbfgs);
+  d.s2_lbfgs = to_dev_lbfgs(p.s2_lbfgs);
   d.chassis_height = p.chassis_height; d.chassis_colli_radius = p.chassis_colli_radius;
   d.max_v = p.max_v; d.max_a = p.max_a; d.max_w = p.max_w; d.max_dw = p.max_dw;
   for (int i = 0; i < 8; i++) d.colli_length[i] = p.colli_length[i];
@@ -436,6 +569,9 @@ static int sphere_layout_ok(const topay_params_t& p) {
 
 // Every copy goes through the context's own (non-blocking) stream: null-stream operations would wait for the solves of
 // every other context of the process (and they for it), which serialises batches that are meant to overlap.
+// A solve in flight is waited for first by every entry that touches its inputs, reads its results or times a launch of its own.
+static topay_status wait_pending(topay_ctx* c) { return c->pending ? topay_synchronize(c) : TOPAY_OK; }
+
 static hipError_t memcpy_sync(topay_ctx* c, void* dst, const void* src, size_t n, hipMemcpyKind kind) {
   hipError_t e = hipMemcpyAsync(dst, src, n, kind, c->stream);
   if (e != hipSuccess) return e;
@@ -474,8 +610,6 @@ static topay_status validate_params(const topay_params_t* params) {
 
 static topay_status create_device_state(topay_ctx* c, int device) {
   HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  HIPCHK(hipEventCreate(&c->ev0));
-  HIPCHK(hipEventCreate(&c->ev1));
   HIPCHK(hipEventCreate(&c->bstart));
   // One stream per launch class (the last class runs on the main stream), all non-blocking and never the null stream:
   // two contexts then use ten of the sixteen hardware queues the library asks for, and no operation of one context
@@ -526,7 +660,7 @@ static void invalidate_sharers(topay_ctx* owner, int first, int n) {
     bool hit = false;
     for (int m = first; m < first + n; m++) hit = hit || s->map_owner[m] == owner;
     if (!hit) continue;
-    if (s->pending) (void)topay_synchronize(s);
+    (void)wait_pending(s);
     for (int m = first; m < first + n; m++)
       if (s->map_owner[m] == owner) {
         s->map_owner[m] = nullptr;
@@ -556,13 +690,10 @@ static void drop_shared_slots(topay_ctx* c, int first, int n) {
   }
 }
 
-// slots [first, first + n) are refilled by something else than the world generator: its occupancy grids no longer describe them
-static void world_forget(topay_ctx* c, int first, int n) {
-  for (int m = first; m < first + n && m < (int)c->sense.size(); m++) c->sense[m].have_occ = false;   // ... nor do the last commit's
-  if (c->world_n > 0 && first < c->world_first + c->world_n && c->world_first < first + n) {
-    c->world_n = 0;
-    c->world_occ.release();
-  }
+// slots [first, first + n) are refilled: neither the world generator's occupancy grids nor the last commit's describe them any more
+static void forget_occupancy(topay_ctx* c, int first, int n) {
+  c->sense.forget(first, n);
+  c->world.forget(first, n);
 }
 
 static int bucket_of(int N) {
@@ -649,7 +780,7 @@ topay_status topay_set_params(topay_ctx* c, const topay_params_t* params) {
   topay_status vs = validate_params(params);
   if (vs != TOPAY_OK) return vs;
   HIPCHK(hipSetDevice(c->device));
-  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }
+  if (topay_status ws = wait_pending(c)) return ws;
   // what the resident batch was laid out with: number of pieces (init step) and history depth (workspace)
   const bool relayout = params->sample_interval != c->hp.sample_interval || params->min_piece_num != c->hp.min_piece_num ||
                         std::max(params->s1_lbfgs.mem_size, params->s2_lbfgs.mem_size) != std::max(c->hp.s1_lbfgs.mem_size, c->hp.s2_lbfgs.mem_size) ||
@@ -687,7 +818,7 @@ topay_status topay_create(const topay_params_t* params, int device, topay_ctx** 
 
 void topay_destroy(topay_ctx* c) {
   if (!c) return;
-  if (c->pending) (void)topay_synchronize(c);
+  (void)wait_pending(c);
   invalidate_sharers(c, 0, TOPAY_MAX_MAPS);
   drop_shared_slots(c, 0, TOPAY_MAX_MAPS);
   {
@@ -695,11 +826,6 @@ void topay_destroy(topay_ctx* c) {
     g_contexts.erase(std::remove(g_contexts.begin(), g_contexts.end(), c), g_contexts.end());
   }
   (void)hipSetDevice(c->device);
-  for (hipEvent_t e : c->plan.events) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->world_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->sense_ev)
-    if (e) (void)hipEventDestroy(e);
   for (int k = 0; k < topay_ctx::NBUCKET; k++) {
     if (c->bevent[k]) (void)hipEventDestroy(c->bevent[k]);
     if (c->bstream[k] && c->bstream[k] != c->stream) (void)hipStreamDestroy(c->bstream[k]);
@@ -711,10 +837,8 @@ void topay_destroy(topay_ctx* c) {
   (void)topay_comm_destroy(c);
   if (c->h_started) (void)hipHostFree(c->h_started);
   if (c->bstart) (void)hipEventDestroy(c->bstart);
-  if (c->ev0) (void)hipEventDestroy(c->ev0);
-  if (c->ev1) (void)hipEventDestroy(c->ev1);
   if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;   // the device buffers are members: freed here
+  delete c;   // the device buffers and the stopwatches are members: freed here
 }
 
 topay_status topay_params_from_yaml(const char* path_or_text, topay_params_t* params, char* ignored, int ignored_cap) {

@@ -89,7 +89,7 @@ topay_status topay_comm_destroy(topay_ctx* c) {
 topay_status topay_scenario_records(topay_ctx* c, const int* scenario_of, int cap_records, topay_record_t* records, int* n_records,
                                     int* winner_index /* cap_records, may be null: batch index of each winner or -1 */) {
   if (!c || !c->have_traj) return TOPAY_ERR_NO_TRAJ;
-  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }   // (waits like the other getters)
+  if (topay_status ws = wait_pending(c)) return ws;   // (waits like the other getters)
   if (!c->solved) return TOPAY_ERR_NO_TRAJ;
   if (!scenario_of || !records || !n_records || cap_records < 0) return TOPAY_ERR_INVALID_ARG;
   const int B = c->B;

@@ -25,21 +25,6 @@ static topay_status ee_params_ok(const topay_ee_params_t& p) {
   return TOPAY_OK;
 }
 
-// map_ids (null: slot 0) name slots with a 3-D field (and a 2-D one when `need2d`)
-static topay_status ee_maps_ok(topay_ctx* c, int n, const int* map_ids, bool need2d, const char* who) {
-  const int one = 0;
-  const int cnt = map_ids ? n : 1;
-  for (int k = 0; k < cnt; k++) {
-    const int m = map_ids ? map_ids[k] : one;
-    if (m < 0 || m >= TOPAY_MAX_MAPS) { set_err(std::string(who) + ": map slot out of range"); return TOPAY_ERR_INVALID_ARG; }
-    if (!c->have_map[m] || !c->hmaps[m].esdf3d || (need2d && !c->hmaps[m].esdf2d)) {
-      set_err(std::string(who) + ": map slot " + std::to_string(m) + " has no fields");
-      return TOPAY_ERR_NO_MAP;
-    }
-  }
-  return TOPAY_OK;
-}
-
 extern "C" {
 
 void topay_ee_default_params(topay_ee_params_t* p) {
@@ -61,7 +46,7 @@ topay_status topay_ee_pose(topay_ctx* c, int n, const double* states, double* po
   const size_t N = (size_t)n;
   double *d_st, *d_po;
   topay_status s;
-  if ((s = c->ee_io.carve([&](Carver& k) { d_st = k.take<double>(10 * N); d_po = k.take<double>(9 * N); })) != TOPAY_OK) return s;
+  if ((s = c->ee.io.carve([&](Carver& k) { d_st = k.take<double>(10 * N); d_po = k.take<double>(9 * N); })) != TOPAY_OK) return s;
   HIPCHK(h2d(c, d_st, states, 10 * N));
   if ((s = push_params(c)) != TOPAY_OK) return s;
   hipLaunchKernelGGL(topay::k_ee_pose, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, n, (const double*)d_st, d_po);
@@ -74,14 +59,14 @@ topay_status topay_ee_pose(topay_ctx* c, int n, const double* states, double* po
 topay_status topay_ee_eval(topay_ctx* c, int n, const int* map_ids, const double* x, const double* ee_ref, double* f, double* g) {
   if (!c || n <= 0 || !x || !ee_ref || !f || !g) return TOPAY_ERR_INVALID_ARG;
   topay_status s;
-  if ((s = ee_maps_ok(c, n, map_ids, false, "topay_ee_eval")) != TOPAY_OK) return s;
+  if ((s = check_map_slots(c, n, map_ids, kMapResident | kMap3d, "topay_ee_eval")) != TOPAY_OK) return s;
   HIPCHK(hipSetDevice(c->device));
   topay_ee_params_t prm;
   topay_ee_default_params(&prm);
   const size_t N = (size_t)n;
   double *d_x, *d_ref, *d_f, *d_g; int* d_mid;
   auto lay = [&](Carver& k) { d_x = k.take<double>(10 * N); d_ref = k.take<double>(9 * N); d_f = k.take<double>(N); d_g = k.take<double>(10 * N); d_mid = k.take<int>(N); };
-  if ((s = c->ee_io.carve(lay)) != TOPAY_OK) return s;
+  if ((s = c->ee.io.carve(lay)) != TOPAY_OK) return s;
   HIPCHK(h2d(c, d_x, x, 10 * N));
   HIPCHK(h2d(c, d_ref, ee_ref, 9 * N));
   if (map_ids) HIPCHK(h2d(c, d_mid, map_ids, N));
@@ -102,7 +87,7 @@ topay_status topay_ee_goals(topay_ctx* c, int n, const int* map_ids, const doubl
   if (params) prm = *params; else topay_ee_default_params(&prm);
   topay_status s;
   if ((s = ee_params_ok(prm)) != TOPAY_OK) return s;
-  if ((s = ee_maps_ok(c, n, map_ids, false, "topay_ee_goals")) != TOPAY_OK) return s;
+  if ((s = check_map_slots(c, n, map_ids, kMapResident | kMap3d, "topay_ee_goals")) != TOPAY_OK) return s;
   for (int k = 0; k < n; k++)
     for (int q = 0; q < 7; q++) {
       const double v = seed_states[10 * (size_t)k + 3 + q];
@@ -112,48 +97,41 @@ topay_status topay_ee_goals(topay_ctx* c, int n, const int* map_ids, const doubl
       }
     }
   HIPCHK(hipSetDevice(c->device));
-  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }
+  if (topay_status ws = wait_pending(c)) return ws;
   const size_t N = (size_t)n, waves = (N + 63) / 64;
   // the history of this call, sized from n and mem_size, kept until the next call
-  if ((s = c->ee_hist.ensure(waves * (size_t)prm.lbfgs.mem_size * topay::kEeHistRows * 64 * sizeof(double))) != TOPAY_OK) return s;
+  if ((s = c->ee.hist.ensure(waves * (size_t)prm.lbfgs.mem_size * topay::kEeHistRows * 64 * sizeof(double))) != TOPAY_OK) return s;
   double *d_seed, *d_ref, *d_st, *d_cost; int *d_mid, *d_code, *d_it, *d_ev;
   auto lay = [&](Carver& k) {
     d_seed = k.take<double>(10 * N); d_ref = k.take<double>(9 * N); d_st = k.take<double>(10 * N); d_cost = k.take<double>(N);
     d_mid = k.take<int>(N); d_code = k.take<int>(N); d_it = k.take<int>(N); d_ev = k.take<int>(N);
   };
-  if ((s = c->ee_io.carve(lay)) != TOPAY_OK) return s;
+  if ((s = c->ee.io.carve(lay)) != TOPAY_OK) return s;
   HIPCHK(h2d(c, d_seed, seed_states, 10 * N));
   HIPCHK(h2d(c, d_ref, ee_ref, 9 * N));
   if (map_ids) HIPCHK(h2d(c, d_mid, map_ids, N));
   if ((s = push_params(c)) != TOPAY_OK) return s;
   topay::EeGoalArgs A;
   A.n = n; A.map_ids = map_ids ? d_mid : nullptr; A.seed = d_seed; A.ee_ref = d_ref; A.W = ee_weights(prm);
-  {
-    const topay_lbfgs_params_t& a = prm.lbfgs;
-    DevLbfgs& b = A.L;
-    b.mem_size = a.mem_size; b.past = a.past; b.max_iterations = a.max_iterations; b.max_linesearch = a.max_linesearch;
-    b.g_epsilon = a.g_epsilon; b.delta = a.delta; b.min_step = a.min_step; b.max_step = a.max_step; b.f_dec_coeff = a.f_dec_coeff;
-    b.s_curv_coeff = a.s_curv_coeff; b.cautious_factor = a.cautious_factor; b.machine_prec = a.machine_prec;
-  }
-  A.hist = c->ee_hist.as<double>(); A.states = d_st; A.cost = d_cost; A.code = d_code; A.iters = d_it; A.evals = d_ev;
-  HIPCHK(hipEventRecord(c->ev0, c->stream));
+  A.L = to_dev_lbfgs(prm.lbfgs);
+  A.hist = c->ee.hist.as<double>(); A.states = d_st; A.cost = d_cost; A.code = d_code; A.iters = d_it; A.evals = d_ev;
+  HIPCHK(c->ee.timer.start(c->stream));
   hipLaunchKernelGGL(topay::k_ee_goals, dim3((unsigned)waves), dim3(64), 0, c->stream, A, (const DevMap*)c->dmaps.p);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev1, c->stream));
+  HIPCHK(c->ee.timer.stop(c->stream));
   HIPCHK(d2h(c, states, d_st, 10 * N));
   if (cost) HIPCHK(d2h(c, cost, d_cost, N));
   if (code) HIPCHK(d2h(c, code, d_code, N));
   if (iters) HIPCHK(d2h(c, iters, d_it, N));
   if (evals) HIPCHK(d2h(c, evals, d_ev, N));
   HIPCHK(hipStreamSynchronize(c->stream));
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->ee_ms = ms;
+  (void)c->ee.timer.read(&c->ee.ms);
   return TOPAY_OK;
 }
 
 topay_status topay_ee_ms(topay_ctx* c, double* ms) {
   if (!c || !ms) return TOPAY_ERR_INVALID_ARG;
-  *ms = c->ee_ms;
+  *ms = c->ee.ms;
   return TOPAY_OK;
 }
 
@@ -165,7 +143,7 @@ topay_status topay_ee_select(topay_ctx* c, int n, const int* map_ids, const int*
   topay_status s;
   if ((s = ee_params_ok(prm)) != TOPAY_OK) return s;
   const bool cf = prm.require_collision_free != 0;
-  if (cf && (s = ee_maps_ok(c, n, map_ids, true, "topay_ee_select")) != TOPAY_OK) return s;
+  if (cf && (s = check_map_slots(c, n, map_ids, kMapResident | kMap2d | kMap3d, "topay_ee_select")) != TOPAY_OK) return s;
   HIPCHK(hipSetDevice(c->device));
   const size_t N = (size_t)n, G = (size_t)n_groups;
   double *d_st, *d_cost, *d_ref, *d_goal; int *d_mid, *d_grp, *d_code, *d_q, *d_win;
@@ -173,7 +151,7 @@ topay_status topay_ee_select(topay_ctx* c, int n, const int* map_ids, const int*
     d_st = k.take<double>(10 * N); d_cost = k.take<double>(N); d_ref = k.take<double>(9 * N); d_goal = k.take<double>(10 * G);
     d_mid = k.take<int>(N); d_grp = k.take<int>(N); d_code = k.take<int>(N); d_q = k.take<int>(N); d_win = k.take<int>(G);
   };
-  if ((s = c->ee_io.carve(lay)) != TOPAY_OK) return s;
+  if ((s = c->ee.io.carve(lay)) != TOPAY_OK) return s;
   HIPCHK(h2d(c, d_st, states, 10 * N));
   HIPCHK(h2d(c, d_cost, cost, N));
   HIPCHK(h2d(c, d_ref, ee_ref, 9 * N));

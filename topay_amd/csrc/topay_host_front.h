@@ -16,17 +16,15 @@ static topay_status dense_launch(topay_ctx* c, int n_paths, const double* d_raw,
 struct JpsDev { int* len; double* out; int* stats; };
 
 // plan2dJPS for n host-side (start, goal) pairs; the results stay on the device in `io` (the public entry copies them
-// back, topay_plan_calls hands them on).  out_ext: write the paths there (n x cap_points x 2) instead of into `io`.
+// back, topay_plan_calls hands them on).  out_ext: write the paths there (n x cap_points x 2) instead of into `io`.  tm (optional):
+// started and stopped around the kernels alone.
 static topay_status jps_impl(topay_ctx* c, int n, const int* map_ids, const double* start_xy, const double* end_xy, double threshold, int cap_points,
-                             DevBuf& io, double* out_ext, JpsDev* dev, hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr) {
+                             DevBuf& io, double* out_ext, JpsDev* dev, const char* who, DevTimer* tm = nullptr) {
+  if (topay_status cs = check_map_slots(c, n, map_ids, kMapResident, who)) return cs;
   std::vector<int> mid((size_t)n, 0);
+  if (map_ids) mid.assign(map_ids, map_ids + n);
   long long ncell = 0;
-  for (int p = 0; p < n; p++) {
-    mid[p] = map_ids ? map_ids[p] : 0;
-    if (mid[p] < 0 || mid[p] >= TOPAY_MAX_MAPS) return TOPAY_ERR_INVALID_ARG;
-    if (!c->have_map[mid[p]]) return TOPAY_ERR_NO_MAP;
-    ncell = std::max(ncell, (long long)c->hmaps[mid[p]].dims[0] * c->hmaps[mid[p]].dims[1]);
-  }
+  for (int m : mid) ncell = std::max(ncell, (long long)c->hmaps[m].dims[0] * c->hmaps[m].dims[1]);
   HIPCHK(hipSetDevice(c->device));
   // search state per instance: g (8) + parent, heap position, heap (3 x 4) + flags (1) bytes per cell; searches run in
   // chunks of at most 2 GB of it
@@ -52,7 +50,7 @@ static topay_status jps_impl(topay_ctx* c, int n, const int* map_ids, const doub
   HIPCHK(h2d(c, d_mid, mid.data(), N));
   B.cap = cap_points; B.ncell_max = ncell; B.map_id = d_mid; B.start = d_start; B.end = d_end; B.threshold = threshold;
   B.out_len = d_len; B.out_xy = d_out; B.stats = d_stats;
-  if (ev_begin) HIPCHK(hipEventRecord(ev_begin, c->stream));
+  if (tm) HIPCHK(tm->start(c->stream));
   for (int i0 = 0; i0 < n; i0 += chunk) {
     B.inst0 = i0;
     B.n = std::min(chunk, n - i0);
@@ -60,7 +58,7 @@ static topay_status jps_impl(topay_ctx* c, int n, const int* map_ids, const doub
     hipLaunchKernelGGL(topay::k_jps, dim3((unsigned)B.n), dim3(64), 0, c->stream, (const DevMap*)c->dmaps.p, B);   // one wave per search
     HIPCHK(hipGetLastError());
   }
-  if (ev_end) HIPCHK(hipEventRecord(ev_end, c->stream));
+  if (tm) HIPCHK(tm->stop(c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));   // (the search state is released on the way out)
   dev->len = d_len; dev->out = d_out; dev->stats = d_stats;
   return TOPAY_OK;
@@ -72,7 +70,7 @@ static topay_status jps_impl(topay_ctx* c, int n, const int* map_ids, const doub
 // forms it again from the map's dimensions); the buffers of a call are strided by the largest.  harness/topo_prm.hpp: topo_pt_cap.
 static int topo_pt_cap(int nx, int ny) { return 2 * (int)std::ceil(std::sqrt((double)nx * nx + (double)ny * ny)) + 512; }
 
-// Layout of the integer scratch of a topay_topo_paths call (topay_ctx::tp_i), in ints from its start: per node type,
+// Layout of the integer scratch of a topay_topo_paths call (FrontState::tp_i), in ints from its start: per node type,
 // neighbour count, guard list, neighbour ids; per query raw-path lengths, kept raw paths, point-buffer lengths, meta.
 struct TopoLayout {
   size_t type, nnb, guards, nb, raw_len, keep, pts_len, meta, total;
@@ -91,10 +89,11 @@ struct TopoDev { int* n_paths; int* path_len; double* path_xy; int* stats; };
 
 // findTopoPaths for n host-side queries; the results stay on the device (in the context's tp_io, or the paths at out_ext:
 // n x cap_paths x cap_points x 2).  inst (optional, host): the instance number of every query instead of first_instance +
-// query.  The public entry copies the results back and clears the unwritten part of the paths first (clear_out).
+// query.  The public entry copies the results back and clears the unwritten part of the paths first (clear_out).  tm: started and
+// stopped around the kernel alone (null: the roadmap's own stopwatch).
 static topay_status topo_impl(topay_ctx* c, int n, const int* map_ids, const double* start_xy, const double* end_xy, const int* critical,
                               const topay_topo_params_t* prm, unsigned long long first_instance, const unsigned long long* inst, int cap_paths,
-                              int cap_points, double* out_ext, bool clear_out, TopoDev* dev, hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr) {
+                              int cap_points, double* out_ext, bool clear_out, TopoDev* dev, DevTimer* tm = nullptr) {
   if (!c || n <= 0 || !start_xy || !end_xy || cap_points < 2) return TOPAY_ERR_INVALID_ARG;
   topay_topo_params_t P;
   if (prm) P = *prm;
@@ -105,28 +104,19 @@ static topay_status topo_impl(topay_ctx* c, int n, const int* map_ids, const dou
     return TOPAY_ERR_INVALID_ARG;
   }
   if (cap_paths < P.reserve_num) { set_err("topay_topo_paths: cap_paths is smaller than reserve_num"); return TOPAY_ERR_INVALID_ARG; }
+  if (topay_status cs = check_map_slots(c, n, map_ids, kMapResident | kMapFront, "topay_topo_paths")) return cs;
   std::vector<int> mid((size_t)n, 0);
+  if (map_ids) mid.assign(map_ids, map_ids + n);
   int pt_cap = 0;
-  for (int p = 0; p < n; p++) {
-    mid[p] = map_ids ? map_ids[p] : 0;
-    if (mid[p] < 0 || mid[p] >= TOPAY_MAX_MAPS) return TOPAY_ERR_INVALID_ARG;
-    if (!c->have_map[mid[p]]) { set_err("map slot not set"); return TOPAY_ERR_NO_MAP; }
-    const DevMap& m = c->hmaps[mid[p]];
-    if (!m.esdf2d_inflate || !m.esdf2d_critical) {
-      set_err("topay_topo_paths: map slot " + std::to_string(mid[p]) + " has no front-end fields (esdf_buffer_2d_inflate / _critical): fill it with "
-              "topay_build_esdf_fields (or topay_build_esdf / _batch), not topay_set_map");
-      return TOPAY_ERR_NO_MAP;
-    }
-    pt_cap = std::max(pt_cap, topo_pt_cap(m.dims[0], m.dims[1]));
-  }
+  for (int m : mid) pt_cap = std::max(pt_cap, topo_pt_cap(c->hmaps[m].dims[0], c->hmaps[m].dims[1]));
   HIPCHK(hipSetDevice(c->device));
   const size_t N = (size_t)n, nn = N * P.node_cap;
   const int nbuf = 2 * P.max_raw_path2 + 2 * P.reserve_num;
   topay_status s;
   const TopoLayout lay(N, P, nbuf);
-  if ((s = c->tp_i.ensure(lay.total * 4)) != TOPAY_OK || (s = c->tp_d.ensure(nn * 2 * 8)) != TOPAY_OK ||
-      (s = c->tp_raw.ensure(N * P.max_raw_path * TOPAY_TOPO_RAWLEN * 2)) != TOPAY_OK ||
-      (s = c->tp_pts.ensure(N * (size_t)nbuf * (size_t)pt_cap * 16)) != TOPAY_OK)
+  if ((s = c->front.tp_i.ensure(lay.total * 4)) != TOPAY_OK || (s = c->front.tp_d.ensure(nn * 2 * 8)) != TOPAY_OK ||
+      (s = c->front.tp_raw.ensure(N * P.max_raw_path * TOPAY_TOPO_RAWLEN * 2)) != TOPAY_OK ||
+      (s = c->front.tp_pts.ensure(N * (size_t)nbuf * (size_t)pt_cap * 16)) != TOPAY_OK)
     return s;
   const size_t out_pts = N * (size_t)cap_paths * cap_points;
   double *d_start, *d_end, *d_own; unsigned long long* d_inst; int *d_mid, *d_crit, *d_np, *d_len, *d_stats;
@@ -135,7 +125,7 @@ static topay_status topo_impl(topay_ctx* c, int n, const int* map_ids, const dou
     d_own = k.take<double>(out_ext ? 0 : 2 * out_pts);
     d_mid = k.take<int>(N); d_crit = k.take<int>(N); d_np = k.take<int>(N); d_len = k.take<int>(N * cap_paths); d_stats = k.take<int>(8 * N);
   };
-  if ((s = c->tp_io.carve(lay_io)) != TOPAY_OK) return s;
+  if ((s = c->front.tp_io.carve(lay_io)) != TOPAY_OK) return s;
   double* d_out = out_ext ? out_ext : d_own;
   HIPCHK(h2d(c, d_start, start_xy, 2 * N));
   HIPCHK(h2d(c, d_end, end_xy, 2 * N));
@@ -150,20 +140,21 @@ static topay_status topo_impl(topay_ctx* c, int n, const int* map_ids, const dou
   B.P.sample_inflate_x = P.sample_inflate_x; B.P.sample_inflate_y = P.sample_inflate_y; B.P.clearance = P.clearance;
   B.P.ratio_to_short = P.ratio_to_short; B.P.max_sample_num = P.max_sample_num; B.P.max_raw_path = P.max_raw_path;
   B.P.max_raw_path2 = P.max_raw_path2; B.P.reserve_num = P.reserve_num; B.P.node_cap = P.node_cap; B.P.reserved = 0; B.P.seed = P.seed;
-  int* ti = c->tp_i.as<int>();
+  int* ti = c->front.tp_i.as<int>();
   B.nd_type = ti + lay.type; B.nd_nnb = ti + lay.nnb; B.guards = ti + lay.guards; B.nd_nb = ti + lay.nb;
   B.raw_len = ti + lay.raw_len; B.keep = ti + lay.keep; B.pts_len = ti + lay.pts_len; B.meta = ti + lay.meta;
-  B.nd_pos = c->tp_d.as<double>();
-  B.raw = c->tp_raw.as<unsigned short>();
-  B.pts = c->tp_pts.as<double>();
+  B.nd_pos = c->front.tp_d.as<double>();
+  B.raw = c->front.tp_raw.as<unsigned short>();
+  B.pts = c->front.tp_pts.as<double>();
   B.n_paths = d_np; B.path_len = d_len; B.path_xy = d_out; B.stats = d_stats;
-  c->tp_n = 0;
-  HIPCHK(hipEventRecord(ev_begin ? ev_begin : c->ev0, c->stream));
+  c->front.tp_n = 0;
+  if (!tm) tm = &c->front.tp_timer;
+  HIPCHK(tm->start(c->stream));
   hipLaunchKernelGGL(topay::k_topo, dim3((unsigned)n), dim3(64), 0, c->stream, (const DevMap*)c->dmaps.p, B);   // one wave per query
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(ev_end ? ev_end : c->ev1, c->stream));
+  HIPCHK(tm->stop(c->stream));
   dev->n_paths = d_np; dev->path_len = d_len; dev->path_xy = d_out; dev->stats = d_stats;
-  c->tp_n = n; c->tp_pt_cap = pt_cap; c->tp_nbuf = nbuf; c->tp_P = P;   // (valid once the stream has been waited for)
+  c->front.tp_n = n; c->front.tp_pt_cap = pt_cap; c->front.tp_nbuf = nbuf; c->front.tp_P = P;   // (valid once the stream has been waited for)
   return TOPAY_OK;
 }
 
@@ -178,8 +169,8 @@ struct McIo {
 static topay_status mcrrt_launch(topay_ctx* c, int n, const topay_mcrrt_params_t& P, unsigned long long first_instance, int cap_per_path, const McIo& io) {
   const size_t nn = (size_t)n * P.node_cap;
   topay_status s;
-  if ((s = c->mc_i.ensure(nn * 5 * 4)) != TOPAY_OK || (s = c->mc_d.ensure(nn * 8 * 8)) != TOPAY_OK ||
-      (s = c->mc_k.ensure(nn * TOPAY_MC_KEYW * 8)) != TOPAY_OK || (s = c->mc_rs.ensure((size_t)n * 2 * cap_per_path * sizeof(topay::RsPath))) != TOPAY_OK)
+  if ((s = c->front.mc_i.ensure(nn * 5 * 4)) != TOPAY_OK || (s = c->front.mc_d.ensure(nn * 8 * 8)) != TOPAY_OK ||
+      (s = c->front.mc_k.ensure(nn * TOPAY_MC_KEYW * 8)) != TOPAY_OK || (s = c->front.mc_rs.ensure((size_t)n * 2 * cap_per_path * sizeof(topay::RsPath))) != TOPAY_OK)
     return s;
   HIPCHK(hipMemsetAsync(io.wb, 0, (size_t)n * cap_per_path * 10 * 8, c->stream));
   HIPCHK(hipMemsetAsync(io.cmax, 0, (size_t)n * 8, c->stream));
@@ -190,16 +181,16 @@ static topay_status mcrrt_launch(topay_ctx* c, int n, const topay_mcrrt_params_t
   B.map_id = io.mid; B.car_off = io.off; B.car_len = io.len; B.car = io.car; B.start = io.start; B.end = io.end;
   B.P.goal_sample_rate = P.goal_sample_rate; B.P.check_colli_res = P.check_colli_res; B.P.rs_rho = P.rs_turning_radius;
   B.P.max_iter = P.max_iter; B.P.max_sample_tries = P.max_sample_tries; B.P.node_cap = P.node_cap; B.P.reserved = 0; B.P.seed = P.seed;
-  int* ni = c->mc_i.as<int>();
+  int* ni = c->front.mc_i.as<int>();
   B.nd_layer = ni; B.nd_state = ni + nn; B.nd_parent = ni + 2 * nn; B.nd_nchild = ni + 3 * nn; B.nd_mark = ni + 4 * nn;
-  B.nd_cost = c->mc_d.as<double>(); B.nd_q = B.nd_cost + nn; B.nd_key = c->mc_k.as<unsigned long long>();
-  B.rs = (topay::RsPath*)c->mc_rs.p;
+  B.nd_cost = c->front.mc_d.as<double>(); B.nd_q = B.nd_cost + nn; B.nd_key = c->front.mc_k.as<unsigned long long>();
+  B.rs = (topay::RsPath*)c->front.mc_rs.p;
   B.wb_len = io.wb_len; B.wb = io.wb; B.stats = io.stats; B.cmax = io.cmax;
-  c->mc_n = 0;
+  c->front.mc_n = 0;
   hipLaunchKernelGGL(topay::k_mcrrt, dim3((unsigned)n), dim3(64), 0, c->stream, (const DevMap*)c->dmaps.p, B);
   HIPCHK(hipGetLastError());
-  c->mc_n = n;
-  c->mc_node_cap = P.node_cap;
+  c->front.mc_n = n;
+  c->front.mc_node_cap = P.node_cap;
   return TOPAY_OK;
 }
 
@@ -212,8 +203,8 @@ extern "C" {
 // GridMap::isWholeBodyCollision (grid_map.h:613-650) of n states (x, y, theta, q1..q7) against map slot map_id:
 // collide[i] = 1 when the state violates a joint limit, leaves the map or collides (front-end building block).
 topay_status topay_whole_body_collision(topay_ctx* c, int map_id, int n, const double* states, int* collide) {
-  if (!c || !states || !collide || n < 0 || map_id < 0 || map_id >= TOPAY_MAX_MAPS) return TOPAY_ERR_INVALID_ARG;
-  if (!c->have_map[map_id]) return TOPAY_ERR_NO_MAP;
+  if (!c || !states || !collide || n < 0) return TOPAY_ERR_INVALID_ARG;
+  if (topay_status cs = check_map_slots(c, 1, &map_id, kMapResident, "topay_whole_body_collision")) return cs;
   if (n == 0) return TOPAY_OK;
   HIPCHK(hipSetDevice(c->device));
   topay_status s;
@@ -279,9 +270,8 @@ topay_status topay_connect_check_num(int n_edges, const double* rs_distance, con
 // ... and the checks themselves (lines 330-345), every interpolated state of every edge in one launch.
 topay_status topay_connect_collision(topay_ctx* c, int map_id, int n_edges, const int* piece_num, const double* car_poses, const double* q_from,
                                      const double* q_to, int* collide) {
-  if (!c || n_edges < 0 || map_id < 0 || map_id >= TOPAY_MAX_MAPS || (n_edges > 0 && (!piece_num || !car_poses || !q_from || !q_to || !collide)))
-    return TOPAY_ERR_INVALID_ARG;
-  if (!c->have_map[map_id]) return TOPAY_ERR_NO_MAP;
+  if (!c || n_edges < 0 || (n_edges > 0 && (!piece_num || !car_poses || !q_from || !q_to || !collide))) return TOPAY_ERR_INVALID_ARG;
+  if (topay_status cs = check_map_slots(c, 1, &map_id, kMapResident, "topay_connect_collision")) return cs;
   if (n_edges == 0) return TOPAY_OK;
   HIPCHK(hipSetDevice(c->device));
   std::vector<int> edge_of, idx;
@@ -320,7 +310,7 @@ topay_status topay_plan2d_jps(topay_ctx* c, int n, const int* map_ids, const dou
   if (n == 0) return TOPAY_OK;
   DevBuf io;
   JpsDev d;
-  topay_status s = jps_impl(c, n, map_ids, start_xy, end_xy, threshold, cap_points, io, nullptr, &d);
+  topay_status s = jps_impl(c, n, map_ids, start_xy, end_xy, threshold, cap_points, io, nullptr, &d, "topay_plan2d_jps");
   if (s != TOPAY_OK) return s;
   HIPCHK(d2h(c, out_len, d.len, (size_t)n));
   HIPCHK(d2h(c, out_xy, d.out, (size_t)n * cap_points * 2));
@@ -352,29 +342,27 @@ topay_status topay_topo_paths(topay_ctx* c, int n, const int* map_ids, const dou
   const size_t N = (size_t)n;
   topay_status s = topo_impl(c, n, map_ids, start_xy, end_xy, critical, prm, first_instance, nullptr, cap_paths, cap_points, nullptr, true, &d);
   if (s != TOPAY_OK) return s;
-  const int keep_n = c->tp_n;
-  c->tp_n = 0;   // (the graphs are readable once the results have arrived)
+  const int keep_n = c->front.tp_n;
+  c->front.tp_n = 0;   // (the graphs are readable once the results have arrived)
   HIPCHK(d2h(c, n_paths, d.n_paths, N));
   HIPCHK(d2h(c, path_len, d.path_len, N * cap_paths));
   HIPCHK(d2h(c, path_xy, d.path_xy, N * (size_t)cap_paths * cap_points * 2));
   if (stats) HIPCHK(d2h(c, stats, d.stats, N * 8));
   HIPCHK(hipStreamSynchronize(c->stream));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  c->last_ms = ms;
+  HIPCHK(c->front.tp_timer.read(&c->last_ms));
   c->last_launches = 1;
-  c->tp_n = keep_n;
+  c->front.tp_n = keep_n;
   return TOPAY_OK;
 }
 
 topay_status topay_topo_graph(topay_ctx* c, int instance, int cap, int* id, int* type, double* pos_xy, int* n_neighbors, int* neighbors,
                               int* n_nodes) {
-  if (!c || instance < 0 || instance >= c->tp_n || cap < 0) return TOPAY_ERR_INVALID_ARG;
+  if (!c || instance < 0 || instance >= c->front.tp_n || cap < 0) return TOPAY_ERR_INVALID_ARG;
   HIPCHK(hipSetDevice(c->device));
-  const topay_topo_params_t& P = c->tp_P;
-  const size_t N = (size_t)c->tp_n, o = (size_t)instance * P.node_cap;
-  const TopoLayout lay(N, P, c->tp_nbuf);
-  const int* ti = c->tp_i.as<int>();
+  const topay_topo_params_t& P = c->front.tp_P;
+  const size_t N = (size_t)c->front.tp_n, o = (size_t)instance * P.node_cap;
+  const TopoLayout lay(N, P, c->front.tp_nbuf);
+  const int* ti = c->front.tp_i.as<int>();
   const int* d_meta = ti + lay.meta + 8 * (size_t)instance;
   int meta[8];
   HIPCHK(memcpy_sync(c, meta, d_meta, sizeof(meta), hipMemcpyDeviceToHost));
@@ -385,7 +373,7 @@ topay_status topay_topo_graph(topay_ctx* c, int instance, int cap, int* id, int*
     HIPCHK(d2h_sync(c, t.data(), ti + lay.type + o, (size_t)created));
     HIPCHK(d2h_sync(c, k.data(), ti + lay.nnb + o, (size_t)created));
     HIPCHK(d2h_sync(c, nb.data(), ti + lay.nb + o * TOPAY_TOPO_MAX_NB, (size_t)created * TOPAY_TOPO_MAX_NB));
-    HIPCHK(d2h_sync(c, pos.data(), c->tp_d.as<double>() + 2 * o, (size_t)created * 2));
+    HIPCHK(d2h_sync(c, pos.data(), c->front.tp_d.as<double>() + 2 * o, (size_t)created * 2));
   }
   int m = 0;
   for (int i = 0; i < created; i++) {
@@ -406,13 +394,13 @@ topay_status topay_topo_graph(topay_ctx* c, int instance, int cap, int* id, int*
 
 topay_status topay_topo_raw_paths(topay_ctx* c, int instance, int which, int cap_paths, int cap_points, int* n_paths, int* path_len,
                                   double* path_xy) {
-  if (!c || instance < 0 || instance >= c->tp_n || which < 0 || which > 1 || cap_paths < 0 || cap_points < 0 || !n_paths || !path_len || !path_xy)
+  if (!c || instance < 0 || instance >= c->front.tp_n || which < 0 || which > 1 || cap_paths < 0 || cap_points < 0 || !n_paths || !path_len || !path_xy)
     return TOPAY_ERR_INVALID_ARG;
   HIPCHK(hipSetDevice(c->device));
-  const topay_topo_params_t& P = c->tp_P;
-  const size_t N = (size_t)c->tp_n, q = (size_t)instance;
-  const TopoLayout lay(N, P, c->tp_nbuf);
-  const int* ti = c->tp_i.as<int>();
+  const topay_topo_params_t& P = c->front.tp_P;
+  const size_t N = (size_t)c->front.tp_n, q = (size_t)instance;
+  const TopoLayout lay(N, P, c->front.tp_nbuf);
+  const int* ti = c->front.tp_i.as<int>();
   const int* d_rawlen = ti + lay.raw_len;
   const int* d_keep = ti + lay.keep;
   const int* d_ptslen = ti + lay.pts_len;
@@ -427,13 +415,13 @@ topay_status topay_topo_raw_paths(topay_ctx* c, int instance, int which, int cap
   if (which == 0) {
     const int created = std::min(std::max(meta[0], 0), P.node_cap);
     std::vector<double> pos((size_t)created * 2);
-    HIPCHK(d2h_sync(c, pos.data(), c->tp_d.as<double>() + 2 * q * P.node_cap, (size_t)created * 2));
+    HIPCHK(d2h_sync(c, pos.data(), c->front.tp_d.as<double>() + 2 * q * P.node_cap, (size_t)created * 2));
     std::vector<int> rl((size_t)P.max_raw_path);
     HIPCHK(d2h_sync(c, rl.data(), d_rawlen + q * P.max_raw_path, rl.size()));
     std::vector<unsigned short> ids(TOPAY_TOPO_RAWLEN);
     for (int k = 0; k < n_keep && k < cap_paths; k++) {
       const int r = keep[k], len = std::min(std::max(rl[r], 0), TOPAY_TOPO_RAWLEN);
-      HIPCHK(d2h_sync(c, ids.data(), c->tp_raw.as<unsigned short>() + (q * P.max_raw_path + r) * TOPAY_TOPO_RAWLEN, (size_t)len));
+      HIPCHK(d2h_sync(c, ids.data(), c->front.tp_raw.as<unsigned short>() + (q * P.max_raw_path + r) * TOPAY_TOPO_RAWLEN, (size_t)len));
       path_len[k] = len;
       for (int j = 0; j < len && j < cap_points; j++) {
         const int nd = std::min((int)ids[j], created - 1);
@@ -443,13 +431,13 @@ topay_status topay_topo_raw_paths(topay_ctx* c, int instance, int which, int cap
     }
   } else {
     std::vector<int> pl((size_t)n_keep);
-    HIPCHK(d2h_sync(c, pl.data(), d_ptslen + q * c->tp_nbuf, (size_t)n_keep));
+    HIPCHK(d2h_sync(c, pl.data(), d_ptslen + q * c->front.tp_nbuf, (size_t)n_keep));
     for (int k = 0; k < n_keep && k < cap_paths; k++) {
-      const int len = std::min(std::max(pl[k], 0), c->tp_pt_cap);
+      const int len = std::min(std::max(pl[k], 0), c->front.tp_pt_cap);
       path_len[k] = len;
       const int w = std::min(len, cap_points);
       if (w > 0)
-        HIPCHK(d2h_sync(c, path_xy + (size_t)k * cap_points * 2, c->tp_pts.as<double>() + (q * c->tp_nbuf + k) * (size_t)c->tp_pt_cap * 2, (size_t)w * 2));
+        HIPCHK(d2h_sync(c, path_xy + (size_t)k * cap_points * 2, c->front.tp_pts.as<double>() + (q * c->front.tp_nbuf + k) * (size_t)c->front.tp_pt_cap * 2, (size_t)w * 2));
     }
   }
   return TOPAY_OK;
@@ -478,6 +466,7 @@ topay_status topay_mcrrt_plan(topay_ctx* c, int n, const int* map_ids, const int
   if (n == 0) return TOPAY_OK;
   std::vector<long long> off((size_t)n + 1, 0);
   std::vector<int> mid((size_t)n, 0);
+  if (map_ids) mid.assign(map_ids, map_ids + n);
   for (int p = 0; p < n; p++) {
     if (path_len[p] < 2 || path_len[p] > cap_per_path || path_len[p] > 255) {
       set_err("topay_mcrrt_plan: chassis path " + std::to_string(p) + " has " + std::to_string(path_len[p]) + " layers (2.." +
@@ -485,10 +474,8 @@ topay_status topay_mcrrt_plan(topay_ctx* c, int n, const int* map_ids, const int
       return TOPAY_ERR_INVALID_ARG;
     }
     off[p + 1] = off[p] + path_len[p];
-    mid[p] = map_ids ? map_ids[p] : 0;
-    if (mid[p] < 0 || mid[p] >= TOPAY_MAX_MAPS) return TOPAY_ERR_INVALID_ARG;
-    if (!c->have_map[mid[p]]) return TOPAY_ERR_NO_MAP;
   }
+  if (topay_status cs = check_map_slots(c, n, map_ids, kMapResident, "topay_mcrrt_plan")) return cs;
   HIPCHK(hipSetDevice(c->device));
   const size_t tot = (size_t)off[n];
   topay_status s;
@@ -500,7 +487,7 @@ topay_status topay_mcrrt_plan(topay_ctx* c, int n, const int* map_ids, const int
     d_wb = k.take<double>(N * cap_per_path * 10); d_cmax = k.take<double>(N);
     d_mid = k.take<int>(N); d_len = k.take<int>(N); d_wlen = k.take<int>(N); d_stats = k.take<int>(8 * N);
   };
-  if ((s = c->mc_in.carve(lay)) != TOPAY_OK) return s;
+  if ((s = c->front.mc_in.carve(lay)) != TOPAY_OK) return s;
   HIPCHK(h2d(c, d_off, off.data(), N + 1));
   HIPCHK(h2d(c, d_car, car_paths, 4 * tot));
   HIPCHK(h2d(c, d_start, start, 10 * N));
@@ -520,12 +507,12 @@ topay_status topay_mcrrt_plan(topay_ctx* c, int n, const int* map_ids, const int
 }
 
 topay_status topay_mcrrt_nodes(topay_ctx* c, int instance, int cap, int* layer, int* state, int* parent, double* cost, double* q) {
-  if (!c || instance < 0 || instance >= c->mc_n || cap < 0) return TOPAY_ERR_INVALID_ARG;
+  if (!c || instance < 0 || instance >= c->front.mc_n || cap < 0) return TOPAY_ERR_INVALID_ARG;
   HIPCHK(hipSetDevice(c->device));
-  const size_t nn = (size_t)c->mc_n * c->mc_node_cap, o = (size_t)instance * c->mc_node_cap;
-  const size_t m = (size_t)std::min(cap, c->mc_node_cap);
-  const int* ni = c->mc_i.as<int>();
-  const double* nd = c->mc_d.as<double>();
+  const size_t nn = (size_t)c->front.mc_n * c->front.mc_node_cap, o = (size_t)instance * c->front.mc_node_cap;
+  const size_t m = (size_t)std::min(cap, c->front.mc_node_cap);
+  const int* ni = c->front.mc_i.as<int>();
+  const double* nd = c->front.mc_d.as<double>();
   if (layer) HIPCHK(d2h_sync(c, layer, ni + o, m));
   if (state) HIPCHK(d2h_sync(c, state, ni + nn + o, m));
   if (parent) HIPCHK(d2h_sync(c, parent, ni + 2 * nn + o, m));

@@ -1,4 +1,5 @@
-// Host side of the C-ABI, part 2: the map slots -- upload, sharing between contexts, ESDF construction on the device.
+// Host side of the C-ABI, part 2: the map slots -- the one check of the slots an entry names, upload, sharing between contexts,
+// ESDF construction on the device.
 
 #pragma once
 
@@ -11,17 +12,56 @@ static topay_status map_dims_check(const topay_map_desc_t* desc) {
   return TOPAY_OK;
 }
 
+// What an entry asks of the map slots it names (check_map_slots).
+enum : unsigned {
+  kMapResident = 1,   // the slot is filled
+  kMap2d = 2,         // ... and has the 2-D field
+  kMap3d = 4,         // ... the 3-D field
+  kMapFront = 8,      // ... the front-end's inflate and critical fields (a slot filled by topay_build_esdf*, not topay_set_map)
+  kMapOnce = 16       // every slot is named once
+};
+// The one check of map slots: map_ids[0 .. n) (null: slot 0).  A slot out of range or named twice is TOPAY_ERR_INVALID_ARG, an
+// empty one or one without a field TOPAY_ERR_NO_MAP; the error text names the entry (`who`) and the slot.
+static topay_status check_map_slots(topay_ctx* c, int n, const int* map_ids, unsigned need, const char* who) {
+  std::vector<char> seen(need & kMapOnce ? TOPAY_MAX_MAPS : 0, 0);
+  for (int k = 0; k < (map_ids ? n : 1); k++) {
+    const int m = map_ids ? map_ids[k] : 0;
+    const std::string slot = std::string(who) + ": map slot " + std::to_string(m);
+    if (m < 0 || m >= TOPAY_MAX_MAPS) { set_err(slot + " out of range"); return TOPAY_ERR_INVALID_ARG; }
+    if (need & kMapOnce) {
+      if (seen[m]) { set_err(slot + " named twice in one call"); return TOPAY_ERR_INVALID_ARG; }
+      seen[m] = 1;
+    }
+    const DevMap& d = c->hmaps[m];
+    const bool fields = ((need & kMap2d) && !d.esdf2d) || ((need & kMap3d) && !d.esdf3d);
+    if (fields || ((need & kMapResident) && !c->have_map[m])) { set_err(slot + (need & (kMap2d | kMap3d) ? " has no fields" : " is not set")); return TOPAY_ERR_NO_MAP; }
+    if ((need & kMapFront) && (!d.esdf2d_inflate || !d.esdf2d_critical)) {
+      set_err(slot + " has no front-end fields (esdf_buffer_2d_inflate / _critical): fill it with topay_build_esdf_fields (or topay_build_esdf / _batch), "
+              "not topay_set_map");
+      return TOPAY_ERR_NO_MAP;
+    }
+  }
+  return TOPAY_OK;
+}
+// ... and of a range of slots that an entry fills or takes over
+static topay_status check_map_range(int first_map_id, int n_maps, const char* who) {
+  if (n_maps > 0 && first_map_id >= 0 && first_map_id + n_maps <= TOPAY_MAX_MAPS) return TOPAY_OK;
+  set_err(std::string(who) + ": map slots [" + std::to_string(first_map_id) + ", " + std::to_string(first_map_id) + " + " + std::to_string(n_maps) + ") out of range");
+  return TOPAY_ERR_INVALID_ARG;
+}
+
 extern "C" {
 
 topay_status topay_set_map(topay_ctx* c, int map_id, const topay_map_desc_t* desc, const double* esdf2d, const double* esdf3d) {
-  if (!c || !desc || !esdf2d || !esdf3d || map_id < 0 || map_id >= TOPAY_MAX_MAPS) return TOPAY_ERR_INVALID_ARG;
+  if (!c || !desc || !esdf2d || !esdf3d) return TOPAY_ERR_INVALID_ARG;
+  if (topay_status s = check_map_slots(c, 1, &map_id, 0, "topay_set_map")) return s;
   HIPCHK(hipSetDevice(c->device));
-  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }   // inputs of a solve in flight stay untouched
+  if (topay_status ws = wait_pending(c)) return ws;   // inputs of a solve in flight stay untouched
   const size_t n2 = (size_t)desc->dims[0] * desc->dims[1], n3 = n2 * desc->dims[2];
   if (topay_status ds = map_dims_check(desc)) return ds;
   invalidate_sharers(c, map_id, 1);
   drop_shared_slots(c, map_id, 1);
-  world_forget(c, map_id, 1);
+  forget_occupancy(c, map_id, 1);
   topay_status s;
   if ((s = c->map2d[map_id].ensure(n2 * 8)) != TOPAY_OK) return s;
   if ((s = c->map3d[map_id].ensure(n3 * 8)) != TOPAY_OK) return s;
@@ -49,15 +89,16 @@ topay_status topay_set_map(topay_ctx* c, int map_id, const topay_map_desc_t* des
 // slots `owner` holds, without a copy of the fields.  The batches in flight of a pipelined planner (one context each)
 // then keep one copy of the maps instead of one per context.
 topay_status topay_share_maps(topay_ctx* c, topay_ctx* owner, int first_map_id, int n_maps) {
-  if (!c || !owner || c == owner || first_map_id < 0 || n_maps <= 0 || first_map_id + n_maps > TOPAY_MAX_MAPS) return TOPAY_ERR_INVALID_ARG;
+  if (!c || !owner || c == owner) return TOPAY_ERR_INVALID_ARG;
+  if (topay_status s = check_map_range(first_map_id, n_maps, "topay_share_maps")) return s;
   if (c->device != owner->device) { set_err("topay_share_maps: the contexts are on different devices"); return TOPAY_ERR_INVALID_ARG; }
   HIPCHK(hipSetDevice(c->device));
-  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }
+  if (topay_status ws = wait_pending(c)) return ws;
   for (int m = first_map_id; m < first_map_id + n_maps; m++)
-    if (!owner->have_map[m]) return TOPAY_ERR_NO_MAP;
+    if (topay_status s = check_map_slots(owner, 1, &m, kMapResident, "topay_share_maps (the owner)")) return s;
   invalidate_sharers(c, first_map_id, n_maps);   // (contexts that shared c's own copies of these slots)
   drop_shared_slots(c, first_map_id, n_maps);
-  world_forget(c, first_map_id, n_maps);
+  forget_occupancy(c, first_map_id, n_maps);
   for (int m = first_map_id; m < first_map_id + n_maps; m++) {
     c->map2d[m].release(); c->map3d[m].release(); c->map2d_inf[m].release(); c->map2d_crit[m].release();   // own copies of these slots, if any
     c->hmaps[m] = owner->hmaps[m];
@@ -95,10 +136,10 @@ static topay_status build_fields_from_device(topay_ctx* c, int n_maps, int first
   invalidate_sharers(c, first_map_id, n_maps);
   drop_shared_slots(c, first_map_id, n_maps);
   topay_status s;
-  if ((s = c->edt_thr.ensure(M * n2)) != TOPAY_OK) return s;
-  signed char* d_occ2t = c->edt_thr.as<signed char>();   // 2-D scratch: the thresholded fields
-  if ((s = c->edt_tmp1.ensure(M * n3 * 8)) != TOPAY_OK) return s;
-  if ((s = c->edt_tmp2.ensure(M * n3 * 8)) != TOPAY_OK) return s;
+  if ((s = c->edt.thr.ensure(M * n2)) != TOPAY_OK) return s;
+  signed char* d_occ2t = c->edt.thr.as<signed char>();   // 2-D scratch: the thresholded fields
+  if ((s = c->edt.tmp1.ensure(M * n3 * 8)) != TOPAY_OK) return s;
+  if ((s = c->edt.tmp2.ensure(M * n3 * 8)) != TOPAY_OK) return s;
   // results: e3 | e2 | e2 inflate | e2 critical in a new arena (they stay there); the plain critical field is scratch
   // (a rebuild of the same range of slots -- a new episode's maps -- takes the arena of the previous build over)
   // arenas of earlier builds whose slots this build overwrites completely are released (a caller that varies the slot
@@ -128,17 +169,17 @@ static topay_status build_fields_from_device(topay_ctx* c, int n_maps, int first
     e3 = k.take<double>(M * n3); e2 = k.take<double>(M * n2); e2i = k.take<double>(M * n2); e2c = k.take<double>(M * n2);
   };
   if ((s = arena.carve(lay_arena)) != TOPAY_OK) return s;
-  if ((s = c->edt_out2.ensure(M * n2 * 8)) != TOPAY_OK) return s;
+  if ((s = c->edt.out2.ensure(M * n2 * 8)) != TOPAY_OK) return s;
   // workspace for the envelope stacks of the pass with the most (lines x cells), per map
   const size_t ws_elems = std::max(std::max((size_t)nx * ny * (nz + 2), (size_t)nx * nz * (ny + 2)), (size_t)ny * nz * (nx + 2));
-  if ((s = c->edt_v.ensure(M * ws_elems * 4)) != TOPAY_OK) return s;
-  if ((s = c->edt_z.ensure(M * ws_elems * 8)) != TOPAY_OK) return s;
-  HIPCHK(hipEventRecord(c->ev0, c->stream));
-  double* t1 = c->edt_tmp1.as<double>();
-  double* t2 = c->edt_tmp2.as<double>();
-  double* e2s = c->edt_out2.as<double>();   // scratch: the plain critical field
-  int* vws = c->edt_v.as<int>();
-  double* zws = c->edt_z.as<double>();
+  if ((s = c->edt.v.ensure(M * ws_elems * 4)) != TOPAY_OK) return s;
+  if ((s = c->edt.z.ensure(M * ws_elems * 8)) != TOPAY_OK) return s;
+  HIPCHK(c->edt.timer.start(c->stream));
+  double* t1 = c->edt.tmp1.as<double>();
+  double* t2 = c->edt.tmp2.as<double>();
+  double* e2s = c->edt.out2.as<double>();   // scratch: the plain critical field
+  int* vws = c->edt.v.as<int>();
+  double* zws = c->edt.z.as<double>();
   const double res = desc->resolution;
   // envelope stacks in LDS when a 64-line block fits ((n + 2) x 64 x (8 + 2) B <= 150 KB, i.e. lines up to ~238 cells)
   // and the launch is small, else in the HBM workspace
@@ -251,7 +292,7 @@ static topay_status build_fields_from_device(topay_ctx* c, int n_maps, int first
   threshold(e2s, d_occ2t);
   if ((s = field2d(d_occ2t, e2c)) != TOPAY_OK) return s;            // critical inflate, stored in esdf_buffer_2d_critical (283-351)
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev1, c->stream));
+  HIPCHK(c->edt.timer.stop(c->stream));
   // the map slots point into the arena; descriptors as topay_set_map
   for (int k = 0; k < n_maps; k++) {
     const int map_id = first_map_id + k;
@@ -272,12 +313,10 @@ static topay_status build_fields_from_device(topay_ctx* c, int n_maps, int first
   HIPCHK(hipMemcpyAsync((char*)c->dmaps.p + sizeof(DevMap) * first_map_id, &c->hmaps[first_map_id], sizeof(DevMap) * n_maps,
                         hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  c->last_edt_ms = ms;
+  HIPCHK(c->edt.timer.read(&c->edt.ms));
   // the construction's workspace (occupancy, two intermediate volumes, the envelope stacks, the staged results: about
   // five times the maps themselves) is not needed once the fields sit in their map slots
-  c->edt_thr.release(); c->edt_tmp1.release(); c->edt_tmp2.release(); c->edt_v.release(); c->edt_z.release(); c->edt_out2.release();
+  c->edt.thr.release(); c->edt.tmp1.release(); c->edt.tmp2.release(); c->edt.v.release(); c->edt.z.release(); c->edt.out2.release();
   return TOPAY_OK;
 }
 
@@ -287,22 +326,22 @@ static topay_status build_fields_from_device(topay_ctx* c, int n_maps, int first
 // launches, blockIdx.y = map: a single 200 x 200 x 16 map has too few lines to fill the device.
 topay_status topay_build_esdf_fields(topay_ctx* c, int n_maps, int first_map_id, const topay_map_desc_t* desc,
                                      const signed char* occ2d, const signed char* occ2d_critical, const signed char* occ3d) {
-  if (!c || !desc || !occ2d || !occ3d || n_maps <= 0 || first_map_id < 0 || first_map_id + n_maps > TOPAY_MAX_MAPS)
-    return TOPAY_ERR_INVALID_ARG;
+  if (!c || !desc || !occ2d || !occ3d) return TOPAY_ERR_INVALID_ARG;
+  if (topay_status rs = check_map_range(first_map_id, n_maps, "topay_build_esdf_fields")) return rs;
   HIPCHK(hipSetDevice(c->device));
-  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }   // inputs of a solve in flight stay untouched
+  if (topay_status ws = wait_pending(c)) return ws;   // inputs of a solve in flight stay untouched
   const size_t n2 = (size_t)desc->dims[0] * desc->dims[1], n3 = n2 * desc->dims[2], M = (size_t)n_maps;
   if (topay_status ds = map_dims_check(desc)) return ds;
-  world_forget(c, first_map_id, n_maps);
+  forget_occupancy(c, first_map_id, n_maps);
   topay_status s;
   signed char *d_occ3, *d_occ2, *d_occ2c;   // 3-D, 2-D, 2-D critical
   auto lay_occ = [&](Carver& k) { d_occ3 = k.take<signed char>(M * n3); d_occ2 = k.take<signed char>(M * n2); d_occ2c = k.take<signed char>(M * n2); };
-  if ((s = c->edt_occ.carve(lay_occ)) != TOPAY_OK) return s;
+  if ((s = c->edt.occ.carve(lay_occ)) != TOPAY_OK) return s;
   HIPCHK(h2d(c, d_occ3, occ3d, M * n3));
   HIPCHK(h2d(c, d_occ2, occ2d, M * n2));
   if (occ2d_critical) HIPCHK(h2d(c, d_occ2c, occ2d_critical, M * n2));
   s = build_fields_from_device(c, n_maps, first_map_id, desc, d_occ3, d_occ2, d_occ2c, occ2d_critical == nullptr);
-  c->edt_occ.release();
+  c->edt.occ.release();
   return s;
 }
 
@@ -318,9 +357,8 @@ topay_status topay_build_esdf(topay_ctx* c, int map_id, const topay_map_desc_t* 
 
 // The two front-end fields of a map built on the device (GridMap::esdf_buffer_2d_inflate, esdf_buffer_2d_critical).
 topay_status topay_get_map_fields(topay_ctx* c, int map_id, double* esdf2d_inflate, double* esdf2d_critical) {
-  if (!c || map_id < 0 || map_id >= TOPAY_MAX_MAPS || !c->have_map[map_id]) return TOPAY_ERR_NO_MAP;
+  if (!c || check_map_slots(c, 1, &map_id, kMapResident | kMapFront, "topay_get_map_fields") != TOPAY_OK) return TOPAY_ERR_NO_MAP;   // (out of range too)
   const DevMap& m = c->hmaps[map_id];
-  if (!m.esdf2d_inflate || !m.esdf2d_critical) { set_err("map slot was not built by topay_build_esdf*"); return TOPAY_ERR_NO_MAP; }
   HIPCHK(hipSetDevice(c->device));
   const size_t n2 = (size_t)m.dims[0] * m.dims[1];
   if (esdf2d_inflate) HIPCHK(d2h_sync(c, esdf2d_inflate, (const double*)m.esdf2d_inflate, n2));
@@ -330,13 +368,13 @@ topay_status topay_get_map_fields(topay_ctx* c, int map_id, double* esdf2d_infla
 
 // Copy a resident map back (tests, or a caller that wants the GPU-built ESDF on the host); milliseconds of the last build.
 topay_status topay_get_map(topay_ctx* c, int map_id, double* esdf2d, double* esdf3d, double* build_ms) {
-  if (!c || map_id < 0 || map_id >= TOPAY_MAX_MAPS || !c->have_map[map_id]) return TOPAY_ERR_NO_MAP;
+  if (!c || check_map_slots(c, 1, &map_id, kMapResident, "topay_get_map") != TOPAY_OK) return TOPAY_ERR_NO_MAP;   // (out of range too)
   HIPCHK(hipSetDevice(c->device));
   const DevMap& m = c->hmaps[map_id];
   const size_t n2 = (size_t)m.dims[0] * m.dims[1], n3 = n2 * m.dims[2];
   if (esdf2d) HIPCHK(d2h_sync(c, esdf2d, (const double*)m.esdf2d, n2));
   if (esdf3d) HIPCHK(d2h_sync(c, esdf3d, (const double*)m.esdf3d, n3));
-  if (build_ms) *build_ms = c->last_edt_ms;
+  if (build_ms) *build_ms = c->edt.ms;
   return TOPAY_OK;
 }
 

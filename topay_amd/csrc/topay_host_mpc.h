@@ -1,6 +1,6 @@
 // Host side of the C-ABI, part 12: the tracking controller and the fake robot (topay_mpc.h; OMPC and moma_sim).  Robot slots are
-// those of topay_host_track.h.  The slots' state lies in two device arrays of TOPAY_TRACK_SLOTS entries, allocated zeroed by the
-// first reset; every argument is checked here, before any launch.
+// those of topay_host_track.h, checked by its check_robot_slots.  The slots' state lies in two device arrays of TOPAY_TRACK_SLOTS
+// entries, allocated zeroed by the first reset (MpcState::alloc); every argument is checked here, before any launch.
 
 #pragma once
 
@@ -27,37 +27,6 @@ static topay_status mpc_check_params(const topay_mpc_params_t& p) {
   return TOPAY_OK;
 }
 
-static topay_status mpc_alloc(topay_ctx* c) {
-  if (c->mpc_slots.p) return TOPAY_OK;
-  topay_status s;
-  if ((s = c->mpc_slots.ensure(sizeof(topay::MpcSlot) * TOPAY_TRACK_SLOTS)) != TOPAY_OK) return s;
-  if ((s = c->mpc_sims.ensure(sizeof(topay::SimSlot) * TOPAY_TRACK_SLOTS)) != TOPAY_OK) return s;
-  HIPCHK(hipMemsetAsync(c->mpc_slots.p, 0, c->mpc_slots.bytes, c->stream));
-  HIPCHK(hipMemsetAsync(c->mpc_sims.p, 0, c->mpc_sims.bytes, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  c->mpc_prm.resize(TOPAY_TRACK_SLOTS);
-  c->mpc_have.assign(TOPAY_TRACK_SLOTS, 0);
-  c->sim_have.assign(TOPAY_TRACK_SLOTS, 0);
-  return TOPAY_OK;
-}
-
-// robots in range, distinct, reset (controller and, when sim, simulator)
-static topay_status mpc_check_robots(topay_ctx* c, int n, const int* robots, bool need_mpc, bool need_sim, const char* who) {
-  for (int k = 0; k < n; k++)
-    if (!track_robot_ok(robots[k])) { set_err(std::string(who) + ": robot slot out of range"); return TOPAY_ERR_INVALID_ARG; }
-  if (!track_robots_distinct(n, robots)) { set_err(std::string(who) + ": a robot slot is named twice"); return TOPAY_ERR_INVALID_ARG; }
-  for (int k = 0; k < n; k++) {
-    if (need_mpc && (c->mpc_have.empty() || !c->mpc_have[robots[k]])) { set_err(std::string(who) + ": robot slot " + std::to_string(robots[k]) + " was never reset (topay_mpc_reset)"); return TOPAY_ERR_INVALID_ARG; }
-    if (need_sim && (c->sim_have.empty() || !c->sim_have[robots[k]])) { set_err(std::string(who) + ": robot slot " + std::to_string(robots[k]) + " has no simulator (topay_sim_reset)"); return TOPAY_ERR_INVALID_ARG; }
-  }
-  return TOPAY_OK;
-}
-static bool mpc_finite(const double* v, size_t n) {   // finite and below 1e9 in magnitude (include/topay.h states the bound)
-  for (size_t i = 0; i < n; i++)
-    if (!(std::fabs(v[i]) < 1.0e9)) return false;
-  return true;
-}
-
 // The launch of k_mpc_cmds: n robots, `periods` periods each.  Outputs may be null.
 static topay_status mpc_launch(topay_ctx* c, int n, const int* robots, const double* t_cur, const double* now_state, int periods, int ticks, bool follow,
                                double* cmd, int* status, double* xopt, double* states_out, const topay::MpcDense* dense) {
@@ -65,10 +34,10 @@ static topay_status mpc_launch(topay_ctx* c, int n, const int* robots, const dou
   std::vector<topay::TrackDesc> desc(N);
   size_t lds = 0;
   for (int k = 0; k < n; k++) {
-    const topay::TrackDesc* d = track_find(c, robots[k], 0);
+    const topay::TrackDesc* d = c->track.find(robots[k], 0);
     if (d) desc[k] = *d;
     else { desc[k].off = 0; desc[k].N = 0; desc[k].num = 0; }
-    const topay_mpc_params_t& p = c->mpc_prm[robots[k]];
+    const topay_mpc_params_t& p = c->mpc.prm[robots[k]];
     lds = std::max(lds, topay::mpc_lds_doubles(p.predict_steps, p.predict_steps - p.delay_num_w) * 8);
   }
   topay::TrackDesc* d_desc; int *d_rob, *d_st; double *d_t, *d_now, *d_cmd, *d_xopt, *d_so;
@@ -78,7 +47,7 @@ static topay_status mpc_launch(topay_ctx* c, int n, const int* robots, const dou
     d_so = k.take<double>(states_out ? 10 * R : 0); d_desc = k.take<topay::TrackDesc>(N); d_rob = k.take<int>(N); d_st = k.take<int>(TOPAY_MPC_ST_LEN * R);
   };
   topay_status s;
-  if ((s = c->mpc_io.carve(lay)) != TOPAY_OK) return s;
+  if ((s = c->mpc.io.carve(lay)) != TOPAY_OK) return s;
   HIPCHK(h2d(c, d_t, t_cur, N));
   if (now_state) HIPCHK(h2d(c, d_now, now_state, 10 * N));
   HIPCHK(h2d(c, d_desc, desc.data(), N));
@@ -87,21 +56,20 @@ static topay_status mpc_launch(topay_ctx* c, int n, const int* robots, const dou
   topay::MpcArgs A;
   memset(&A, 0, sizeof(A));
   A.n = n; A.periods = periods; A.ticks = ticks; A.follow = follow ? 1 : 0; A.probe = dense ? 1 : 0;
-  A.robots = d_rob; A.slots = c->mpc_slots.as<topay::MpcSlot>(); A.sims = c->mpc_sims.as<topay::SimSlot>(); A.desc = d_desc;
-  A.arena = c->tr_arena.as<double>(); A.t_cur = d_t; A.now_state = d_now; A.cmd = d_cmd; A.status = d_st; A.xopt = xopt ? d_xopt : nullptr;
+  A.robots = d_rob; A.slots = c->mpc.slots.as<topay::MpcSlot>(); A.sims = c->mpc.sims.as<topay::SimSlot>(); A.desc = d_desc;
+  A.arena = c->track.arena.as<double>(); A.t_cur = d_t; A.now_state = d_now; A.cmd = d_cmd; A.status = d_st; A.xopt = xopt ? d_xopt : nullptr;
   A.states_out = states_out ? d_so : nullptr;
   if (dense) A.D = *dense;
-  HIPCHK(hipEventRecord(c->ev0, c->stream));
+  HIPCHK(c->mpc.timer.start(c->stream));
   hipLaunchKernelGGL(topay::k_mpc_cmds, dim3((unsigned)n), dim3(64), lds, c->stream, A);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev1, c->stream));
+  HIPCHK(c->mpc.timer.stop(c->stream));
   if (cmd) HIPCHK(d2h(c, cmd, d_cmd, 16 * R));
   if (status) HIPCHK(d2h(c, status, d_st, TOPAY_MPC_ST_LEN * R));
   if (xopt) HIPCHK(d2h(c, xopt, d_xopt, XO * N));
   if (states_out) HIPCHK(d2h(c, states_out, d_so, 10 * R));
   HIPCHK(hipStreamSynchronize(c->stream));
-  float ms = 0.f;
-  if (!dense && hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->mpc_ms = ms;
+  if (!dense) (void)c->mpc.timer.read(&c->mpc.ms);
   return TOPAY_OK;
 }
 
@@ -134,25 +102,25 @@ topay_status topay_mpc_qp_dims(const topay_mpc_params_t* p, int* nx, int* nc) {
 topay_status topay_mpc_reset(topay_ctx* c, int n, const int* robots, const topay_mpc_params_t* params) {
   if (!c || n <= 0 || !robots || !params) return TOPAY_ERR_INVALID_ARG;
   if (topay_status s = mpc_check_params(*params); s != TOPAY_OK) return s;
-  if (topay_status s = mpc_check_robots(c, n, robots, false, false, "topay_mpc_reset"); s != TOPAY_OK) return s;
+  if (topay_status s = check_robot_slots(c, n, robots, kRobotDistinct, "topay_mpc_reset")) return s;
   HIPCHK(hipSetDevice(c->device));
-  if (topay_status s = mpc_alloc(c); s != TOPAY_OK) return s;
+  if (topay_status s = c->mpc.alloc(c->stream)) return s;
   topay::MpcSlot* slot = new topay::MpcSlot();
   memset(slot, 0, sizeof(*slot));
   slot->P = *params; slot->have = 1;
   hipError_t e = hipSuccess;
-  for (int k = 0; k < n && e == hipSuccess; k++) e = hipMemcpyAsync(c->mpc_slots.as<topay::MpcSlot>() + robots[k], slot, sizeof(*slot), hipMemcpyHostToDevice, c->stream);
+  for (int k = 0; k < n && e == hipSuccess; k++) e = hipMemcpyAsync(c->mpc.slots.as<topay::MpcSlot>() + robots[k], slot, sizeof(*slot), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   delete slot;
   HIPCHK(e);
-  for (int k = 0; k < n; k++) { c->mpc_prm[robots[k]] = *params; c->mpc_have[robots[k]] = 1; }
+  for (int k = 0; k < n; k++) { c->mpc.prm[robots[k]] = *params; c->mpc.have[robots[k]] = 1; }
   return TOPAY_OK;
 }
 
 topay_status topay_mpc_set_direct(topay_ctx* c, int n, const int* robots, const double* direct_pos) {
   if (!c || n <= 0 || !robots) return TOPAY_ERR_INVALID_ARG;
-  if (topay_status s = mpc_check_robots(c, n, robots, true, false, "topay_mpc_set_direct"); s != TOPAY_OK) return s;
-  if (direct_pos && !mpc_finite(direct_pos, 3 * (size_t)n)) { set_err("topay_mpc_set_direct: direct_pos must be finite"); return TOPAY_ERR_INVALID_ARG; }
+  if (topay_status s = check_robot_slots(c, n, robots, kRobotDistinct | kRobotMpc, "topay_mpc_set_direct")) return s;
+  if (direct_pos && !all_finite(direct_pos, 3 * (size_t)n)) { set_err("topay_mpc_set_direct: direct_pos must be finite"); return TOPAY_ERR_INVALID_ARG; }
   HIPCHK(hipSetDevice(c->device));
   struct Head { int mode, have; double direct[3]; } h;   // MpcSlot's members from `mode` to `direct`, as they lie there
   static_assert(offsetof(topay::MpcSlot, have) == offsetof(topay::MpcSlot, mode) + offsetof(Head, have) &&
@@ -162,7 +130,7 @@ topay_status topay_mpc_set_direct(topay_ctx* c, int n, const int* robots, const 
   for (int k = 0; k < n; k++) {
     h.mode = direct_pos ? 1 : 0; h.have = 1;
     for (int a = 0; a < 3; a++) h.direct[a] = direct_pos ? direct_pos[3 * (size_t)k + a] : 0.0;
-    char* dst = (char*)(c->mpc_slots.as<topay::MpcSlot>() + robots[k]) + offsetof(topay::MpcSlot, mode);
+    char* dst = (char*)(c->mpc.slots.as<topay::MpcSlot>() + robots[k]) + offsetof(topay::MpcSlot, mode);
     HIPCHK(hipMemcpyAsync(dst, &h, sizeof(h), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
   }
@@ -171,8 +139,8 @@ topay_status topay_mpc_set_direct(topay_ctx* c, int n, const int* robots, const 
 
 topay_status topay_mpc_cmds(topay_ctx* c, int n, const int* robots, const double* t_cur, const double* now_state, double* cmd, int* status, double* xopt) {
   if (!c || n <= 0 || !robots || !t_cur || !now_state || !cmd) return TOPAY_ERR_INVALID_ARG;
-  if (topay_status s = mpc_check_robots(c, n, robots, true, false, "topay_mpc_cmds"); s != TOPAY_OK) return s;
-  if (!mpc_finite(t_cur, (size_t)n) || !mpc_finite(now_state, 10 * (size_t)n)) { set_err("topay_mpc_cmds: clocks and states must be finite"); return TOPAY_ERR_INVALID_ARG; }
+  if (topay_status s = check_robot_slots(c, n, robots, kRobotDistinct | kRobotMpc, "topay_mpc_cmds")) return s;
+  if (!all_finite(t_cur, (size_t)n) || !all_finite(now_state, 10 * (size_t)n)) { set_err("topay_mpc_cmds: clocks and states must be finite"); return TOPAY_ERR_INVALID_ARG; }
   HIPCHK(hipSetDevice(c->device));
   return mpc_launch(c, n, robots, t_cur, now_state, 1, 0, false, cmd, status, xopt, nullptr, nullptr);
 }
@@ -180,10 +148,10 @@ topay_status topay_mpc_cmds(topay_ctx* c, int n, const int* robots, const double
 topay_status topay_mpc_probe(topay_ctx* c, int robot, double t_cur, const double* now_state, double* P, double* q, double* A, double* l, double* u,
                              double* x, double* y, double* z, int* info) {
   if (!c || !now_state) return TOPAY_ERR_INVALID_ARG;
-  if (topay_status s = mpc_check_robots(c, 1, &robot, true, false, "topay_mpc_probe"); s != TOPAY_OK) return s;
-  if (!mpc_finite(&t_cur, 1) || !mpc_finite(now_state, 10)) { set_err("topay_mpc_probe: clock and state must be finite"); return TOPAY_ERR_INVALID_ARG; }
+  if (topay_status s = check_robot_slots(c, 1, &robot, kRobotMpc, "topay_mpc_probe")) return s;
+  if (!all_finite(&t_cur, 1) || !all_finite(now_state, 10)) { set_err("topay_mpc_probe: clock and state must be finite"); return TOPAY_ERR_INVALID_ARG; }
   HIPCHK(hipSetDevice(c->device));
-  const topay_mpc_params_t& p = c->mpc_prm[robot];
+  const topay_mpc_params_t& p = c->mpc.prm[robot];
   int nx = 0, nc = 0;
   topay_mpc_qp_dims(&p, &nx, &nc);
   const size_t NX = (size_t)nx, NC = (size_t)nc;
@@ -192,8 +160,8 @@ topay_status topay_mpc_probe(topay_ctx* c, int robot, double t_cur, const double
     D.P = k.take<double>(NX * NX); D.q = k.take<double>(NX); D.A = k.take<double>(NC * NX); D.l = k.take<double>(NC); D.u = k.take<double>(NC);
     D.x = k.take<double>(NX); D.y = k.take<double>(NC); D.z = k.take<double>(NC); D.info = k.take<int>(2);
   };
-  if (topay_status s = c->mpc_dense.carve(lay); s != TOPAY_OK) return s;
-  HIPCHK(hipMemsetAsync(c->mpc_dense.p, 0, c->mpc_dense.bytes, c->stream));
+  if (topay_status s = c->mpc.dense.carve(lay); s != TOPAY_OK) return s;
+  HIPCHK(hipMemsetAsync(c->mpc.dense.p, 0, c->mpc.dense.bytes, c->stream));
   if (topay_status s = mpc_launch(c, 1, &robot, &t_cur, now_state, 1, 0, false, nullptr, nullptr, nullptr, nullptr, &D); s != TOPAY_OK) return s;
   // whether the call reaches the QP is the kernel's decision (its sum of the durations, its mode): it says so in info[1]
   int hinfo[2] = {0, 0};
@@ -214,10 +182,10 @@ topay_status topay_mpc_probe(topay_ctx* c, int robot, double t_cur, const double
 
 topay_status topay_mpc_get_state(topay_ctx* c, int robot, double* output, double* fifo, int* mode) {
   if (!c) return TOPAY_ERR_INVALID_ARG;
-  if (topay_status s = mpc_check_robots(c, 1, &robot, true, false, "topay_mpc_get_state"); s != TOPAY_OK) return s;
+  if (topay_status s = check_robot_slots(c, 1, &robot, kRobotMpc, "topay_mpc_get_state")) return s;
   HIPCHK(hipSetDevice(c->device));
   topay::MpcSlot* hs = new topay::MpcSlot();
-  const hipError_t e = d2h_sync(c, (char*)hs, (const char*)(c->mpc_slots.as<topay::MpcSlot>() + robot), sizeof(*hs));
+  const hipError_t e = d2h_sync(c, (char*)hs, (const char*)(c->mpc.slots.as<topay::MpcSlot>() + robot), sizeof(*hs));
   if (e == hipSuccess) {
     if (output) memcpy(output, hs->output, sizeof(hs->output));
     if (fifo) memcpy(fifo, hs->buff, sizeof(hs->buff));
@@ -230,45 +198,45 @@ topay_status topay_mpc_get_state(topay_ctx* c, int robot, double* output, double
 
 topay_status topay_mpc_ms(topay_ctx* c, double* ms) {
   if (!c || !ms) return TOPAY_ERR_INVALID_ARG;
-  *ms = c->mpc_ms;
+  *ms = c->mpc.ms;
   return TOPAY_OK;
 }
 
 topay_status topay_sim_reset(topay_ctx* c, int n, const int* robots, const double* state0, int delay_cmds) {
   if (!c || n <= 0 || !robots || !state0) return TOPAY_ERR_INVALID_ARG;
   if (delay_cmds < 1 || delay_cmds > TOPAY_MPC_MAX_STEPS) { set_err("topay_sim_reset: delay_cmds in 1..128"); return TOPAY_ERR_INVALID_ARG; }
-  if (topay_status s = mpc_check_robots(c, n, robots, false, false, "topay_sim_reset"); s != TOPAY_OK) return s;
-  if (!mpc_finite(state0, 10 * (size_t)n)) { set_err("topay_sim_reset: states must be finite"); return TOPAY_ERR_INVALID_ARG; }
+  if (topay_status s = check_robot_slots(c, n, robots, kRobotDistinct, "topay_sim_reset")) return s;
+  if (!all_finite(state0, 10 * (size_t)n)) { set_err("topay_sim_reset: states must be finite"); return TOPAY_ERR_INVALID_ARG; }
   HIPCHK(hipSetDevice(c->device));
-  if (topay_status s = mpc_alloc(c); s != TOPAY_OK) return s;
+  if (topay_status s = c->mpc.alloc(c->stream)) return s;
   topay::SimSlot* slot = new topay::SimSlot();
   hipError_t e = hipSuccess;
   for (int k = 0; k < n && e == hipSuccess; k++) {
     memset(slot, 0, sizeof(*slot));
     for (int a = 0; a < 10; a++) slot->st[a] = state0[10 * (size_t)k + a];
     slot->delay = delay_cmds; slot->have = 1;
-    e = hipMemcpyAsync(c->mpc_sims.as<topay::SimSlot>() + robots[k], slot, sizeof(*slot), hipMemcpyHostToDevice, c->stream);
+    e = hipMemcpyAsync(c->mpc.sims.as<topay::SimSlot>() + robots[k], slot, sizeof(*slot), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   }
   delete slot;
   HIPCHK(e);
-  for (int k = 0; k < n; k++) c->sim_have[robots[k]] = 1;
+  for (int k = 0; k < n; k++) c->mpc.sim_have[robots[k]] = 1;
   return TOPAY_OK;
 }
 
 topay_status topay_sim_step(topay_ctx* c, int n, const int* robots, const double* cmd, int ticks, double* state) {
   if (!c || n <= 0 || !robots || ticks < 0) return TOPAY_ERR_INVALID_ARG;
-  if (topay_status s = mpc_check_robots(c, n, robots, false, true, "topay_sim_step"); s != TOPAY_OK) return s;
-  if (cmd && !mpc_finite(cmd, 16 * (size_t)n)) { set_err("topay_sim_step: commands must be finite"); return TOPAY_ERR_INVALID_ARG; }
+  if (topay_status s = check_robot_slots(c, n, robots, kRobotDistinct | kRobotSim, "topay_sim_step")) return s;
+  if (cmd && !all_finite(cmd, 16 * (size_t)n)) { set_err("topay_sim_step: commands must be finite"); return TOPAY_ERR_INVALID_ARG; }
   HIPCHK(hipSetDevice(c->device));
   const size_t N = (size_t)n;
   double *d_cmd, *d_state; int* d_rob;
   auto lay = [&](Carver& k) { d_cmd = k.take<double>(16 * N); d_state = k.take<double>(10 * N); d_rob = k.take<int>(N); };
-  if (topay_status s = c->mpc_io.carve(lay); s != TOPAY_OK) return s;
+  if (topay_status s = c->mpc.io.carve(lay); s != TOPAY_OK) return s;
   if (cmd) HIPCHK(h2d(c, d_cmd, cmd, 16 * N));
   HIPCHK(h2d(c, d_rob, robots, N));
   topay::SimArgs A;
-  A.n = n; A.ticks = ticks; A.robots = d_rob; A.sims = c->mpc_sims.as<topay::SimSlot>(); A.cmd = cmd ? d_cmd : nullptr; A.state = d_state;
+  A.n = n; A.ticks = ticks; A.robots = d_rob; A.sims = c->mpc.sims.as<topay::SimSlot>(); A.cmd = cmd ? d_cmd : nullptr; A.state = d_state;
   hipLaunchKernelGGL(topay::k_sim_step, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, A);
   HIPCHK(hipGetLastError());
   if (state) HIPCHK(d2h(c, state, d_state, 10 * N));
@@ -279,8 +247,8 @@ topay_status topay_sim_step(topay_ctx* c, int n, const int* robots, const double
 topay_status topay_track_follow(topay_ctx* c, int n, const int* robots, const double* t0, int periods, int ticks_per_period, double* states_out,
                                 double* cmds_out, int* status_out) {
   if (!c || n <= 0 || !robots || !t0 || periods < 1 || periods > 100000 || ticks_per_period < 0) return TOPAY_ERR_INVALID_ARG;
-  if (topay_status s = mpc_check_robots(c, n, robots, true, true, "topay_track_follow"); s != TOPAY_OK) return s;
-  if (!mpc_finite(t0, (size_t)n)) { set_err("topay_track_follow: clocks must be finite"); return TOPAY_ERR_INVALID_ARG; }
+  if (topay_status s = check_robot_slots(c, n, robots, kRobotDistinct | kRobotMpc | kRobotSim, "topay_track_follow")) return s;
+  if (!all_finite(t0, (size_t)n)) { set_err("topay_track_follow: clocks must be finite"); return TOPAY_ERR_INVALID_ARG; }
   HIPCHK(hipSetDevice(c->device));
   return mpc_launch(c, n, robots, t0, nullptr, periods, ticks_per_period, true, cmds_out, status_out, nullptr, states_out, nullptr);
 }

@@ -2,7 +2,7 @@
 // include/topay.h in their order, one function each: per front-end launch the calls, roadmap + JPS, candidate table + dense
 // paths, search, hand-off to the solver; then once per try solve + gate + winner, and the winners into the store.  What passes
 // between the stages is a PlanTry; every packed device block is a struct that states its layout once.  The buffers and the
-// clock's events are the context's PlanWork, the winners go to its PlanStore (topay_host_ctx.h), which the getters below read.
+// clock's stopwatches are the context's PlanWork, the winners go to its PlanStore (topay_host_ctx.h), which the getters below read.
 
 #pragma once
 
@@ -19,44 +19,27 @@ static const int kPlanJpsCap = 512;     // points per JPS path kept
 static int* result_row(int* result, int p) { return result + TOPAY_PLAN_RES_LEN * (size_t)p; }
 static int* cand_row(int* cand, int p, int t, int k) { return cand + (((size_t)p * 2 + t) * TOPAY_PLAN_MAX_CAND + k) * TOPAY_PLAN_CAND_LEN; }
 
-// Device time of one stage (TOPAY_PLAN_MS_*): a pair of events around its launches on the context's stream, read once the call
-// has finished.  Only pairs whose end has been recorded in THIS call are read (an error return between begin and end leaves none behind).
+// Device time of one stage (TOPAY_PLAN_MS_*): a stopwatch around its launches on the context's stream, read once the call has
+// finished.  A stage is timed once per launch of a call, so the stopwatches are taken in turn from PlanWork and their times
+// summed by stage; one whose stop was never recorded (an error return between begin and end) is not read.
 struct PlanClock {
   topay_ctx* c;
   PlanWork& w;
   size_t used = 0;
   explicit PlanClock(topay_ctx* c_) : c(c_), w(c_->plan) {}
-  int reserve(int stage) {   // a pair for a launcher that records the events itself, around its kernels only; then done(id)
-    if (used + 2 > w.events.size()) {
-      hipEvent_t a = nullptr, b = nullptr;
-      if (hipEventCreate(&a) != hipSuccess) return -1;
-      if (hipEventCreate(&b) != hipSuccess) { (void)hipEventDestroy(a); return -1; }
-      w.events.push_back(a);
-      w.events.push_back(b);
-    }
-    w.event_stage.resize(w.events.size() / 2);
-    w.event_done.resize(w.events.size() / 2);
-    const int id = (int)(used / 2);
-    w.event_stage[id] = stage;
-    w.event_done[id] = 0;
-    used += 2;
-    return id;
+  DevTimer* reserve(int stage) {   // for a launcher that starts and stops it itself, around its kernels only
+    if (used == w.timers.size()) { w.timers.emplace_back(); w.timer_stage.push_back(0); }
+    w.timer_stage[used] = stage;
+    w.timers[used].stopped = false;
+    return &w.timers[used++];
   }
-  hipEvent_t ev(int id, int which) { return id < 0 ? nullptr : w.events[2 * (size_t)id + which]; }
-  void done(int id) { if (id >= 0) w.event_done[id] = 1; }
-  int begin(int stage) {
-    const int id = reserve(stage);
-    if (id >= 0) (void)hipEventRecord(ev(id, 0), c->stream);
-    return id;
-  }
-  void end(int id) {
-    if (id >= 0 && hipEventRecord(ev(id, 1), c->stream) == hipSuccess) done(id);
-  }
+  DevTimer* begin(int stage) { DevTimer* t = reserve(stage); (void)t->start(c->stream); return t; }
+  void end(DevTimer* t) { (void)t->stop(c->stream); }
   void collect() {
     (void)hipStreamSynchronize(c->stream);
-    for (size_t i = 0; i + 1 < used; i += 2) {
-      float ms = 0.f;
-      if (w.event_done[i / 2] && hipEventElapsedTime(&ms, w.events[i], w.events[i + 1]) == hipSuccess) w.stage_ms[w.event_stage[i / 2]] += ms;
+    for (size_t i = 0; i < used; i++) {
+      double ms = 0.0;
+      if (w.timers[i].read(&ms) == hipSuccess) w.stage_ms[w.timer_stage[i]] += ms;
     }
   }
 };
@@ -177,20 +160,14 @@ static topay_status plan_roadmap_jps(PlanTry& T) {
   topay_ctx* c = T.c;
   const topay_plan_params_t& P = T.R.P;
   double* raw = c->plan.raw.as<double>();
-  int ev = T.clk.reserve(TOPAY_PLAN_MS_ROADMAP);
   topay_status s = topo_impl(c, T.nc, T.cmid.data(), T.sxy.data(), T.exy.data(), T.crit.data(), &P.topo, 0, T.inst.data(), P.topo.reserve_num, T.cap_points, raw,
-                             false, &T.td, T.clk.ev(ev, 0), T.clk.ev(ev, 1));
+                             false, &T.td, T.clk.reserve(TOPAY_PLAN_MS_ROADMAP));
   if (s != TOPAY_OK) return s;
-  T.clk.done(ev);
   T.jd.len = nullptr;
-  if (T.t == 0) {   // (the second try has no JPS candidate)
-    ev = T.clk.reserve(TOPAY_PLAN_MS_JPS);
+  if (T.t == 0)   // (the second try has no JPS candidate)
     s = jps_impl(c, T.nc, T.cmid.data(), T.sxy.data(), T.exy.data(), c->hp.chassis_colli_radius + P.jps_margin, kPlanJpsCap, c->plan.jps_io, raw + 2 * T.topo_pts,
-                 &T.jd, T.clk.ev(ev, 0), T.clk.ev(ev, 1));
-    if (s != TOPAY_OK) return s;
-    T.clk.done(ev);
-  }
-  return TOPAY_OK;
+                 &T.jd, "topay_plan_calls", T.clk.reserve(TOPAY_PLAN_MS_JPS));
+  return s;
 }
 
 // ---- candidate table, dense paths; the calls' counts into `result`, the slots that go on into T.sel
@@ -206,7 +183,7 @@ static topay_status plan_candidates(PlanTry& T) {
   A.jps_base = (long long)T.topo_pts;
   A.topo_np = T.td.n_paths; A.topo_len = T.td.path_len; A.jps_len = T.jd.len; A.start = T.in.start; A.end = T.in.end;
   A.ncand = T.tab.ncand; A.raw_off = T.tab.raw_off; A.raw_len = T.tab.raw_len; A.syaw = T.tab.syaw; A.eyaw = T.tab.eyaw;
-  const int ev = T.clk.begin(TOPAY_PLAN_MS_DENSE);
+  DevTimer* ev = T.clk.begin(TOPAY_PLAN_MS_DENSE);
   hipLaunchKernelGGL(topay::k_plan_candidates, dim3((T.nc + 63) / 64), dim3(64), 0, c->stream, A);
   HIPCHK(hipGetLastError());
   if ((s = dense_launch(c, (int)NS, c->plan.raw.as<double>(), T.tab.raw_off, T.tab.raw_len, R.P.dense_step, T.tab.syaw, T.tab.eyaw, c->hp.max_v, c->hp.max_w,
@@ -247,7 +224,7 @@ static topay_status plan_search(PlanTry& T, std::vector<int>& wlen, std::vector<
   M.n = NI;
   if ((s = c->plan.mc.place(M)) != TOPAY_OK) return s;
   HIPCHK(h2d(c, M.slot, T.sel.data(), NI));
-  const int ev = T.clk.begin(TOPAY_PLAN_MS_SEARCH);
+  DevTimer* ev = T.clk.begin(TOPAY_PLAN_MS_SEARCH);
   hipLaunchKernelGGL(topay::k_plan_pack_search, dim3((ni + 63) / 64), dim3(64), 0, c->stream, ni, (const int*)M.slot, kPlanDenseCap, (const int*)T.tab.dense_len,
                      (const double*)T.in.start, (const double*)T.in.end, (const int*)T.in.mid, (const unsigned long long*)T.in.call_no, T.t, M.off, M.len, M.start,
                      M.end, M.mid, M.inst);
@@ -292,7 +269,7 @@ static topay_status plan_handoff(PlanTry& T, const std::vector<int>& wlen, const
   HIPCHK(h2d(c, H.path_off, poff.data(), H.n));
   HIPCHK(h2d(c, H.src, src.data(), H.n));
   HIPCHK(h2d(c, H.src_call, src_call.data(), H.n));
-  const int ev = T.clk.begin(TOPAY_PLAN_MS_INIT);
+  DevTimer* ev = T.clk.begin(TOPAY_PLAN_MS_INIT);
   hipLaunchKernelGGL(topay::k_plan_pack_solver, dim3((unsigned)nsv), dim3(64), 0, c->stream, nsv, (const int*)H.src, (const int*)H.src_call, T.mc.layer_cap,
                      (const int*)T.mc.wb_len, (const double*)T.mc.wb, (const long long*)H.path_off, (const double*)T.in.start_v, b0, c->plan.paths.as<double>(),
                      c->plan.bvel.as<double>());
@@ -308,7 +285,7 @@ static topay_status plan_solve(PlanTry& T, PlanStore::Winners& W) {
   topay_ctx* c = T.c;
   const PlanReq& R = T.R;
   const int B = (int)T.call.size(), t = T.t;
-  int ev = T.clk.begin(TOPAY_PLAN_MS_INIT);
+  DevTimer* ev = T.clk.begin(TOPAY_PLAN_MS_INIT);
   topay_status s = set_init_traj_impl(c, B, T.len.data(), c->plan.paths.as<double>(), c->plan.bvel.as<double>(), nullptr, T.mid.data(), hipMemcpyDeviceToDevice);
   T.clk.end(ev);
   if (s == TOPAY_ERR_TOO_MANY_PIECES) {   // every candidate needs more pieces than the build solves
@@ -376,7 +353,7 @@ static topay_status plan_store_winners(PlanTry& T, const PlanStore::Winners& W) 
   HIPCHK(h2d(c, I.idx, W.idx.data(), I.n));
   HIPCHK(h2d(c, I.piece_off, W.piece_off.data(), I.n + 1));
   HIPCHK(h2d(c, I.front_off, W.front_off.data(), I.n + 1));
-  const int ev = T.clk.begin(TOPAY_PLAN_MS_STORE);
+  DevTimer* ev = T.clk.begin(TOPAY_PLAN_MS_STORE);
   hipLaunchKernelGGL(k_gather_results, dim3(nw), dim3(64), 0, c->stream, c->db, nw, (const int*)I.idx, (const int*)I.piece_off, dst.dur, dst.coef, dst.knots);
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(topay::k_plan_gather_front, dim3(nw), dim3(64), 0, c->stream, nw, (const int*)I.idx, (const double*)c->paths.as<double>(),
@@ -436,19 +413,11 @@ static topay_status plan_calls_impl(topay_ctx* c, int n, const int* map_ids, con
     set_err("topay_plan_calls: parameters out of range (max_candidates 1..8, dense_step > 0, cancel_budget >= 0)");
     return TOPAY_ERR_INVALID_ARG;
   }
+  if (topay_status cs = check_map_slots(c, n, map_ids, kMapResident | kMapFront, "topay_plan_calls")) return cs;
   R.mids.assign((size_t)n, 0);
-  for (int p = 0; p < n; p++) {
-    const int mid = R.mids[p] = map_ids ? map_ids[p] : 0;
-    if (mid < 0 || mid >= TOPAY_MAX_MAPS) return TOPAY_ERR_INVALID_ARG;
-    if (!c->have_map[mid]) { set_err("map slot not set"); return TOPAY_ERR_NO_MAP; }
-    const DevMap& m = c->hmaps[mid];
-    if (!m.esdf2d_inflate || !m.esdf2d_critical) {
-      set_err("topay_plan_calls: map slot " + std::to_string(mid) + " has no front-end fields: fill it with topay_build_esdf*, not topay_set_map");
-      return TOPAY_ERR_NO_MAP;
-    }
-  }
+  if (map_ids) R.mids.assign(map_ids, map_ids + n);
   HIPCHK(hipSetDevice(c->device));
-  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }
+  if (topay_status ws = wait_pending(c)) return ws;
   c->plan_store.reset(n);
   for (int k = 0; k < TOPAY_PLAN_MS_LEN; k++) c->plan.stage_ms[k] = 0.0;
   for (int p = 0; p < n; p++) {

@@ -21,7 +21,7 @@ static topay_status eval_one(topay_ctx* c, int stage, int i, const double* x, co
   if (!c || !c->have_traj) return TOPAY_ERR_NO_TRAJ;
   if (i < 0 || i >= c->B || (stage != 1 && stage != 2) || !x) return TOPAY_ERR_INVALID_ARG;
   HIPCHK(hipSetDevice(c->device));
-  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }   // inputs of a solve in flight stay untouched
+  if (topay_status ws = wait_pending(c)) return ws;   // inputs of a solve in flight stay untouched
   const int N = c->hN[i], nn = 10 * N - 8;
   if (N == 0) return TOPAY_ERR_TOO_MANY_PIECES;
   HIPCHK(h2d_sync(c, c->db.x_of(c->h_noff[i]), x, (size_t)nn));
@@ -216,7 +216,7 @@ topay_status topay_get_result(topay_ctx* c, int i, int* success, double* cost, i
   if (!c || !c->have_traj) return TOPAY_ERR_NO_TRAJ;
   if (i < 0 || i >= c->B) return TOPAY_ERR_INVALID_ARG;
   HIPCHK(hipSetDevice(c->device));
-  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }
+  if (topay_status ws = wait_pending(c)) return ws;
   const int N = c->hN[i], rows = 6 * N;
   if (N == 0) {  // not representable (more than TOPAY_MAX_N pieces): failed candidate, nothing else to report
     if (success) *success = 0;
@@ -247,7 +247,7 @@ topay_status topay_get_results(topay_ctx* c, int n, const int* idx, int cap_piec
   if (n < 0 || (n > 0 && (!idx || !piece_off))) return TOPAY_ERR_INVALID_ARG;
   if (n == 0) return TOPAY_OK;
   HIPCHK(hipSetDevice(c->device));
-  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }
+  if (topay_status ws = wait_pending(c)) return ws;
   if (!c->solved) { set_err("topay_get_results: the batch has not been optimised"); return TOPAY_ERR_NO_TRAJ; }
   std::vector<int> off((size_t)n + 1, 0);
   for (int k = 0; k < n; k++) {
@@ -357,7 +357,7 @@ topay_status topay_eval_batch(topay_ctx* c, int stage, int repeats, double* f) {
   if (!c || !c->have_traj) return TOPAY_ERR_NO_TRAJ;
   if ((stage != 1 && stage != 2) || repeats == 0) return TOPAY_ERR_INVALID_ARG;
   HIPCHK(hipSetDevice(c->device));
-  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }   // inputs of a solve in flight stay untouched
+  if (topay_status ws = wait_pending(c)) return ws;   // inputs of a solve in flight stay untouched
   // x <- x0 (strided copy), alm <- init
   std::vector<double> x0((size_t)c->B * kX0Stride), xs((size_t)c->h_noff[c->B] + 1, 0.0), alm((size_t)c->B * kAlmLen);
   HIPCHK(d2h_sync(c, x0.data(), c->x0.as<double>(), x0.size()));
@@ -371,14 +371,12 @@ topay_status topay_eval_batch(topay_ctx* c, int stage, int repeats, double* f) {
   }
   HIPCHK(h2d_sync(c, c->x.as<double>(), xs.data(), (size_t)c->h_noff[c->B]));
   HIPCHK(h2d_sync(c, c->alm.as<double>(), alm.data(), alm.size()));
-  HIPCHK(hipEventRecord(c->ev0, c->stream));
+  HIPCHK(c->eval_timer.start(c->stream));
   topay_status s = launch_classes<true>(c, false, stage, repeats);
   if (s != TOPAY_OK) return s;
-  HIPCHK(hipEventRecord(c->ev1, c->stream));
+  HIPCHK(c->eval_timer.stop(c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  c->last_ms = ms;
+  HIPCHK(c->eval_timer.read(&c->last_ms));
   if (f) HIPCHK(d2h_sync(c, f, c->fout.as<double>(), (size_t)c->B));
   return TOPAY_OK;
 }

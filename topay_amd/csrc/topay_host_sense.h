@@ -38,40 +38,11 @@ static topay_status sense_half_box(const topay_sense_params_t* p, double res, Se
   }
   return TOPAY_OK;
 }
-static topay_status sense_events(topay_ctx* c) {
-  for (hipEvent_t& e : c->sense_ev)
-    if (!e) HIPCHK(hipEventCreate(&e));
+// every slot of a call has a belief (the slots are in range: check_map_slots)
+static topay_status sense_check_beliefs(topay_ctx* c, int n, const int* map_ids, const char* who) {
+  for (int k = 0; k < n; k++)
+    if (!c->sense.has_belief(map_ids[k])) { set_err(std::string(who) + ": slot " + std::to_string(map_ids[k]) + " without a belief (topay_sense_reset)"); return TOPAY_ERR_NO_MAP; }
   return TOPAY_OK;
-}
-static topay_status sense_elapsed(topay_ctx* c, int which) {
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, c->sense_ev[0], c->sense_ev[1]));
-  c->sense_ms[which] = ms;
-  return TOPAY_OK;
-}
-// the slots of a call: in range, each once
-static topay_status sense_check_ids(int n, const int* map_ids) {
-  std::vector<char> seen(TOPAY_MAX_MAPS, 0);
-  for (int k = 0; k < n; k++) {
-    const int m = map_ids[k];
-    if (m < 0 || m >= TOPAY_MAX_MAPS) return TOPAY_ERR_INVALID_ARG;
-    if (seen[m]) { set_err("topay_sense: map slot " + std::to_string(m) + " named twice in one call"); return TOPAY_ERR_INVALID_ARG; }
-    seen[m] = 1;
-  }
-  return TOPAY_OK;
-}
-// the occupancy grid a scan reads: a slot of the last topay_sense_commit or of the last world generation
-static const signed char* sense_truth_occ3(topay_ctx* c, int m, int* dims) {
-  if (m >= 0 && m < (int)c->sense.size() && c->sense[m].have_occ) {
-    for (int a = 0; a < 3; a++) dims[a] = c->sense[m].desc.dims[a];
-    return c->sense_occ.as<signed char>() + c->sense[m].occ3_off;
-  }
-  if (c->world_n > 0 && m >= c->world_first && m < c->world_first + c->world_n && c->world_occ.p) {
-    for (int a = 0; a < 3; a++) dims[a] = c->world_dims[a];
-    const size_t n3 = (size_t)dims[0] * dims[1] * dims[2];
-    return c->world_occ.as<signed char>() + (size_t)(m - c->world_first) * n3;
-  }
-  return nullptr;
 }
 
 extern "C" {
@@ -99,14 +70,14 @@ topay_status topay_sense_logodds(const topay_sense_params_t* p, float* l6) {
 
 topay_status topay_sense_reset(topay_ctx* c, int n, const int* map_ids, const topay_map_desc_t* desc) {
   if (!c || n <= 0 || !map_ids || !desc || !(desc->resolution > 0.0)) return TOPAY_ERR_INVALID_ARG;
-  if (topay_status s = sense_check_ids(n, map_ids)) return s;
+  if (topay_status s = check_map_slots(c, n, map_ids, kMapOnce, "topay_sense_reset")) return s;
   if (topay_status s = map_dims_check(desc)) return s;
   HIPCHK(hipSetDevice(c->device));
-  if (c->sense.empty()) c->sense.resize(TOPAY_MAX_MAPS);
+  if (c->sense.slot.empty()) c->sense.slot.resize(TOPAY_MAX_MAPS);
   const size_t n3 = (size_t)desc->dims[0] * desc->dims[1] * desc->dims[2];
   const int empty_box[6] = {0x7f7f7f7f, 0x7f7f7f7f, 0x7f7f7f7f, 0x7f7f7f7f, 0x7f7f7f7f, 0x7f7f7f7f};
   for (int k = 0; k < n; k++) {
-    topay_ctx::SenseBelief& b = c->sense[map_ids[k]];
+    SenseBelief& b = c->sense.slot[map_ids[k]];
     b.have = false;
     auto lay = [&](Carver& q) { b.logodds = q.take<float>(n3); b.cnt = q.take<int>(n3); b.box = q.take<int>(8); };
     if (topay_status s = b.buf.carve(lay)) return s;
@@ -126,7 +97,7 @@ topay_status topay_sense_insert(topay_ctx* c, int n, const int* map_ids, const i
                                 const topay_sense_params_t* params, int* status) {
   if (!c || n <= 0 || !map_ids || !cloud_off || !sensor_pos || !params) return TOPAY_ERR_INVALID_ARG;
   topay_status s;
-  if ((s = sense_check_ids(n, map_ids)) != TOPAY_OK) return s;
+  if ((s = check_map_slots(c, n, map_ids, kMapOnce, "topay_sense_insert")) != TOPAY_OK) return s;
   SenseP P;
   if ((s = sense_make_params(params, P)) != TOPAY_OK) return s;
   const int batch_size = params->batch_update_size > 0 ? params->batch_update_size : 1;   // config.hpp:190-194
@@ -136,9 +107,8 @@ topay_status topay_sense_insert(topay_ctx* c, int n, const int* map_ids, const i
     if (cloud_off[k + 1] < cloud_off[k]) return TOPAY_ERR_INVALID_ARG;
   const size_t total = (size_t)cloud_off[n];
   if (total > 0 && !points_xyzi) return TOPAY_ERR_INVALID_ARG;
-  if (from_scan && total > c->sense_scan_points) { set_err("topay_sense_insert: offsets beyond the points of the last topay_sense_scan"); return TOPAY_ERR_INVALID_ARG; }
-  for (int k = 0; k < n; k++)
-    if (map_ids[k] >= (int)c->sense.size() || !c->sense[map_ids[k]].have) { set_err("topay_sense_insert: slot without a belief (topay_sense_reset)"); return TOPAY_ERR_NO_MAP; }
+  if (from_scan && total > c->sense.scan_points) { set_err("topay_sense_insert: offsets beyond the points of the last topay_sense_scan"); return TOPAY_ERR_INVALID_ARG; }
+  if ((s = sense_check_beliefs(c, n, map_ids, "topay_sense_insert")) != TOPAY_OK) return s;
   // per slot: the descriptor, the rays this cloud can add to the batch, the voxel box a flush has to cover
   std::vector<SenseSlot> hs((size_t)n);
   std::vector<int> h_nsurv((size_t)n), st((size_t)n, 0);
@@ -146,11 +116,11 @@ topay_status topay_sense_insert(topay_ctx* c, int n, const int* map_ids, const i
   long long max_fvol = 0;
   bool any_flush = false;
   for (int k = 0; k < n; k++) {
-    topay_ctx::SenseBelief& b = c->sense[map_ids[k]];
+    SenseBelief& b = c->sense.slot[map_ids[k]];
     SenseSlot& S = hs[(size_t)k];
     memset(&S, 0, sizeof(S));
     if (k == 0) { if ((s = sense_half_box(params, b.desc.resolution, P)) != TOPAY_OK) return s; }
-    else if (b.desc.resolution != c->sense[map_ids[0]].desc.resolution) { set_err("topay_sense_insert: the slots of a call share one resolution"); return TOPAY_ERR_INVALID_ARG; }
+    else if (b.desc.resolution != c->sense.slot[map_ids[0]].desc.resolution) { set_err("topay_sense_insert: the slots of a call share one resolution"); return TOPAY_ERR_INVALID_ARG; }
     const double* sp = sensor_pos + 3 * (size_t)k;
     for (int a = 0; a < 3; a++) {
       if (!(std::fabs(sp[a] - b.desc.origin[a]) <= 1.0e6)) { set_err("topay_sense_insert: sensor position not finite or more than 1e6 m from the map"); return TOPAY_ERR_INVALID_ARG; }
@@ -178,7 +148,7 @@ topay_status topay_sense_insert(topay_ctx* c, int n, const int* map_ids, const i
   std::vector<Next> nx((size_t)n);
   long long max_vol = 0;   // the largest grid of the call: no cache box is larger
   for (int k = 0; k < n; k++) {
-    const topay_ctx::SenseBelief& b = c->sense[map_ids[k]];
+    const SenseBelief& b = c->sense.slot[map_ids[k]];
     SenseSlot& S = hs[(size_t)k];
     Next& N = nx[(size_t)k];
     N.batch_counter = b.batch_counter; N.pending_rays = b.pending_rays;
@@ -196,26 +166,26 @@ topay_status topay_sense_insert(topay_ctx* c, int n, const int* map_ids, const i
   }
   if ((long long)n * ((max_vol + TOPAY_SENSE_BLOCK - 1) / TOPAY_SENSE_BLOCK) >= (1ll << 31)) { set_err("topay_sense_insert: flush launch too large"); return TOPAY_ERR_UNSUPPORTED; }
   HIPCHK(hipSetDevice(c->device));
-  if ((s = sense_events(c)) != TOPAY_OK) return s;
+  DevTimer* tm = c->sense.timer;
   const bool select = P.thresh > 0 && max_len > 0;
   SenseSlot* d_slots; int *d_nsurv, *d_surv, *d_boxes;
   auto lay = [&](Carver& q) {
     d_slots = q.take<SenseSlot>((size_t)n); d_nsurv = q.take<int>((size_t)n); d_boxes = q.take<int>(6 * (size_t)n); d_surv = q.take<int>(select ? total : 1);
   };
-  if ((s = c->sense_io.carve(lay)) != TOPAY_OK) return s;
+  if ((s = c->sense.io.carve(lay)) != TOPAY_OK) return s;
   const SensePoint* d_pts = nullptr;
-  if (from_scan) d_pts = c->sense_scan.as<SensePoint>();
+  if (from_scan) d_pts = c->sense.scan.as<SensePoint>();
   else if (total > 0) {
-    if ((s = c->sense_pts.ensure(total * sizeof(SensePoint))) != TOPAY_OK) return s;
-    HIPCHK(h2d(c, c->sense_pts.as<float>(), points_xyzi, total * 4));
-    d_pts = c->sense_pts.as<SensePoint>();
+    if ((s = c->sense.pts.ensure(total * sizeof(SensePoint))) != TOPAY_OK) return s;
+    HIPCHK(h2d(c, c->sense.pts.as<float>(), points_xyzi, total * 4));
+    d_pts = c->sense.pts.as<SensePoint>();
   }
   HIPCHK(h2d(c, d_slots, (const SenseSlot*)hs.data(), (size_t)n));
   HIPCHK(h2d(c, d_nsurv, (const int*)h_nsurv.data(), (size_t)n));
-  HIPCHK(hipEventRecord(c->sense_ev[0], c->stream));
+  HIPCHK(tm[SenseState::kInsert].start(c->stream));
   for (int k = 0; k < n; k++) {   // the launches follow: the slots' host state moves with them
     if (hs[(size_t)k].skip) continue;
-    topay_ctx::SenseBelief& b = c->sense[map_ids[k]];
+    SenseBelief& b = c->sense.slot[map_ids[k]];
     const Next& N = nx[(size_t)k];
     b.prm = *params;
     b.batch_counter = N.batch_counter; b.pending_rays = N.pending_rays;
@@ -235,9 +205,9 @@ topay_status topay_sense_insert(topay_ctx* c, int n, const int* map_ids, const i
     HIPCHK(d2h(c, h_boxes.data(), (const int*)d_boxes, 6 * (size_t)n));
   }
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->sense_ev[1], c->stream));
+  HIPCHK(tm[SenseState::kInsert].stop(c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  if ((s = sense_elapsed(c, 1)) != TOPAY_OK) return s;
+  HIPCHK(tm[SenseState::kInsert].read(&c->sense.ms[SenseState::kInsert]));
   for (int k = 0; k < n; k++) {
     const int* bx = h_boxes.data() + 6 * (size_t)k;
     if (!hs[(size_t)k].flush || bx[0] == 0x7f7f7f7f) continue;
@@ -247,7 +217,7 @@ topay_status topay_sense_insert(topay_ctx* c, int n, const int* map_ids, const i
   }
   max_fvol = std::min(max_fvol, max_vol);   // (a box lies inside its grid: the launch size checked above holds)
   const long long fbps = (max_fvol + TOPAY_SENSE_BLOCK - 1) / TOPAY_SENSE_BLOCK;
-  HIPCHK(hipEventRecord(c->sense_ev[0], c->stream));
+  HIPCHK(tm[SenseState::kFlush].start(c->stream));
   if (any_flush) {
     if (max_fvol > 0) {
       hipLaunchKernelGGL(k_sense_flush, dim3((unsigned)((long long)n * fbps)), dim3(TOPAY_SENSE_BLOCK), 0, c->stream, P, (const SenseSlot*)d_slots, (int)fbps);
@@ -255,9 +225,9 @@ topay_status topay_sense_insert(topay_ctx* c, int n, const int* map_ids, const i
     hipLaunchKernelGGL(k_sense_box_reset, dim3((unsigned)((n * 6 + 255) / 256)), dim3(256), 0, c->stream, (const SenseSlot*)d_slots, n);
   }
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->sense_ev[1], c->stream));
+  HIPCHK(tm[SenseState::kFlush].stop(c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  if ((s = sense_elapsed(c, 2)) != TOPAY_OK) return s;
+  HIPCHK(tm[SenseState::kFlush].read(&c->sense.ms[SenseState::kFlush]));
   if (status) memcpy(status, st.data(), sizeof(int) * (size_t)n);
   return TOPAY_OK;
 }
@@ -265,12 +235,11 @@ topay_status topay_sense_insert(topay_ctx* c, int n, const int* map_ids, const i
 topay_status topay_sense_commit(topay_ctx* c, int n, const int* map_ids) {
   if (!c || n <= 0 || !map_ids) return TOPAY_ERR_INVALID_ARG;
   topay_status s;
-  if ((s = sense_check_ids(n, map_ids)) != TOPAY_OK) return s;
-  for (int k = 0; k < n; k++)
-    if (map_ids[k] >= (int)c->sense.size() || !c->sense[map_ids[k]].have) { set_err("topay_sense_commit: slot without a belief (topay_sense_reset)"); return TOPAY_ERR_NO_MAP; }
+  if ((s = check_map_slots(c, n, map_ids, kMapOnce, "topay_sense_commit")) != TOPAY_OK) return s;
+  if ((s = sense_check_beliefs(c, n, map_ids, "topay_sense_commit")) != TOPAY_OK) return s;
   HIPCHK(hipSetDevice(c->device));
-  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }   // inputs of a solve in flight stay untouched
-  if ((s = sense_events(c)) != TOPAY_OK) return s;
+  if (topay_status ws = wait_pending(c)) return ws;   // inputs of a solve in flight stay untouched
+  DevTimer& tm = c->sense.timer[SenseState::kCommit];
   // Runs of consecutive slots on one grid go through the field construction together (its launches take a batch of maps).  The lane
   // emulator runs the blocks of a launch along x only (blockIdx.y = map stays 0), so there a run is one slot.
 #ifdef TOPAY_CPU_EMU
@@ -291,8 +260,8 @@ topay_status topay_sense_commit(topay_ctx* c, int n, const int* map_ids) {
   };
   for (int k = 0; k < n;) {
     int e = k + 1;
-    while (e < n && e - k < max_run && ids[e] == ids[e - 1] + 1 && same_grid(c->sense[ids[e]].desc, c->sense[ids[k]].desc)) e++;
-    const topay_map_desc_t& d = c->sense[ids[k]].desc;
+    while (e < n && e - k < max_run && ids[e] == ids[e - 1] + 1 && same_grid(c->sense.slot[ids[e]].desc, c->sense.slot[ids[k]].desc)) e++;
+    const topay_map_desc_t& d = c->sense.slot[ids[k]].desc;
     const size_t n2 = (size_t)d.dims[0] * d.dims[1], n3 = n2 * d.dims[2], R = (size_t)(e - k);
     Run r{ids[k], e - k, bytes, 0, 0};
     bytes += (R * n3 + 15) & ~(size_t)15;   // (each grid starts on a 16-byte boundary: k_sense_occupancy's 16-byte stores)
@@ -301,14 +270,14 @@ topay_status topay_sense_commit(topay_ctx* c, int n, const int* map_ids) {
     runs.push_back(r);
     k = e;
   }
-  for (auto& b : c->sense) b.have_occ = false;   // the grids of the last commit are overwritten
-  if ((s = c->sense_occ.ensure(bytes)) != TOPAY_OK) return s;
-  signed char* base = c->sense_occ.as<signed char>();
+  c->sense.forget(0, TOPAY_MAX_MAPS);   // the grids of the last commit are overwritten
+  if ((s = c->sense.occ.ensure(bytes)) != TOPAY_OK) return s;
+  signed char* base = c->sense.occ.as<signed char>();
   std::vector<SenseOccSlot> ho((size_t)n);
   int max_cols = 0, at = 0;
   for (const Run& r : runs)
     for (int i = 0; i < r.n; i++, at++) {
-      topay_ctx::SenseBelief& b = c->sense[r.first + i];
+      SenseBelief& b = c->sense.slot[r.first + i];
       const size_t n2 = (size_t)b.desc.dims[0] * b.desc.dims[1], n3 = n2 * b.desc.dims[2];
       SenseP P;
       if ((s = sense_make_params(&b.prm, P)) != TOPAY_OK) return s;
@@ -319,27 +288,29 @@ topay_status topay_sense_commit(topay_ctx* c, int n, const int* map_ids) {
       for (int a = 0; a < 3; a++) S.dims[a] = b.desc.dims[a];
       max_cols = std::max(max_cols, (int)n2);
     }
-  if ((s = c->sense_io.ensure(sizeof(SenseOccSlot) * (size_t)n)) != TOPAY_OK) return s;
-  HIPCHK(h2d(c, c->sense_io.as<SenseOccSlot>(), (const SenseOccSlot*)ho.data(), (size_t)n));
-  HIPCHK(hipEventRecord(c->sense_ev[0], c->stream));
+  if ((s = c->sense.io.ensure(sizeof(SenseOccSlot) * (size_t)n)) != TOPAY_OK) return s;
+  HIPCHK(h2d(c, c->sense.io.as<SenseOccSlot>(), (const SenseOccSlot*)ho.data(), (size_t)n));
+  HIPCHK(tm.start(c->stream));
   const int bps = (max_cols + TOPAY_SENSE_BLOCK - 1) / TOPAY_SENSE_BLOCK;
-  hipLaunchKernelGGL(k_sense_occupancy, dim3((unsigned)((size_t)n * bps)), dim3(TOPAY_SENSE_BLOCK), 0, c->stream, (const SenseOccSlot*)c->sense_io.as<SenseOccSlot>(), bps);
+  hipLaunchKernelGGL(k_sense_occupancy, dim3((unsigned)((size_t)n * bps)), dim3(TOPAY_SENSE_BLOCK), 0, c->stream, (const SenseOccSlot*)c->sense.io.as<SenseOccSlot>(), bps);
   HIPCHK(hipGetLastError());
   for (const Run& r : runs) {
-    world_forget(c, r.first, r.n);
-    if ((s = build_fields_from_device(c, r.n, r.first, &c->sense[r.first].desc, base + r.o3, base + r.o2, base + r.o2c, false)) != TOPAY_OK) return s;
-    for (int i = 0; i < r.n; i++) c->sense[r.first + i].have_occ = true;
+    forget_occupancy(c, r.first, r.n);
+    if ((s = build_fields_from_device(c, r.n, r.first, &c->sense.slot[r.first].desc, base + r.o3, base + r.o2, base + r.o2c, false)) != TOPAY_OK) return s;
+    for (int i = 0; i < r.n; i++) c->sense.slot[r.first + i].have_occ = true;
   }
-  HIPCHK(hipEventRecord(c->sense_ev[1], c->stream));
+  HIPCHK(tm.stop(c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  return sense_elapsed(c, 3);
+  HIPCHK(tm.read(&c->sense.ms[SenseState::kCommit]));
+  return TOPAY_OK;
 }
 
 topay_status topay_sense_get(topay_ctx* c, int map_id, float* logodds, int* op_cnt, int* hit_cnt, int* batch_counter) {
-  if (!c || map_id < 0 || map_id >= TOPAY_MAX_MAPS) return TOPAY_ERR_INVALID_ARG;
-  if (map_id >= (int)c->sense.size() || !c->sense[map_id].have) return TOPAY_ERR_NO_MAP;
+  if (!c) return TOPAY_ERR_INVALID_ARG;
+  if (topay_status s = check_map_slots(c, 1, &map_id, 0, "topay_sense_get")) return s;
+  if (topay_status s = sense_check_beliefs(c, 1, &map_id, "topay_sense_get")) return s;
   HIPCHK(hipSetDevice(c->device));
-  const topay_ctx::SenseBelief& b = c->sense[map_id];
+  const SenseBelief& b = c->sense.slot[map_id];
   const size_t n3 = (size_t)b.desc.dims[0] * b.desc.dims[1] * b.desc.dims[2];
   if (logodds) HIPCHK(d2h_sync(c, logodds, (const float*)b.logodds, n3));
   if (op_cnt || hit_cnt) {
@@ -361,14 +332,14 @@ topay_status topay_sense_scan(topay_ctx* c, int n, const int* truth_map_ids, con
   const long long rays = (long long)n_az * n_el, total = rays * n;
   if (rays > (1 << 24) || total >= (1ll << 31) / 16) { set_err("topay_sense_scan: too many rays"); return TOPAY_ERR_INVALID_ARG; }
   if (points && (long long)cloud_cap < total) { set_err("topay_sense_scan: cloud_cap below n * n_az * n_el"); return TOPAY_ERR_INVALID_ARG; }
+  if (topay_status cs = check_map_slots(c, n, truth_map_ids, kMapResident, "topay_sense_scan")) return cs;
   std::vector<SenseScanSlot> hs((size_t)n);
   for (int k = 0; k < n; k++) {
     const int m = truth_map_ids[k];
-    if (m < 0 || m >= TOPAY_MAX_MAPS) return TOPAY_ERR_INVALID_ARG;
     SenseScanSlot& S = hs[(size_t)k];
     memset(&S, 0, sizeof(S));
-    S.occ3 = sense_truth_occ3(c, m, S.dims);
-    if (!S.occ3 || !c->have_map[m]) { set_err("topay_sense_scan: slot " + std::to_string(m) + " has no resident occupancy (topay_get_occupancy)"); return TOPAY_ERR_NO_MAP; }
+    S.occ3 = c->sense.has_occ(m) ? c->sense.occ3_of(m, S.dims) : c->world.occ3_of(m, S.dims);   // the last commit's grid, or the world generator's
+    if (!S.occ3) { set_err("topay_sense_scan: slot " + std::to_string(m) + " has no resident occupancy (topay_get_occupancy)"); return TOPAY_ERR_NO_MAP; }
     const DevMap& M = c->hmaps[m];
     for (int a = 0; a < 3; a++) S.origin[a] = M.origin[a];
     S.res = M.res;
@@ -379,28 +350,29 @@ topay_status topay_sense_scan(topay_ctx* c, int n, const int* truth_map_ids, con
   }
   HIPCHK(hipSetDevice(c->device));
   topay_status s;
-  if ((s = sense_events(c)) != TOPAY_OK) return s;
-  c->sense_scan_points = 0;
-  if ((s = c->sense_scan.ensure((size_t)total * sizeof(SensePoint))) != TOPAY_OK) return s;
-  if ((s = c->sense_io.ensure(sizeof(SenseScanSlot) * (size_t)n)) != TOPAY_OK) return s;
-  HIPCHK(h2d(c, c->sense_io.as<SenseScanSlot>(), (const SenseScanSlot*)hs.data(), (size_t)n));
-  HIPCHK(hipEventRecord(c->sense_ev[0], c->stream));
+  DevTimer& tm = c->sense.timer[SenseState::kScan];
+  c->sense.scan_points = 0;
+  if ((s = c->sense.scan.ensure((size_t)total * sizeof(SensePoint))) != TOPAY_OK) return s;
+  if ((s = c->sense.io.ensure(sizeof(SenseScanSlot) * (size_t)n)) != TOPAY_OK) return s;
+  HIPCHK(h2d(c, c->sense.io.as<SenseScanSlot>(), (const SenseScanSlot*)hs.data(), (size_t)n));
+  HIPCHK(tm.start(c->stream));
   const int bps = (int)((rays + TOPAY_SENSE_BLOCK - 1) / TOPAY_SENSE_BLOCK);
-  hipLaunchKernelGGL(k_sense_scan, dim3((unsigned)((size_t)n * bps)), dim3(TOPAY_SENSE_BLOCK), 0, c->stream, (const SenseScanSlot*)c->sense_io.as<SenseScanSlot>(), bps,
-                     n_az, n_el, fov, range, c->sense_scan.as<SensePoint>());
+  hipLaunchKernelGGL(k_sense_scan, dim3((unsigned)((size_t)n * bps)), dim3(TOPAY_SENSE_BLOCK), 0, c->stream, (const SenseScanSlot*)c->sense.io.as<SenseScanSlot>(), bps,
+                     n_az, n_el, fov, range, c->sense.scan.as<SensePoint>());
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->sense_ev[1], c->stream));
-  if (points) HIPCHK(d2h(c, points, (const float*)c->sense_scan.as<float>(), (size_t)total * 4));
+  HIPCHK(tm.stop(c->stream));
+  if (points) HIPCHK(d2h(c, points, (const float*)c->sense.scan.as<float>(), (size_t)total * 4));
   HIPCHK(hipStreamSynchronize(c->stream));
-  c->sense_scan_points = (size_t)total;
+  c->sense.scan_points = (size_t)total;
   if (cloud_off)
     for (int k = 0; k <= n; k++) cloud_off[k] = (int)(rays * k);
-  return sense_elapsed(c, 0);
+  HIPCHK(tm.read(&c->sense.ms[SenseState::kScan]));
+  return TOPAY_OK;
 }
 
 topay_status topay_sense_ms(topay_ctx* c, double ms[4]) {
   if (!c || !ms) return TOPAY_ERR_INVALID_ARG;
-  for (int k = 0; k < 4; k++) ms[k] = c->sense_ms[k];
+  for (int k = 0; k < 4; k++) ms[k] = c->sense.ms[k];
   return TOPAY_OK;
 }
 

@@ -1,10 +1,11 @@
-// Host side of the C-ABI, part 9: tracked trajectories (end_traj / global_traj of every robot slot), the safety sweep, the
-// endpoints of a replan and the replanning cycle (topay_track.h; Planner::safeCallback and replanCallback).
+// Host side of the C-ABI, part 9: tracked trajectories (end_traj / global_traj of every robot slot), the one check of the robot
+// slots an entry names, the safety sweep, the endpoints of a replan and the replanning cycle (topay_track.h;
+// Planner::safeCallback and replanCallback).
 
 #pragma once
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The store.  One arena (c->tr_arena) holds every tracked trajectory in the layout stated in topay_track.h; it grows by
+// The store.  One arena (TrackState::arena) holds every tracked trajectory in the layout stated in topay_track.h; it grows by
 // ragged offsets and keeps its contents.  A slot whose block is large enough for its next trajectory reuses it; one that is
 // not gets a new block and the old one is lost.  Blocks are sized to a power of two, so the lost blocks of a slot sum to
 // less than its last one: the arena is bounded by four times the largest need of every (slot, which), whatever the order
@@ -30,15 +31,15 @@ struct TrackPut {   // one trajectory on its way into the arena
 static topay_status track_commit_impl(topay_ctx* c, const std::vector<TrackPut>& puts, const double* s_dur, const double* s_coef, const double* s_start) {
   const size_t n = puts.size();
   if (n == 0) return TOPAY_OK;
-  if (c->tr_slots.empty()) c->tr_slots.resize(TOPAY_TRACK_SLOTS);
+  if (c->track.slots.empty()) c->track.slots.resize(TOPAY_TRACK_SLOTS);
   std::vector<topay::TrackDesc> dst(n);
   std::vector<long long> sp(n), ss(n), cap(n);
-  size_t used = c->tr_used;
+  size_t used = c->track.used;
   for (size_t k = 0; k < n; k++) {
     const TrackPut& p = puts[k];
     const long long num = (long long)std::floor(p.T / kTrackPanel);
     const long long need = topay::track_doubles(p.N, num);
-    const topay_ctx::TrackSlot& sl = c->tr_slots[p.robot];
+    const TrackSlot& sl = c->track.slots[p.robot];
     dst[k].N = p.N;
     dst[k].num = (int)num;
     if (sl.cap[p.w] >= need) { dst[k].off = sl.d[p.w].off; cap[k] = sl.cap[p.w]; }
@@ -50,20 +51,20 @@ static topay_status track_commit_impl(topay_ctx* c, const std::vector<TrackPut>&
     sp[k] = p.src_piece; ss[k] = p.src_start;
   }
   topay_status s;
-  if ((s = c->tr_arena.ensure_keep(c->stream, used * 8, c->tr_used * 8)) != TOPAY_OK) return s;
+  if ((s = c->track.arena.ensure_keep(c->stream, used * 8, c->track.used * 8)) != TOPAY_OK) return s;
   topay::TrackDesc* d_dst; long long *d_sp, *d_ss;
   auto lay = [&](Carver& k) { d_sp = k.take<long long>(n); d_ss = k.take<long long>(n); d_dst = k.take<topay::TrackDesc>(n); };
-  if ((s = c->tr_io.carve(lay)) != TOPAY_OK) return s;
+  if ((s = c->track.io.carve(lay)) != TOPAY_OK) return s;
   HIPCHK(h2d(c, d_sp, sp.data(), n));
   HIPCHK(h2d(c, d_ss, ss.data(), n));
   HIPCHK(h2d(c, d_dst, dst.data(), n));
   hipLaunchKernelGGL(topay::k_track_commit, dim3((unsigned)n), dim3(64), 0, c->stream, (int)n, (const topay::TrackDesc*)d_dst, (const long long*)d_sp,
-                     (const long long*)d_ss, s_dur, s_coef, s_start, c->tr_arena.as<double>());
+                     (const long long*)d_ss, s_dur, s_coef, s_start, c->track.arena.as<double>());
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
-  c->tr_used = used;
+  c->track.used = used;
   for (size_t k = 0; k < n; k++) {
-    topay_ctx::TrackSlot& sl = c->tr_slots[puts[k].robot];
+    TrackSlot& sl = c->track.slots[puts[k].robot];
     sl.d[puts[k].w] = dst[k];
     sl.cap[puts[k].w] = cap[k];
     sl.T[puts[k].w] = puts[k].T;
@@ -71,76 +72,71 @@ static topay_status track_commit_impl(topay_ctx* c, const std::vector<TrackPut>&
   return TOPAY_OK;
 }
 
-static bool track_robot_ok(int robot) { return robot >= 0 && robot < TOPAY_TRACK_SLOTS; }
-static bool track_robots_distinct(int n, const int* robots) {   // (every robots[k] in range)
-  std::vector<char> seen(TOPAY_TRACK_SLOTS, 0);
-  for (int k = 0; k < n; k++) {
-    if (seen[robots[k]]) return false;
+// What an entry asks of the robot slots it names (check_robot_slots).
+enum : unsigned {
+  kRobotDistinct = 1,   // every slot is named once
+  kRobotEndTraj = 2,    // ... has an end_traj
+  kRobotMpc = 4,        // ... a controller that was reset (topay_mpc_reset)
+  kRobotSim = 8         // ... a simulator that was reset (topay_sim_reset)
+};
+// The one check of robot slots: robots[0 .. n).  A slot out of range, named twice or never reset is TOPAY_ERR_INVALID_ARG, one
+// without an end_traj TOPAY_ERR_NO_TRAJ; the error text names the entry (`who`).
+static topay_status check_robot_slots(topay_ctx* c, int n, const int* robots, unsigned need, const char* who) {
+  std::vector<char> seen(need & kRobotDistinct ? TOPAY_TRACK_SLOTS : 0, 0);
+  for (int k = 0; k < n; k++)
+    if (robots[k] < 0 || robots[k] >= TOPAY_TRACK_SLOTS) { set_err(std::string(who) + ": robot slot out of range"); return TOPAY_ERR_INVALID_ARG; }
+  for (int k = 0; k < n && (need & kRobotDistinct); k++) {
+    if (seen[robots[k]]) { set_err(std::string(who) + ": a robot slot is named twice"); return TOPAY_ERR_INVALID_ARG; }
     seen[robots[k]] = 1;
   }
-  return true;
-}
-static const topay::TrackDesc* track_find(topay_ctx* c, int robot, int w) {
-  if (c->tr_slots.empty() || c->tr_slots[robot].d[w].N <= 0) return nullptr;
-  return &c->tr_slots[robot].d[w];
-}
-
-// The arguments every sweep / endpoint call checks: robot slots with an end_traj; map slots with distance fields.
-static topay_status track_check(topay_ctx* c, int n, const int* robots, const int* map_ids, const char* who) {
   for (int k = 0; k < n; k++) {
-    if (!track_robot_ok(robots[k])) { set_err(std::string(who) + ": robot slot out of range"); return TOPAY_ERR_INVALID_ARG; }
-    if (map_ids) {
-      const int m = map_ids[k];
-      if (m < 0 || m >= TOPAY_MAX_MAPS) return TOPAY_ERR_INVALID_ARG;
-      if (!c->have_map[m] || !c->hmaps[m].esdf2d || !c->hmaps[m].esdf3d) { set_err(std::string(who) + ": map slot " + std::to_string(m) + " has no fields"); return TOPAY_ERR_NO_MAP; }
-    }
+    const int r = robots[k];
+    const std::string slot = std::string(who) + ": robot slot " + std::to_string(r);
+    if ((need & kRobotEndTraj) && !c->track.find(r, 0)) { set_err(slot + " has no end_traj"); return TOPAY_ERR_NO_TRAJ; }
+    if ((need & kRobotMpc) && (c->mpc.have.empty() || !c->mpc.have[r])) { set_err(slot + " was never reset (topay_mpc_reset)"); return TOPAY_ERR_INVALID_ARG; }
+    if ((need & kRobotSim) && (c->mpc.sim_have.empty() || !c->mpc.sim_have[r])) { set_err(slot + " has no simulator (topay_sim_reset)"); return TOPAY_ERR_INVALID_ARG; }
   }
-  for (int k = 0; k < n; k++)
-    if (!track_find(c, robots[k], 0)) { set_err(std::string(who) + ": robot slot " + std::to_string(robots[k]) + " has no end_traj"); return TOPAY_ERR_NO_TRAJ; }
   return TOPAY_OK;
 }
 
 static topay_status track_safe_impl(topay_ctx* c, int n, const int* robots, const int* map_ids, int* safe, int* first_hit, double* hit) {
   const size_t N = (size_t)n;
   std::vector<topay::TrackDesc> desc(N);
-  for (int k = 0; k < n; k++) desc[k] = *track_find(c, robots[k], 0);
+  for (int k = 0; k < n; k++) desc[k] = *c->track.find(robots[k], 0);
   topay::TrackDesc* d_desc; int *d_mid, *d_safe, *d_fh; double* d_hit;
   auto lay = [&](Carver& k) {
     d_hit = k.take<double>(2 * N); d_desc = k.take<topay::TrackDesc>(N); d_mid = k.take<int>(N); d_safe = k.take<int>(N); d_fh = k.take<int>(2 * N);
   };
   topay_status s;
-  if ((s = c->tr_io.carve(lay)) != TOPAY_OK) return s;
+  if ((s = c->track.io.carve(lay)) != TOPAY_OK) return s;
   HIPCHK(h2d(c, d_desc, desc.data(), N));
   HIPCHK(h2d(c, d_mid, map_ids, N));
   if ((s = push_params(c)) != TOPAY_OK) return s;
   topay::TrackSafeArgs A;
-  A.n = n; A.desc = d_desc; A.arena = c->tr_arena.as<double>(); A.map_id = d_mid; A.safe = d_safe; A.first_hit = d_fh; A.hit = d_hit;
-  HIPCHK(hipEventRecord(c->ev0, c->stream));
+  A.n = n; A.desc = d_desc; A.arena = c->track.arena.as<double>(); A.map_id = d_mid; A.safe = d_safe; A.first_hit = d_fh; A.hit = d_hit;
+  HIPCHK(c->track.safe_timer.start(c->stream));
   hipLaunchKernelGGL(topay::k_track_safe, dim3((unsigned)n), dim3(64), 0, c->stream, A, (const DevMap*)c->dmaps.p);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev1, c->stream));
+  HIPCHK(c->track.safe_timer.stop(c->stream));
   if (safe) HIPCHK(d2h(c, safe, d_safe, N));
   if (first_hit) HIPCHK(d2h(c, first_hit, d_fh, 2 * N));
   if (hit) HIPCHK(d2h(c, hit, d_hit, 2 * N));
   HIPCHK(hipStreamSynchronize(c->stream));
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->tr_safe_ms = ms;
+  (void)c->track.safe_timer.read(&c->track.safe_ms);
   return TOPAY_OK;
 }
 
 static topay_status track_endpoints_impl(topay_ctx* c, int n, const int* robots, const double* t_replan, const double* t_begin, const double* global_goal,
                                          double budget, double horizon, double* start, double* start_v, double* goal, int* goal_source) {
   const size_t N = (size_t)n;
-  for (int k = 0; k < n; k++)
-    if (!(std::fabs(t_replan[k]) < 1.0e9 && t_begin[k] >= 0.0 && t_begin[k] < 1.0e9)) {   // (the walk along global_traj starts at t_begin)
-      set_err("topay_replan_inputs: the clocks must be finite, t_since_begin not negative");
-      return TOPAY_ERR_INVALID_ARG;
-    }
-  if (!(std::fabs(budget) < 1.0e9) || !(horizon >= 0.0)) return TOPAY_ERR_INVALID_ARG;
+  bool clocks = all_finite(t_replan, N) && all_finite(t_begin, N);
+  for (int k = 0; k < n; k++) clocks = clocks && t_begin[k] >= 0.0;   // (the walk along global_traj starts at t_begin)
+  if (!clocks) { set_err("topay_replan_inputs: the clocks must be finite, t_since_begin not negative"); return TOPAY_ERR_INVALID_ARG; }
+  if (!all_finite(&budget, 1) || !(horizon >= 0.0)) return TOPAY_ERR_INVALID_ARG;
   std::vector<topay::TrackDesc> de(N), dg(N);
   for (int k = 0; k < n; k++) {
-    de[k] = *track_find(c, robots[k], 0);
-    const topay::TrackDesc* g = track_find(c, robots[k], 1);
+    de[k] = *c->track.find(robots[k], 0);
+    const topay::TrackDesc* g = c->track.find(robots[k], 1);
     if (g) dg[k] = *g;
     else { dg[k].off = 0; dg[k].N = 0; dg[k].num = 0; }
   }
@@ -151,14 +147,14 @@ static topay_status track_endpoints_impl(topay_ctx* c, int n, const int* robots,
     d_de = k.take<topay::TrackDesc>(N); d_dg = k.take<topay::TrackDesc>(N); d_src = k.take<int>(N);
   };
   topay_status s;
-  if ((s = c->tr_io.carve(lay)) != TOPAY_OK) return s;
+  if ((s = c->track.io.carve(lay)) != TOPAY_OK) return s;
   HIPCHK(h2d(c, d_tr, t_replan, N));
   HIPCHK(h2d(c, d_tb, t_begin, N));
   HIPCHK(h2d(c, d_gg, global_goal, 10 * N));
   HIPCHK(h2d(c, d_de, de.data(), N));
   HIPCHK(h2d(c, d_dg, dg.data(), N));
   topay::TrackEndArgs A;
-  A.n = n; A.end_desc = d_de; A.glob_desc = d_dg; A.arena = c->tr_arena.as<double>(); A.t_replan = d_tr; A.t_begin = d_tb; A.global_goal = d_gg;
+  A.n = n; A.end_desc = d_de; A.glob_desc = d_dg; A.arena = c->track.arena.as<double>(); A.t_replan = d_tr; A.t_begin = d_tb; A.global_goal = d_gg;
   A.budget = budget; A.horizon = horizon; A.start = d_st; A.start_v = d_sv; A.goal = d_go; A.goal_source = d_src;
   hipLaunchKernelGGL(topay::k_track_endpoints, dim3((unsigned)n), dim3(64), 0, c->stream, A);
   HIPCHK(hipGetLastError());
@@ -194,7 +190,7 @@ extern "C" {
 
 topay_status topay_track_set(topay_ctx* c, int robot, int which, const double* start3, int n_pieces, const double* durations, const double* coeffs) {
   if (!c || !start3 || !durations || !coeffs) return TOPAY_ERR_INVALID_ARG;
-  if (!track_robot_ok(robot)) { set_err("topay_track_set: robot slot out of range"); return TOPAY_ERR_INVALID_ARG; }
+  if (topay_status cs = check_robot_slots(c, 1, &robot, 0, "topay_track_set")) return cs;
   if (which < 1 || which > 3) { set_err("topay_track_set: which must be 1 (end_traj), 2 (global_traj) or 3 (both)"); return TOPAY_ERR_INVALID_ARG; }
   if (n_pieces < 1 || n_pieces > TOPAY_MAX_N) { set_err("topay_track_set: 1..170 pieces"); return TOPAY_ERR_INVALID_ARG; }
   TrackPut p;
@@ -204,7 +200,7 @@ topay_status topay_track_set(topay_ctx* c, int robot, int which, const double* s
   const size_t N = (size_t)n_pieces;
   double *d_dur, *d_coef, *d_start;
   auto lay = [&](Carver& k) { d_dur = k.take<double>(N); d_coef = k.take<double>(N * kCoefPerPiece); d_start = k.take<double>(4); };
-  if (topay_status s = c->tr_stage.carve(lay); s != TOPAY_OK) return s;
+  if (topay_status s = c->track.stage.carve(lay); s != TOPAY_OK) return s;
   HIPCHK(h2d(c, d_dur, durations, N));
   HIPCHK(h2d(c, d_coef, coeffs, N * kCoefPerPiece));
   HIPCHK(h2d(c, d_start, start3, 3));
@@ -218,20 +214,18 @@ topay_status topay_track_commit_plan(topay_ctx* c, int n, const int* robots, con
   if (!c || n < 0 || (n > 0 && (!robots || !call_idx))) return TOPAY_ERR_INVALID_ARG;
   if (which < 1 || which > 3) { set_err("topay_track_commit_plan: which must be 1, 2 or 3"); return TOPAY_ERR_INVALID_ARG; }
   if (c->plan_store.empty()) { set_err("topay_track_commit_plan: no planning call has been run"); return TOPAY_ERR_NO_TRAJ; }
-  for (int k = 0; k < n; k++) {
-    if (!track_robot_ok(robots[k])) { set_err("topay_track_commit_plan: robot slot out of range"); return TOPAY_ERR_INVALID_ARG; }
-    if (!c->plan_store.has(call_idx[k])) return TOPAY_ERR_INVALID_ARG;
-  }
-  if (!track_robots_distinct(n, robots)) { set_err("topay_track_commit_plan: a robot slot is named twice"); return TOPAY_ERR_INVALID_ARG; }
+  if (topay_status cs = check_robot_slots(c, n, robots, kRobotDistinct, "topay_track_commit_plan")) return cs;
+  for (int k = 0; k < n; k++)
+    if (!c->plan_store.has(call_idx[k])) { set_err("topay_track_commit_plan: call " + std::to_string(call_idx[k]) + " is not in the plan store"); return TOPAY_ERR_INVALID_ARG; }
   HIPCHK(hipSetDevice(c->device));
   return track_commit_plan_impl(c, n, robots, call_idx, which, committed);
 }
 
 topay_status topay_track_get(topay_ctx* c, int robot, int which, int cap_pieces, int* n_pieces, double* start3, double* durations, double* coeffs) {
   if (!c || !n_pieces || cap_pieces < 0) return TOPAY_ERR_INVALID_ARG;
-  if (!track_robot_ok(robot)) { set_err("topay_track_get: robot slot out of range"); return TOPAY_ERR_INVALID_ARG; }
+  if (topay_status cs = check_robot_slots(c, 1, &robot, 0, "topay_track_get")) return cs;
   if (which < 1 || which > 2) { set_err("topay_track_get: which must be 1 (end_traj) or 2 (global_traj)"); return TOPAY_ERR_INVALID_ARG; }
-  const topay::TrackDesc* D = track_find(c, robot, which - 1);
+  const topay::TrackDesc* D = c->track.find(robot, which - 1);
   *n_pieces = D ? D->N : 0;
   if (!D) return TOPAY_OK;
   if (!start3 && !durations && !coeffs) return TOPAY_OK;
@@ -239,7 +233,7 @@ topay_status topay_track_get(topay_ctx* c, int robot, int which, int cap_pieces,
   HIPCHK(hipSetDevice(c->device));
   const int N = D->N, rows = 6 * N;
   std::vector<double> h(4 + (size_t)N + (size_t)N * kCoefPerPiece);
-  HIPCHK(d2h_sync(c, h.data(), c->tr_arena.as<double>() + D->off, h.size()));
+  HIPCHK(d2h_sync(c, h.data(), c->track.arena.as<double>() + D->off, h.size()));
   if (start3) memcpy(start3, h.data(), 24);
   if (durations) memcpy(durations, h.data() + 4, (size_t)N * 8);
   if (coeffs) {
@@ -254,23 +248,25 @@ topay_status topay_track_get(topay_ctx* c, int robot, int which, int cap_pieces,
 
 topay_status topay_track_clear(topay_ctx* c, int robot) {
   if (!c) return TOPAY_ERR_INVALID_ARG;
-  if (!track_robot_ok(robot)) { set_err("topay_track_clear: robot slot out of range"); return TOPAY_ERR_INVALID_ARG; }
-  if (!c->tr_slots.empty())
-    for (int w = 0; w < 2; w++) c->tr_slots[robot].d[w].N = 0;   // (the block stays the slot's: its next trajectory may reuse it)
+  if (topay_status cs = check_robot_slots(c, 1, &robot, 0, "topay_track_clear")) return cs;
+  if (!c->track.slots.empty())
+    for (int w = 0; w < 2; w++) c->track.slots[robot].d[w].N = 0;   // (the block stays the slot's: its next trajectory may reuse it)
   return TOPAY_OK;
 }
 
 topay_status topay_track_safe(topay_ctx* c, int n, const int* robots, const int* map_ids, int* safe, int* first_hit, double* hit) {
   if (!c || n <= 0 || !robots || !map_ids) return TOPAY_ERR_INVALID_ARG;
-  if (topay_status s = track_check(c, n, robots, map_ids, "topay_track_safe"); s != TOPAY_OK) return s;
+  if (topay_status s = check_robot_slots(c, n, robots, 0, "topay_track_safe")) return s;   // (in range, then the maps, then the trajectories)
+  if (topay_status s = check_map_slots(c, n, map_ids, kMapResident | kMap2d | kMap3d, "topay_track_safe")) return s;
+  if (topay_status s = check_robot_slots(c, n, robots, kRobotEndTraj, "topay_track_safe")) return s;
   HIPCHK(hipSetDevice(c->device));
-  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }
+  if (topay_status ws = wait_pending(c)) return ws;
   return track_safe_impl(c, n, robots, map_ids, safe, first_hit, hit);
 }
 
 topay_status topay_track_safe_ms(topay_ctx* c, double* ms) {
   if (!c || !ms) return TOPAY_ERR_INVALID_ARG;
-  *ms = c->tr_safe_ms;
+  *ms = c->track.safe_ms;
   return TOPAY_OK;
 }
 
@@ -278,7 +274,7 @@ topay_status topay_replan_inputs(topay_ctx* c, int n, const int* robots, const d
                                  const double* global_goal, double planning_budget, double planning_horizon, double* start, double* start_v,
                                  double* goal, int* goal_source) {
   if (!c || n <= 0 || !robots || !t_since_replan || !t_since_begin || !global_goal || !start || !start_v || !goal || !goal_source) return TOPAY_ERR_INVALID_ARG;
-  if (topay_status s = track_check(c, n, robots, nullptr, "topay_replan_inputs"); s != TOPAY_OK) return s;
+  if (topay_status s = check_robot_slots(c, n, robots, kRobotEndTraj, "topay_replan_inputs")) return s;
   HIPCHK(hipSetDevice(c->device));
   return track_endpoints_impl(c, n, robots, t_since_replan, t_since_begin, global_goal, planning_budget, planning_horizon, start, start_v, goal, goal_source);
 }
@@ -289,10 +285,11 @@ topay_status topay_replan_calls(topay_ctx* c, int n, const int* robots, const in
                                 double* endpoints, int* plan_result, int* plan_candidates) {
   if (!c || n <= 0 || !robots || !map_ids || !t_since_replan || !t_since_begin || !global_goal || !status) return TOPAY_ERR_INVALID_ARG;
   topay_status s;
-  if ((s = track_check(c, n, robots, map_ids, "topay_replan_calls")) != TOPAY_OK) return s;
-  if (!track_robots_distinct(n, robots)) { set_err("topay_replan_calls: a robot slot is named twice"); return TOPAY_ERR_INVALID_ARG; }
+  if ((s = check_robot_slots(c, n, robots, 0, "topay_replan_calls")) != TOPAY_OK) return s;   // (in range, then the maps, then the trajectories)
+  if ((s = check_map_slots(c, n, map_ids, kMapResident | kMap2d | kMap3d, "topay_replan_calls")) != TOPAY_OK) return s;
+  if ((s = check_robot_slots(c, n, robots, kRobotEndTraj | kRobotDistinct, "topay_replan_calls")) != TOPAY_OK) return s;
   HIPCHK(hipSetDevice(c->device));
-  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }
+  if (topay_status ws = wait_pending(c)) return ws;
   const size_t N = (size_t)n;
   // ---- 1. safety sweep (safeCallback) of every robot against its map of now
   std::vector<int> safe(N);

@@ -33,37 +33,16 @@ static void world_map_desc(const topay_world_params_t* p, topay_map_desc_t* d) {
 // a start / goal pair 3 m apart has to fit the square the ends are drawn from (the harness would draw for ever)
 static bool world_fits_start_goal(double size_xy) { return (size_xy - 4.0) * 1.4142135623730951 > 3.0; }
 
-static topay_status world_events(topay_ctx* c) {
-  for (hipEvent_t& e : c->world_ev)
-    if (!e) HIPCHK(hipEventCreate(&e));
-  return TOPAY_OK;
-}
-// events 0..3 bound generation, rasterisation and the fields; 4 and 5 the sampler's launch
-static topay_status world_stage_times(topay_ctx* c) {
-  for (int k = 0; k < 3; k++) {
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, c->world_ev[k], c->world_ev[k + 1]));
-    c->world_ms[k] = ms;
-  }
-  c->world_ms[3] = 0.0;
-  return TOPAY_OK;
-}
-static topay_status world_sampling_time(topay_ctx* c) {
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, c->world_ev[4], c->world_ev[5]));
-  c->world_ms[3] = ms;
-  return TOPAY_OK;
-}
-
 // generation, rasterisation and the fields of n maps; the seeds and keep-outs are host arrays
 static topay_status world_generate(topay_ctx* c, int n, int first_map_id, const topay_world_params_t* p, const unsigned long long* seed,
-                                   const double* keepouts_xy, int* status) {
+                                   const double* keepouts_xy, int* status, const char* who) {
   topay_status s;
   if ((s = world_check_params(p)) != TOPAY_OK) return s;
-  if (!c || !seed || n <= 0 || first_map_id < 0 || first_map_id + n > TOPAY_MAX_MAPS) return TOPAY_ERR_INVALID_ARG;
+  if (!c || !seed) return TOPAY_ERR_INVALID_ARG;
+  if ((s = check_map_range(first_map_id, n, who)) != TOPAY_OK) return s;
   HIPCHK(hipSetDevice(c->device));
-  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }
-  if ((s = world_events(c)) != TOPAY_OK) return s;
+  if (topay_status ws = wait_pending(c)) return ws;
+  WorldState& W = c->world;
   topay_map_desc_t desc;
   world_map_desc(p, &desc);
   const int nx = desc.dims[0], ny = desc.dims[1], nz = desc.dims[2];
@@ -96,33 +75,34 @@ static topay_status world_generate(topay_ctx* c, int n, int first_map_id, const 
 
   unsigned long long* d_seed; double* d_keep; int *d_count, *d_status;
   auto lay_io = [&](Carver& k) { d_seed = k.take<unsigned long long>(M); d_keep = k.take<double>(M * 4); d_count = k.take<int>(M); d_status = k.take<int>(M); };
-  if ((s = c->world_io.carve(lay_io)) != TOPAY_OK) return s;
-  if ((s = c->world_prims.ensure(M * (size_t)G.prim_cap * sizeof(WorldPrim))) != TOPAY_OK) return s;
+  if ((s = c->world.io.carve(lay_io)) != TOPAY_OK) return s;
+  if ((s = c->world.prims.ensure(M * (size_t)G.prim_cap * sizeof(WorldPrim))) != TOPAY_OK) return s;
   signed char *d_occ3, *d_occ2, *d_occ2c;
   // (each grid starts on a 16-byte boundary: the first path stores 16 bytes at a time)
-  const size_t b3 = (M * n3 + 15) & ~(size_t)15, b2 = (M * n2 + 15) & ~(size_t)15;
-  for (int m = first_map_id; m < first_map_id + n && m < (int)c->sense.size(); m++) c->sense[m].have_occ = false;   // (topay_sense_commit's grids)
-  c->world_n = 0;
-  if ((s = c->world_occ.ensure(b3 + 2 * b2)) != TOPAY_OK) return s;
-  d_occ3 = c->world_occ.as<signed char>();
+  const size_t b3 = WorldState::pad16(M * n3), b2 = WorldState::pad16(M * n2);
+  c->sense.forget(first_map_id, n);   // (topay_sense_commit's grids)
+  c->world.n = 0;
+  if ((s = c->world.occ.ensure(b3 + 2 * b2)) != TOPAY_OK) return s;
+  d_occ3 = c->world.occ.as<signed char>();
   d_occ2 = d_occ3 + b3;
   d_occ2c = d_occ2 + b2;
-  WorldPrim* d_prims = c->world_prims.as<WorldPrim>();
+  WorldPrim* d_prims = c->world.prims.as<WorldPrim>();
   HIPCHK(h2d(c, d_seed, seed, M));
   if (keep) HIPCHK(h2d(c, d_keep, keepouts_xy, M * 4));
 
-  HIPCHK(hipEventRecord(c->world_ev[0], c->stream));
+  HIPCHK(W.timer[WorldState::kGen].start(c->stream));
   {
     const size_t lb = (size_t)(312 + 6 * G.box_cap + 16) * sizeof(double);
     HIPCHK(hipFuncSetAttribute((const void*)k_world_generate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
     hipLaunchKernelGGL(k_world_generate, dim3((unsigned)n), dim3(TOPAY_WAVE), lb, c->stream, G, n, (const unsigned long long*)d_seed,
                        keep ? (const double*)d_keep : (const double*)nullptr, d_prims, d_count, d_status);
   }
-  HIPCHK(hipEventRecord(c->world_ev[1], c->stream));
+  HIPCHK(W.timer[WorldState::kGen].stop(c->stream));
+  HIPCHK(W.timer[WorldState::kRaster].start(c->stream));
   // The rule that picks the path: masks in LDS when the map has at most 32 layers, a multiple of 16 columns (whole 16-byte
   // stores, every map of the batch aligned) and masks of at most 150 KB; byte stores otherwise.
   const size_t lb = world_lds_bytes(nx, ny, nz);
-  const bool lds_path = c->world_force_path != 2 && nz <= 32 && n2 % 16 == 0 && lb <= 150 * 1024;
+  const bool lds_path = c->world.force_path != 2 && nz <= 32 && n2 % 16 == 0 && lb <= 150 * 1024;
   if (lds_path) {
     auto kern = nz <= 16 ? k_world_raster_lds<16> : k_world_raster_lds<32>;
     HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
@@ -132,42 +112,34 @@ static topay_status world_generate(topay_ctx* c, int n, int first_map_id, const 
     hipLaunchKernelGGL(k_world_raster_bytes, dim3((unsigned)(M * (size_t)G.prim_cap)), dim3(TOPAY_WAVE), 0, c->stream, R, (const WorldPrim*)d_prims,
                        (const int*)d_count, d_occ3, d_occ2, d_occ2c);
   }
-  c->world_path = lds_path ? 1 : 2;
+  c->world.path = lds_path ? 1 : 2;
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->world_ev[2], c->stream));
+  HIPCHK(W.timer[WorldState::kRaster].stop(c->stream));
+  HIPCHK(W.timer[WorldState::kFields].start(c->stream));
   if ((s = build_fields_from_device(c, n, first_map_id, &desc, d_occ3, d_occ2, d_occ2c, false)) != TOPAY_OK) return s;
-  HIPCHK(hipEventRecord(c->world_ev[3], c->stream));
+  HIPCHK(W.timer[WorldState::kFields].stop(c->stream));
   if (status) HIPCHK(d2h(c, status, (const int*)d_status, M));
   HIPCHK(hipStreamSynchronize(c->stream));
-  if ((s = world_stage_times(c)) != TOPAY_OK) return s;
-  c->world_first = first_map_id;
-  c->world_n = n;
-  for (int i = 0; i < 3; i++) c->world_dims[i] = desc.dims[i];
-  c->world_prims.release();
+  for (int k = WorldState::kGen; k <= WorldState::kFields; k++) HIPCHK(W.timer[k].read(&W.ms[k]));
+  W.ms[WorldState::kSample] = 0.0;
+  c->world.first = first_map_id;
+  c->world.n = n;
+  for (int i = 0; i < 3; i++) c->world.dims[i] = desc.dims[i];
+  c->world.prims.release();
   return TOPAY_OK;
 }
 
-// every slot a sampler reads is resident
-static topay_status world_check_slots(topay_ctx* c, int n, const int* map_ids) {
-  for (int i = 0; i < n; i++) {
-    const int m = map_ids ? map_ids[i] : 0;
-    if (m < 0 || m >= TOPAY_MAX_MAPS) return TOPAY_ERR_INVALID_ARG;
-    if (!c->have_map[m]) return TOPAY_ERR_NO_MAP;
-  }
-  return TOPAY_OK;
-}
-
-// The samplers' bodies: host arrays in and out, the slots checked by the caller.  timed: events 4 and 5 are recorded around the
-// launch alone (not the copies) and the sampling stage time is kept.
+// The samplers' bodies: host arrays in and out, the slots checked by the caller.  timed: the sampling stopwatch runs around the
+// launch alone (not the copies) and its time is kept.
 static topay_status world_sample_arm(topay_ctx* c, int n, const int* map_ids, const unsigned long long* seed, int max_tries, double* states, int* ok,
                                      int* tries, bool timed) {
   topay_status s;
   HIPCHK(hipSetDevice(c->device));
-  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }
+  if (topay_status ws = wait_pending(c)) return ws;
   const size_t N = (size_t)n;
   unsigned long long* d_seed; double* d_st; int *d_mid, *d_ok, *d_tr;
   auto lay = [&](Carver& k) { d_seed = k.take<unsigned long long>(N); d_st = k.take<double>(N * 10); d_mid = k.take<int>(N); d_ok = k.take<int>(N); d_tr = k.take<int>(N); };
-  if ((s = c->world_io.carve(lay)) != TOPAY_OK) return s;
+  if ((s = c->world.io.carve(lay)) != TOPAY_OK) return s;
   std::vector<int> mid(N, 0);
   if (map_ids) mid.assign(map_ids, map_ids + n);
   HIPCHK(h2d(c, d_seed, seed, N));
@@ -175,42 +147,44 @@ static topay_status world_sample_arm(topay_ctx* c, int n, const int* map_ids, co
   HIPCHK(h2d(c, d_mid, (const int*)mid.data(), N));
   if ((s = push_params(c)) != TOPAY_OK) return s;
   const int bs = TOPAY_WORLD_SAMPLER_LANES;
-  if (timed) HIPCHK(hipEventRecord(c->world_ev[4], c->stream));
+  if (timed) HIPCHK(c->world.timer[WorldState::kSample].start(c->stream));
   hipLaunchKernelGGL(k_world_sample_arm, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), (size_t)bs * 312 * 8, c->stream, (const DevMap*)c->dmaps.p, n,
                      (const int*)d_mid, (const unsigned long long*)d_seed, max_tries > 0 ? max_tries : 2000, d_st, d_ok, d_tr);
   HIPCHK(hipGetLastError());
-  if (timed) HIPCHK(hipEventRecord(c->world_ev[5], c->stream));
+  if (timed) HIPCHK(c->world.timer[WorldState::kSample].stop(c->stream));
   HIPCHK(d2h(c, states, (const double*)d_st, N * 10));
   HIPCHK(d2h(c, ok, (const int*)d_ok, N));
   if (tries) HIPCHK(d2h(c, tries, (const int*)d_tr, N));
   HIPCHK(hipStreamSynchronize(c->stream));
-  return timed ? world_sampling_time(c) : TOPAY_OK;
+  if (timed) HIPCHK(c->world.timer[WorldState::kSample].read(&c->world.ms[WorldState::kSample]));
+  return TOPAY_OK;
 }
 static topay_status world_sample_scenarios(topay_ctx* c, int n, const int* map_ids, const unsigned long long* seed, double* start, double* goal, int* ok,
                                            bool timed) {
   topay_status s;
   HIPCHK(hipSetDevice(c->device));
-  if (c->pending) { topay_status ws = topay_synchronize(c); if (ws != TOPAY_OK) return ws; }
+  if (topay_status ws = wait_pending(c)) return ws;
   const size_t N = (size_t)n;
   unsigned long long* d_seed; double *d_s, *d_g; int *d_mid, *d_ok;
   auto lay = [&](Carver& k) { d_seed = k.take<unsigned long long>(N); d_s = k.take<double>(N * 10); d_g = k.take<double>(N * 10); d_mid = k.take<int>(N); d_ok = k.take<int>(N); };
-  if ((s = c->world_io.carve(lay)) != TOPAY_OK) return s;
+  if ((s = c->world.io.carve(lay)) != TOPAY_OK) return s;
   std::vector<int> mid(N, 0);
   if (map_ids) mid.assign(map_ids, map_ids + n);
   HIPCHK(h2d(c, d_seed, seed, N));
   HIPCHK(h2d(c, d_mid, (const int*)mid.data(), N));
   if ((s = push_params(c)) != TOPAY_OK) return s;
   const int bs = TOPAY_WORLD_SAMPLER_LANES;
-  if (timed) HIPCHK(hipEventRecord(c->world_ev[4], c->stream));
+  if (timed) HIPCHK(c->world.timer[WorldState::kSample].start(c->stream));
   hipLaunchKernelGGL(k_world_sample_scenario, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), (size_t)bs * 312 * 8, c->stream, (const DevMap*)c->dmaps.p, n,
                      (const int*)d_mid, (const unsigned long long*)d_seed, d_s, d_g, d_ok);
   HIPCHK(hipGetLastError());
-  if (timed) HIPCHK(hipEventRecord(c->world_ev[5], c->stream));
+  if (timed) HIPCHK(c->world.timer[WorldState::kSample].stop(c->stream));
   HIPCHK(d2h(c, start, (const double*)d_s, N * 10));
   HIPCHK(d2h(c, goal, (const double*)d_g, N * 10));
   HIPCHK(d2h(c, ok, (const int*)d_ok, N));
   HIPCHK(hipStreamSynchronize(c->stream));
-  return timed ? world_sampling_time(c) : TOPAY_OK;
+  if (timed) HIPCHK(c->world.timer[WorldState::kSample].read(&c->world.ms[WorldState::kSample]));
+  return TOPAY_OK;
 }
 
 extern "C" {
@@ -236,50 +210,42 @@ topay_status topay_world_default_params(int kind, topay_world_params_t* p) {
 topay_status topay_generate_worlds(topay_ctx* c, int n, int first_map_id, const topay_world_params_t* params, const unsigned long long* seed,
                                    const double* keepouts_xy, int* status) {
   if (!c) return TOPAY_ERR_INVALID_ARG;
-  return world_generate(c, n, first_map_id, params, seed, keepouts_xy, status);
+  return world_generate(c, n, first_map_id, params, seed, keepouts_xy, status, "topay_generate_worlds");
 }
 
 topay_status topay_get_occupancy(topay_ctx* c, int map_id, signed char* occ2d, signed char* occ2d_critical, signed char* occ3d) {
   if (!c) return TOPAY_ERR_INVALID_ARG;
-  if (map_id >= 0 && map_id < (int)c->sense.size() && c->sense[map_id].have_occ) {   // a slot of the last topay_sense_commit
-    const topay_ctx::SenseBelief& b = c->sense[map_id];
-    HIPCHK(hipSetDevice(c->device));
-    const size_t n2 = (size_t)b.desc.dims[0] * b.desc.dims[1], n3 = n2 * b.desc.dims[2];
-    const signed char* base = c->sense_occ.as<signed char>();
-    if (occ3d) HIPCHK(d2h_sync(c, occ3d, base + b.occ3_off, n3));
-    if (occ2d) HIPCHK(d2h_sync(c, occ2d, base + b.occ2_off, n2));
-    if (occ2d_critical) HIPCHK(d2h_sync(c, occ2d_critical, base + b.occ2c_off, n2));
-    return TOPAY_OK;
-  }
-  if (map_id < c->world_first || map_id >= c->world_first + c->world_n || !c->world_occ.p) return TOPAY_ERR_NO_MAP;
+  // a slot of the last topay_sense_commit, or of the last world generation
+  int dims[3];
+  const bool sensed = c->sense.has_occ(map_id);
+  const signed char* o3 = sensed ? c->sense.occ3_of(map_id, dims) : c->world.occ3_of(map_id, dims);
+  if (!o3) { set_err("topay_get_occupancy: map slot " + std::to_string(map_id) + " has no resident occupancy grids"); return TOPAY_ERR_NO_MAP; }
   HIPCHK(hipSetDevice(c->device));
-  const size_t n2 = (size_t)c->world_dims[0] * c->world_dims[1], n3 = n2 * c->world_dims[2], M = (size_t)c->world_n, k = (size_t)(map_id - c->world_first);
-  const size_t b3 = (M * n3 + 15) & ~(size_t)15, b2 = (M * n2 + 15) & ~(size_t)15;
-  const signed char* base = c->world_occ.as<signed char>();
-  if (occ3d) HIPCHK(d2h_sync(c, occ3d, base + k * n3, n3));
-  if (occ2d) HIPCHK(d2h_sync(c, occ2d, base + b3 + k * n2, n2));
-  if (occ2d_critical) HIPCHK(d2h_sync(c, occ2d_critical, base + b3 + b2 + k * n2, n2));
+  const size_t n2 = (size_t)dims[0] * dims[1], n3 = n2 * dims[2];
+  if (occ3d) HIPCHK(d2h_sync(c, occ3d, o3, n3));
+  if (occ2d) HIPCHK(d2h_sync(c, occ2d, sensed ? c->sense.occ2_of(map_id, false) : c->world.occ2_of(map_id, false), n2));
+  if (occ2d_critical) HIPCHK(d2h_sync(c, occ2d_critical, sensed ? c->sense.occ2_of(map_id, true) : c->world.occ2_of(map_id, true), n2));
   return TOPAY_OK;
 }
 
 topay_status topay_world_last_path(topay_ctx* c, int* path) {
   if (!c || !path) return TOPAY_ERR_INVALID_ARG;
-  *path = c->world_path;
+  *path = c->world.path;
   return TOPAY_OK;
 }
 topay_status topay_world_test_path(topay_ctx* c, int path) {
   if (!c || (path != 0 && path != 2)) return TOPAY_ERR_INVALID_ARG;
-  c->world_force_path = path;
+  c->world.force_path = path;
   return TOPAY_OK;
 }
 topay_status topay_world_test_max_tries(topay_ctx* c, int max_tries) {
   if (!c || max_tries < 0) return TOPAY_ERR_INVALID_ARG;
-  c->world_max_tries = max_tries;
+  c->world.max_tries = max_tries;
   return TOPAY_OK;
 }
 topay_status topay_world_stage_ms(topay_ctx* c, double ms[4]) {
   if (!c || !ms) return TOPAY_ERR_INVALID_ARG;
-  for (int k = 0; k < 4; k++) ms[k] = c->world_ms[k];
+  for (int k = 0; k < 4; k++) ms[k] = c->world.ms[k];
   return TOPAY_OK;
 }
 
@@ -299,14 +265,14 @@ topay_status topay_sample_arm(topay_ctx* c, int n, const int* map_ids, const uns
                               int* tries) {
   if (!c || n <= 0 || !seed || !states || !ok) return TOPAY_ERR_INVALID_ARG;
   topay_status s;
-  if ((s = world_check_slots(c, n, map_ids)) != TOPAY_OK) return s;
+  if ((s = check_map_slots(c, n, map_ids, kMapResident, "topay_sample_arm")) != TOPAY_OK) return s;
   return world_sample_arm(c, n, map_ids, seed, max_tries, states, ok, tries, false);
 }
 
 topay_status topay_sample_scenarios(topay_ctx* c, int n, const int* map_ids, const unsigned long long* seed, double* start, double* goal, int* ok) {
   if (!c || n <= 0 || !seed || !start || !goal || !ok) return TOPAY_ERR_INVALID_ARG;
   topay_status s;
-  if ((s = world_check_slots(c, n, map_ids)) != TOPAY_OK) return s;
+  if ((s = check_map_slots(c, n, map_ids, kMapResident, "topay_sample_scenarios")) != TOPAY_OK) return s;
   for (int i = 0; i < n; i++) {
     const DevMap& m = c->hmaps[map_ids ? map_ids[i] : 0];
     if (!world_fits_start_goal(m.max_b[0] - m.min_b[0]) || !world_fits_start_goal(m.max_b[1] - m.min_b[1])) {
@@ -319,8 +285,9 @@ topay_status topay_sample_scenarios(topay_ctx* c, int n, const int* map_ids, con
 
 topay_status topay_generate_episodes(topay_ctx* c, int n, int first_map_id, const topay_world_params_t* params, const unsigned long long* seed,
                                      const int* attempt, double* start, double* goal, int* status) {
-  if (!c || !params || !seed || !start || !goal || !status || n <= 0 || first_map_id < 0 || first_map_id + n > TOPAY_MAX_MAPS) return TOPAY_ERR_INVALID_ARG;
+  if (!c || !params || !seed || !start || !goal || !status) return TOPAY_ERR_INVALID_ARG;
   topay_status s;
+  if ((s = check_map_range(first_map_id, n, "topay_generate_episodes")) != TOPAY_OK) return s;
   if ((s = world_check_params(params)) != TOPAY_OK) return s;
   if (!world_fits_start_goal(params->size_xy)) { set_err("topay_generate_episodes: the map is too small for a start and a goal 3 m apart"); return TOPAY_ERR_INVALID_ARG; }
   const size_t N = (size_t)n;
@@ -339,7 +306,7 @@ topay_status topay_generate_episodes(topay_ctx* c, int n, int first_map_id, cons
     keep.resize(4 * N);
     for (size_t i = 0; i < N; i++) { keep[4 * i] = s3[3 * i]; keep[4 * i + 1] = s3[3 * i + 1]; keep[4 * i + 2] = g3[3 * i]; keep[4 * i + 3] = g3[3 * i + 1]; }
   }
-  if ((s = world_generate(c, n, first_map_id, params, sd.data(), params->kind == 0 ? keep.data() : nullptr, nullptr)) != TOPAY_OK) return s;
+  if ((s = world_generate(c, n, first_map_id, params, sd.data(), params->kind == 0 ? keep.data() : nullptr, nullptr, "topay_generate_episodes")) != TOPAY_OK) return s;
   if (params->kind == 1) return world_sample_scenarios(c, n, mid.data(), sd.data(), start, goal, status, true);
   // tables: both arms in one launch, goal states first (instances i and n + i share map i)
   std::vector<double> st(20 * N, 0.0);
@@ -348,7 +315,7 @@ topay_status topay_generate_episodes(topay_ctx* c, int n, int first_map_id, cons
     for (int k = 0; k < 3; k++) { st[10 * i + k] = g3[3 * i + k]; st[10 * (N + i) + k] = s3[3 * i + k]; }
     mid2[i] = mid2[N + i] = mid[i];
   }
-  if ((s = world_sample_arm(c, 2 * n, mid2.data(), arm_seed.data(), c->world_max_tries, st.data(), ok.data(), nullptr, true)) != TOPAY_OK) return s;
+  if ((s = world_sample_arm(c, 2 * n, mid2.data(), arm_seed.data(), c->world.max_tries, st.data(), ok.data(), nullptr, true)) != TOPAY_OK) return s;
   for (size_t i = 0; i < N; i++) {
     for (int k = 0; k < 10; k++) { goal[10 * i + k] = st[10 * i + k]; start[10 * i + k] = st[10 * (N + i) + k]; }
     status[i] = ok[i] && ok[N + i] ? 1 : 0;
