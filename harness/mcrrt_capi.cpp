@@ -243,10 +243,17 @@ int wl_pm_update(void* h, int n, const float* xyzi, const double* sensor3, const
 }
 void wl_pm_get(void* h, float* logodds, int* op_cnt, int* hit_cnt, int* batch_counter) {
   const prob_map::ProbMap& m = *(prob_map::ProbMap*)h;
-  if (logodds) memcpy(logodds, m.occupancy_buffer.data(), m.occupancy_buffer.size() * sizeof(float));
-  if (op_cnt) memcpy(op_cnt, m.operation_cnt.data(), m.operation_cnt.size() * sizeof(int));
-  if (hit_cnt) memcpy(hit_cnt, m.hit_cnt.data(), m.hit_cnt.size() * sizeof(int));
+  if (logodds) m.unring(m.occupancy_buffer, logodds);
+  if (op_cnt) m.unring(m.operation_cnt, op_cnt);
+  if (hit_cnt) m.unring(m.hit_cnt, hit_cnt);
   if (batch_counter) *batch_counter = m.batch_update_counter;
+}
+// the slide of one sensor position (ProbMap::slide); shift3 receives the voxels the window moved by, origin3 the grid's origin after it
+int wl_pm_slide(void* h, const double* sensor3, double threshold, int slide_z, int* shift3, double* origin3) {
+  prob_map::ProbMap& m = *(prob_map::ProbMap*)h;
+  const int st = m.slide(sensor3, threshold, slide_z != 0, shift3);
+  for (int a = 0; a < 3; a++) origin3[a] = m.origin[a];
+  return st;
 }
 void wl_pm_occupancy(void* h, const prob_map::Params* params, int8_t* occ2d, int8_t* occ2d_critical, int8_t* occ3d) {
   ((prob_map::ProbMap*)h)->occupancy(prob_map::logit(params->p_occ), params->chassis_height, occ2d, occ2d_critical, occ3d);

@@ -9,15 +9,21 @@
 //   RayCaster::setInput / step        src/rog_map/include/utils/raycaster.cpp:65-192 (ORIGIN_AT_CORNER, CMakeLists.txt:14)
 //   lineBoxIntersectPoint             src/rog_map/include/utils/common_lib.hpp:148-170
 //   logit                             src/rog_map/include/rog_map/rog_map_core/config.hpp:229-235
-// Configuration: raycasting on, no sliding window (the local map is the grid given to reset), no ESDF, no frontiers, no inflation.
+//   SlidingMap::mapSliding            src/rog_map/src/rog_map/sliding_map.cpp:113-166, clearMemoryOutOfMap 96-111
+//   the two triggers of a slide       prob_map.cpp:306-311, 324-328
+// Configuration: raycasting on, no ESDF, no frontiers, no inflation.  The sliding window is a step of its own (slide): the local map
+// is the grid given to reset until then.  As in the reference the buffers are addressed as a ring (getLocalIndexHash of the index
+// modulo the size, sliding_map.cpp:168-173, 205-): a slide clears the slabs that leave and moves the origin, no voxel is copied.
 // Every position is moved into the grid's frame first (u = p - origin) and the reference's code runs on u.  The first-frame clearing
 // of a sphere of raycast_range_min (356-372) is not restated: range_min is 0.
 // This is the checker only; nothing on the product path includes it.  Its parity with rog_map itself is not pinned (rog_map needs
 // Eigen, PCL and ROS).  The range sensor at the end is not a restatement; its sin / cos are the library's deterministic ones
 // (FreeBSD msun k_sin / k_cos with a two-step Cody-Waite reduction), restated so that a ray's direction has the library's bits.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <queue>
@@ -88,6 +94,7 @@ inline Vec3 normalized(const Vec3& d) {   // Eigen's: v / sqrt(squaredNorm) when
 struct ProbMap {
   double origin[3] = {0, 0, 0}, res = 0.1, res_inv = 10.0;
   int dims[3] = {0, 0, 0};
+  int ring[3] = {0, 0, 0};   // ring address of local voxel 0, per axis
   std::vector<float> occupancy_buffer;
   std::vector<int> operation_cnt, hit_cnt;
   std::queue<Idx3> update_cache;
@@ -95,7 +102,7 @@ struct ProbMap {
   float l_hit = 0, l_miss = 0, l_min = 0, l_max = 0, l_occ = 0, l_free = 0;
 
   void reset(const double* origin_, double res_, const int* dims_) {
-    for (int a = 0; a < 3; a++) { origin[a] = origin_[a]; dims[a] = dims_[a]; }
+    for (int a = 0; a < 3; a++) { origin[a] = origin_[a]; dims[a] = dims_[a]; ring[a] = 0; }
     res = res_;
     res_inv = 1.0 / res_;
     const size_t n3 = (size_t)dims[0] * dims[1] * dims[2];
@@ -105,7 +112,10 @@ struct ProbMap {
     update_cache = std::queue<Idx3>();
     batch_update_counter = 0;
   }
-  size_t address(const Idx3& id) const { return ((size_t)id[0] * dims[1] + id[1]) * dims[2] + id[2]; }
+  size_t address(const Idx3& id) const {
+    const int r[3] = {(id[0] + ring[0]) % dims[0], (id[1] + ring[1]) % dims[1], (id[2] + ring[2]) % dims[2]};
+    return ((size_t)r[0] * dims[1] + r[1]) * dims[2] + r[2];
+  }
   bool insideLocalMap(const Idx3& id) const {
     for (int a = 0; a < 3; a++)
       if (id[a] < 0 || id[a] >= dims[a]) return false;
@@ -222,13 +232,81 @@ struct ProbMap {
     return 1;
   }
 
+  void resetCell(size_t h) { occupancy_buffer[h] = 0.0f; }   // prob_map.cpp:511- (the counter maps it feeds are out of scope)
+  void resetLocalMap() {                                     // prob_map.cpp:823-831
+    std::fill(occupancy_buffer.begin(), occupancy_buffer.end(), 0.0f);
+    update_cache = std::queue<Idx3>();
+    batch_update_counter = 0;
+    std::fill(operation_cnt.begin(), operation_cnt.end(), 0);
+    std::fill(hit_cnt.begin(), hit_cnt.end(), 0);
+  }
+  // The slide of updateProbMap for one sensor position.  Returns 0 within the threshold, 1 slid, 2 slid because the sensor was
+  // outside the local map (the reference then drops the cloud), -1 a batch is open; shift: the voxels the window moved by.
+  // slide_z false: z takes no part (the deviation of include/topay.h).
+  int slide(const double* sensor, double threshold, bool slide_z, int* shift) {
+    shift[0] = shift[1] = shift[2] = 0;
+    if (batch_update_counter != 0) return -1;   // the condition of both slides (prob_map.cpp:306, 324)
+    const int axes = slide_z ? 3 : 2;
+    const Vec3 pos{{sensor[0] - origin[0], sensor[1] - origin[1], sensor[2] - origin[2]}};
+    const Idx3 new_origin_i = posToGlobalIndex(pos);
+    int local_map_origin_i[3];                   // the centre voxel of the window, in the grid's frame
+    double local_map_origin_d[3];                // origin_i * resolution: its low corner (sliding_map.cpp:118)
+    for (int a = 0; a < 3; a++) { local_map_origin_i[a] = dims[a] / 2; local_map_origin_d[a] = (double)local_map_origin_i[a] * res; }
+    bool inside = true;                          // insideLocalMap(pos), on the sliding axes
+    for (int a = 0; a < axes; a++) inside = inside && new_origin_i[a] >= 0 && new_origin_i[a] < dims[a];
+    int status;
+    if (!inside) status = 2;                     // prob_map.cpp:306-311
+    else {
+      double n2 = 0.0;                           // (pos - local_map_origin_d_).norm(), prob_map.cpp:326
+      for (int a = 0; a < axes; a++) { const double d = pos[a] - local_map_origin_d[a]; n2 = a == 0 ? d * d : n2 + d * d; }
+      if (!(std::sqrt(n2) > threshold)) return 0;
+      status = 1;
+    }
+    // mapSliding
+    int shift_num[3] = {0, 0, 0};
+    for (int a = 0; a < axes; a++) shift_num[a] = new_origin_i[a] - local_map_origin_i[a];
+    bool all = false;
+    for (int a = 0; a < 3; a++) all = all || std::abs(shift_num[a]) > dims[a];
+    if (all) resetLocalMap();                    // sliding_map.cpp:121-128
+    else
+      for (int i = 0; i < 3; i++) {              // the slabs that leave, axis by axis (130-163, clearMemoryOutOfMap)
+        if (shift_num[i] == 0) continue;
+        std::vector<int> clear_id;               // local indices on axis i before the slide
+        if (shift_num[i] > 0) for (int k = 0; k < shift_num[i]; k++) clear_id.push_back(k % dims[i]);
+        else for (int k = -1; k >= shift_num[i]; k--) clear_id.push_back(((dims[i] + k) % dims[i] + dims[i]) % dims[i]);
+        const int i1 = (i + 1) % 3, i2 = (i + 2) % 3;
+        for (int idd : clear_id)
+          for (int x = 0; x < dims[i1]; x++)
+            for (int y = 0; y < dims[i2]; y++) {
+              Idx3 id;
+              id[i] = idd; id[i1] = x; id[i2] = y;
+              resetCell(address(id));
+            }
+      }
+    // updateLocalMapOriginAndBound: local voxel l is now what was l + shift, the frame moves by whole voxels
+    for (int a = 0; a < 3; a++) {
+      ring[a] = ((ring[a] + shift_num[a]) % dims[a] + dims[a]) % dims[a];
+      origin[a] = origin[a] + (double)shift_num[a] * res;
+      shift[a] = shift_num[a];
+    }
+    return status;
+  }
+  // a buffer in local order [nx][ny][nz]
+  template <typename T> void unring(const std::vector<T>& buf, T* out) const {
+    Idx3 id;
+    size_t k = 0;
+    for (id[0] = 0; id[0] < dims[0]; id[0]++)
+      for (id[1] = 0; id[1] < dims[1]; id[1]++)
+        for (id[2] = 0; id[2] < dims[2]; id[2]++) out[k++] = buf[address(id)];
+  }
+
   // isOccupied per voxel, its projection, and the cells with an occupied voxel whose centre is below the chassis height
   void occupancy(float l_occ_, double chassis_height, int8_t* occ2d, int8_t* occ2d_critical, int8_t* occ3d) const {
     const size_t n2 = (size_t)dims[0] * dims[1];
     for (size_t c = 0; c < n2; c++) {
       bool any = false, low = false;
       for (int z = 0; z < dims[2]; z++) {
-        const bool occ = occupancy_buffer[c * dims[2] + z] >= l_occ_;
+        const bool occ = occupancy_buffer[address(Idx3{{(int)(c / dims[1]), (int)(c % dims[1]), z}})] >= l_occ_;
         occ3d[c * dims[2] + z] = occ ? 1 : 0;
         any = any || occ;
         low = low || (occ && origin[2] + ((double)z + 0.5) * res < chassis_height);

@@ -331,6 +331,7 @@ def mlib():
         L.wl_pm_update.argtypes = [C.c_void_p, C.c_int, C.c_void_p, c_dp, C.c_void_p]
         L.wl_pm_get.argtypes = [C.c_void_p, C.c_void_p, c_ip, c_ip, c_ip]
         L.wl_pm_get.restype = None
+        L.wl_pm_slide.argtypes = [C.c_void_p, c_dp, C.c_double, C.c_int, c_ip, c_dp]
         L.wl_pm_occupancy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.wl_pm_occupancy.restype = None
         L.wl_pm_logodds.argtypes = [C.c_void_p, C.c_void_p]
@@ -384,6 +385,14 @@ class ProbMapCheck:
         bc = C.c_int(0)
         mlib().wl_pm_get(self.h, lo.ctypes.data, op.ctypes.data_as(c_ip), hit.ctypes.data_as(c_ip), C.byref(bc))
         return lo, op, hit, bc.value
+
+    def slide(self, sensor, params):
+        """ProbMap::slide for one sensor position.  params: threshold and slide_z (topay_amd.api.SenseSlideParams).  Returns
+        (status, shift int32[3]); self.origin is the grid's origin after it."""
+        sp = np.ascontiguousarray(sensor, dtype=np.float64)
+        shift = np.zeros(3, dtype=np.int32)
+        st = mlib().wl_pm_slide(self.h, _dp(sp), float(params.threshold), int(params.slide_z), shift.ctypes.data_as(c_ip), _dp(self.origin))
+        return st, shift
 
     def occupancy(self, params):
         nx, ny, nz = (int(v) for v in self.dims)

@@ -677,8 +677,9 @@ topay_status topay_ee_select(topay_ctx* ctx, int n, const int* map_ids, const in
  * real-robot mode plans on (grid_map.cpp:20-26), as a per-slot occupancy belief.  Clouds are inserted on the device, occupancy
  * grids are derived from the belief and the slot's five fields rebuilt from them, so that the map can change under a committed
  * trajectory (topay_track_safe) without the host touching a voxel.
- * Configuration restated: raycasting/enable true, map_sliding/enable false, esdf/enable false, frontier_extraction_en false, no
- * inflation map, no kd-tree.  Left out: the sliding window and its hash; the InfMap / CounterMap counters; ESDFMap::updateESDF3D
+ * Configuration restated: raycasting/enable true, esdf/enable false, frontier_extraction_en false, no inflation map, no kd-tree;
+ * map_sliding is a step of its own (topay_sense_slide, below): the insert never moves the grid.  Left out: re-addressing the
+ * window through its hash (a slide moves the belief); the InfMap / CounterMap counters; ESDFMap::updateESDF3D
  * (the slot's fields come from the exact builder of topay_build_esdf_fields); the first-frame block that clears a sphere of
  * raycast_range_min around the robot (prob_map.cpp:356-372), a no-op at the shipped ray_range [0.0, 5]: ray_range[0] > 0 is
  * refused with TOPAY_ERR_UNSUPPORTED.
@@ -745,6 +746,59 @@ topay_status topay_sense_scan(topay_ctx* ctx, int n, const int* truth_map_ids, c
                               double range, int cloud_cap, int* cloud_off, float* points);
 /* Device time (HIP events) of the last scan, insert (selection and rays), flush, and commit with its fields, in ms. */
 topay_status topay_sense_ms(topay_ctx* ctx, double ms[4]);
+
+/* ---- Sliding sensor map: a slot's belief moves with the robot ---------------------------------------------------------------
+ * params/rog_map.yaml ships map_sliding: {enable: true, threshold: 0.3}: ProbMap::updateProbMap re-centres the local map on the
+ * sensor before it inserts a cloud (prob_map.cpp:306-311, 324-328), and SlidingMap::mapSliding forgets what leaves the window and
+ * keeps what stays (sliding_map.cpp:113-166).  topay_sense_slide is that step for n slots; the cycle of a moving robot is
+ * scan -> slide -> insert (skipped on status 2) -> commit.  A caller who never calls it sees nothing change.
+ * Frame.  The belief's descriptor stays the one statement of the grid.  A slide by s voxels replaces origin[a] by
+ * origin[a] + (double)s[a] * resolution (one multiply and one add per axis), and min_boundary / max_boundary move by the same
+ * amount.  After that every sense entry runs unchanged on the new descriptor: the reference's code on u = p - origin.
+ * Centre.  c[a] = dims[a] / 2 (integer division; for the reference's odd sizes 2h + 1 its centre voxel).
+ *   v[a] = floor((sensor[a] - origin[a]) * (1 / resolution))    the inserter's expression (posToGlobalIndex, sliding_map.cpp:181-183)
+ *   s[a] = v[a] - c[a] on the sliding axes, 0 elsewhere          shift_num (sliding_map.cpp:120)
+ * Trigger (prob_map.cpp:324-326).  local_map_origin_d_ is origin_i * resolution, the LOW CORNER of the centre voxel and not its
+ * centre (sliding_map.cpp:118); restated as it stands: d[a] = (sensor[a] - origin[a]) - (double)c[a] * resolution, and the slot
+ * slides iff sqrt(d0 d0 + d1 d1 (+ d2 d2)), summed left to right over the sliding axes, is > threshold.  threshold = 0 re-centres
+ * unconditionally.  The reference's implicit first-frame slide (map_empty_, !init_; prob_map.cpp:325, 329-332) has no counterpart:
+ * topay_sense_reset places the grid explicitly.
+ *   status[k]   0  within the threshold: nothing changes, shift 0 0 0
+ *               1  slid by shift[3k ..]
+ *               2  the sensor's voxel lay outside 0 .. dims - 1 on a sliding axis: slid as in 1, whatever the threshold.  The
+ *                  reference drops that frame's cloud (prob_map.cpp:306-311), so the caller should skip the insert too
+ *              -1  a batch is open (batch counter != 0, the reference's condition for both slides): nothing changes, shift 0 0 0
+ * Effect.  The log-odds of local voxel l afterwards are those of local voxel l + s before, where l + s lies in 0 .. dims - 1 on
+ * every axis; every other voxel holds 0 = unknown, what resetCell and resetLocalMap leave (prob_map.cpp:511-, 823-831).  A shift of
+ * dims[a] or more on an axis therefore clears everything (resetLocalMap, sliding_map.cpp:121-128; the slab clearing of a shift of
+ * exactly dims[a] gives the same).  Counts are zero whenever a slide is legal (no count outlives a flush, and a slide needs a
+ * closed batch): they stay zero and do not move.  The batch counter stays 0.
+ * Fields.  A slide touches the belief only.  The slot's five fields and the slot's own descriptor stay those of the last
+ * topay_sense_commit, so a planning call between slide and commit reads a consistent map; the next topay_sense_commit builds the
+ * fields on the slid descriptor and installs it with them.
+ * Memory.  The shifted image is written into one scratch buffer of the context and copied back on the context's stream.  The
+ * scratch holds 4 bytes per voxel of the slots that moved in one call and grows to the largest such call: at most the log-odds
+ * of all beliefs named in one call, never a second copy per slot.
+ * Deviations.  slide_z defaults to 0: a ground robot's slot spans z from the floor, and topay_sense_commit's chassis rule and the
+ * 16-layer columns assume it; with slide_z = 0 the z axis takes no part in the shift, the trigger or status 2.  slide_z = 1 is
+ * the reference.  The window is moved physically and not re-addressed through getLocalIndexHash (sliding_map.cpp:168-173),
+ * because every kernel that reads a belief or a field indexes a dense grid.  Left out as for the insert: InfMap, FreeCntMap and
+ * ESDFMap::mapSliding.
+ * TOPAY_ERR_NO_MAP: a slot without a belief.  TOPAY_ERR_INVALID_ARG: a slot named twice or out of range, n <= 0, NULL map_ids or
+ * sensor_pos, a negative or non-finite threshold, a sensor that is not finite or more than 1e6 m from the origin (the inserter's
+ * rule) or whose voxel index exceeds 1e9. */
+typedef struct {
+  double threshold;   /* 0.3   rog_map.yaml map_sliding/threshold */
+  int slide_z;        /* 0: x and y only (see Deviations); 1: all three axes, as the reference */
+  int reserved;
+} topay_sense_slide_params_t;
+topay_status topay_sense_slide_default_params(topay_sense_slide_params_t* p);
+topay_status topay_sense_slide(topay_ctx* ctx, int n, const int* map_ids, const double* sensor_pos /* n x 3 */,
+                               const topay_sense_slide_params_t* params /* NULL = defaults */,
+                               int* status /* n, optional */, int* shift /* n x 3, optional */);
+topay_status topay_sense_slide_ms(topay_ctx* ctx, double* ms);   /* device time of the last call's launches */
+/* The parity hook beside topay_sense_get: the descriptor of a slot's belief as it is (the slot's own follows at the commit). */
+topay_status topay_sense_get_desc(topay_ctx* ctx, int map_id, topay_map_desc_t* desc);
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * The tracking controller and the fake robot: what Planner::cmdCallback (planner.cpp:158-178) runs between two replans.

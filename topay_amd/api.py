@@ -115,6 +115,11 @@ class SenseParams(C.Structure):
                 ("virtual_ground_height", C.c_double), ("local_update_box", C.c_double * 3), ("chassis_height", C.c_double)]
 
 
+class SenseSlideParams(C.Structure):
+    """topay_sense_slide_params_t (include/topay.h): map_sliding/threshold of params/rog_map.yaml and whether z slides."""
+    _fields_ = [("threshold", C.c_double), ("slide_z", C.c_int), ("reserved", C.c_int)]
+
+
 class MpcParams(C.Structure):
     """topay_mpc_params_t (include/topay.h): the ompc/ keys of params/mpc.yaml and the QP solver's knobs."""
     _fields_ = [("du_threshold", C.c_double), ("dt", C.c_double), ("ctrl_freq", C.c_double), ("max_iter", C.c_int),
@@ -256,6 +261,11 @@ def load(path=None):
         L.topay_sense_get.argtypes = [C.c_void_p, C.c_int, c_fp, c_ip, c_ip, c_ip]
         L.topay_sense_scan.argtypes = [C.c_void_p, C.c_int, c_ip, c_dp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, c_ip, c_fp]
         L.topay_sense_ms.argtypes = [C.c_void_p, c_dp]
+    if hasattr(L, "topay_sense_slide"):
+        L.topay_sense_slide_default_params.argtypes = [C.POINTER(SenseSlideParams)]
+        L.topay_sense_slide.argtypes = [C.c_void_p, C.c_int, c_ip, c_dp, C.POINTER(SenseSlideParams), c_ip, c_ip]
+        L.topay_sense_slide_ms.argtypes = [C.c_void_p, c_dp]
+        L.topay_sense_get_desc.argtypes = [C.c_void_p, C.c_int, C.POINTER(MapDesc)]
     if hasattr(L, "topay_mpc_cmds"):   # (older builds of the library under tools/libs, A/B runs)
         L.topay_mpc_default_params.argtypes = [C.POINTER(MpcParams)]
         L.topay_mpc_qp_dims.argtypes = [C.POINTER(MpcParams), c_ip, c_ip]
@@ -886,6 +896,37 @@ class MomaTrajOptBatch:
         ms = np.zeros(4)
         _chk(self.L, self.L.topay_sense_ms(self.h, _dp(ms)))
         return dict(zip(SENSE_MS_KEYS, ms.tolist()))
+
+    def sense_slide_params(self, **kw):
+        """topay_sense_slide_default_params (threshold 0.3, slide_z 0) with the given fields replaced."""
+        p = SenseSlideParams()
+        _chk(self.L, self.L.topay_sense_slide_default_params(C.byref(p)))
+        for k, v in kw.items():
+            setattr(p, k, v)
+        return p
+
+    def sense_slide(self, map_ids, sensor_pos, params=None):
+        """topay_sense_slide: the beliefs of the slots re-centred on their sensors where the trigger says so.  Returns
+        (status int32[n], shift int32[n, 3]): 0 within the threshold, 1 slid, 2 slid from outside the window (skip this frame's
+        insert), -1 a batch is open."""
+        ids = np.ascontiguousarray(map_ids, dtype=np.int32).reshape(-1)
+        n = len(ids)
+        sp = np.ascontiguousarray(sensor_pos, dtype=np.float64).reshape(n, 3)
+        st, sh = np.zeros(n, dtype=np.int32), np.zeros((n, 3), dtype=np.int32)
+        _chk(self.L, self.L.topay_sense_slide(self.h, n, _ip(ids), _dp(sp), C.byref(params) if params is not None else None, _ip(st), _ip(sh)))
+        return st, sh
+
+    def sense_slide_ms(self):
+        """Device time of the last sense_slide's launches in ms."""
+        ms = C.c_double(0.0)
+        _chk(self.L, self.L.topay_sense_slide_ms(self.h, C.byref(ms)))
+        return ms.value
+
+    def sense_desc(self, map_id):
+        """topay_sense_get_desc: (origin, min_boundary, max_boundary) of a slot's belief, float64[3] each."""
+        d = MapDesc()
+        _chk(self.L, self.L.topay_sense_get_desc(self.h, int(map_id), C.byref(d)))
+        return np.array(d.origin[:]), np.array(d.min_boundary[:]), np.array(d.max_boundary[:])
 
     def playback(self, i, times):
         """MomaTraj playback of candidate i: (states[len(times), 10], car_seq[n, 4])."""

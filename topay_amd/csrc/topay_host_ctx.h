@@ -328,7 +328,8 @@ struct WorldState {
 // counter, the rays counted since the last flush and the parameters of the last insert (topay_sense_commit reads l_occ and
 // chassis_height from them); the uploads of a call; the points of the last topay_sense_scan; the occupancy grids of the last
 // topay_sense_commit and where each slot's lie in them (topay_get_occupancy); the device time of the last scan, insert, flush
-// and commit with the fields.
+// and commit with the fields; the scratch image of topay_sense_slide (the log-odds of the slots that moved in the largest call so
+// far, never a second copy per slot) and the device time of its last call.
 struct SenseBelief {
   DevBuf buf;
   float* logodds = nullptr; int* cnt = nullptr; int* box = nullptr;
@@ -340,11 +341,11 @@ struct SenseBelief {
 };
 struct SenseState {
   std::vector<SenseBelief> slot;   // sized by the first topay_sense_reset
-  DevBuf pts, io, scan, occ;
+  DevBuf pts, io, scan, occ, slide;
   size_t scan_points = 0;
   enum { kScan, kInsert, kFlush, kCommit };
-  DevTimer timer[4];
-  double ms[4] = {0, 0, 0, 0};
+  DevTimer timer[4], slide_timer;
+  double ms[4] = {0, 0, 0, 0}, slide_ms = 0;
   bool has_belief(int m) const { return m >= 0 && m < (int)slot.size() && slot[m].have; }
   bool has_occ(int m) const { return m >= 0 && m < (int)slot.size() && slot[m].have_occ; }
   const signed char* occ3_of(int m, int* d) const {

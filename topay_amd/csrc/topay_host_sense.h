@@ -45,6 +45,34 @@ static topay_status sense_check_beliefs(topay_ctx* c, int n, const int* map_ids,
   return TOPAY_OK;
 }
 
+// What topay_sense_slide does to one slot, from its descriptor and the sensor (include/topay.h, "Sliding sensor map"): the sensor's
+// voxel v with the inserter's expression, the centre voxel c = dims / 2, the shift v - c on the sliding axes, and the trigger of
+// prob_map.cpp:324-326 with local_map_origin_d_ the LOW CORNER of the centre voxel (sliding_map.cpp:118).  A sensor whose voxel is
+// outside the window slides whatever the threshold (prob_map.cpp:306-311).  false: a voxel index beyond an int.
+struct SenseSlide { int status, shift[3]; };
+static bool sense_slide_decide(const topay_map_desc_t& g, const double* sensor, double threshold, bool slide_z, bool batch_open, SenseSlide& D) {
+  D.status = 0;
+  D.shift[0] = D.shift[1] = D.shift[2] = 0;
+  const double res_inv = 1.0 / g.resolution;
+  const int axes = slide_z ? 3 : 2;
+  double sq = 0.0;
+  bool outside = false;
+  for (int a = 0; a < axes; a++) {
+    const double u = sensor[a] - g.origin[a];
+    const double vf = floor(u * res_inv);
+    if (!(std::fabs(vf) <= 1.0e9)) return false;
+    const int v = (int)vf, cv = g.dims[a] / 2;
+    D.shift[a] = v - cv;
+    outside = outside || v < 0 || v >= g.dims[a];
+    const double d = u - (double)cv * g.resolution;
+    sq = a == 0 ? d * d : sq + d * d;
+  }
+  if (batch_open) D.status = -1;   // batch_update_counter == 0 is the condition of both slides
+  else if (outside) D.status = 2;
+  else if (sqrt(sq) > threshold) D.status = 1;
+  return true;
+}
+
 extern "C" {
 
 topay_status topay_sense_default_params(topay_sense_params_t* p) {
@@ -373,6 +401,108 @@ topay_status topay_sense_scan(topay_ctx* c, int n, const int* truth_map_ids, con
 topay_status topay_sense_ms(topay_ctx* c, double ms[4]) {
   if (!c || !ms) return TOPAY_ERR_INVALID_ARG;
   for (int k = 0; k < 4; k++) ms[k] = c->sense.ms[k];
+  return TOPAY_OK;
+}
+
+topay_status topay_sense_slide_default_params(topay_sense_slide_params_t* p) {
+  if (!p) return TOPAY_ERR_INVALID_ARG;
+  memset(p, 0, sizeof(*p));
+  p->threshold = 0.3;   // params/rog_map.yaml map_sliding/threshold
+  p->slide_z = 0;
+  return TOPAY_OK;
+}
+
+topay_status topay_sense_slide(topay_ctx* c, int n, const int* map_ids, const double* sensor_pos, const topay_sense_slide_params_t* params, int* status,
+                               int* shift) {
+  if (!c || n <= 0 || !map_ids || !sensor_pos) return TOPAY_ERR_INVALID_ARG;
+  topay_status s;
+  if ((s = check_map_slots(c, n, map_ids, kMapOnce, "topay_sense_slide")) != TOPAY_OK) return s;
+  topay_sense_slide_params_t prm;
+  topay_sense_slide_default_params(&prm);
+  if (params) prm = *params;
+  if (!(prm.threshold >= 0.0) || !(prm.threshold <= 1.7976931348623157e308)) { set_err("topay_sense_slide: threshold negative or not finite"); return TOPAY_ERR_INVALID_ARG; }
+  if ((s = sense_check_beliefs(c, n, map_ids, "topay_sense_slide")) != TOPAY_OK) return s;
+  // the decisions, slot by slot; nothing of a slot moves before every check, allocation and upload of the call has succeeded
+  std::vector<SenseSlide> dec((size_t)n);
+  std::vector<SenseSlideSlot> rows;
+  std::vector<int> row_slot;
+  size_t floats = 0;
+  int max_cols = 0;
+  for (int k = 0; k < n; k++) {
+    const SenseBelief& b = c->sense.slot[map_ids[k]];
+    const double* sp = sensor_pos + 3 * (size_t)k;
+    for (int a = 0; a < 3; a++)
+      if (!(std::fabs(sp[a] - b.desc.origin[a]) <= 1.0e6)) { set_err("topay_sense_slide: sensor position not finite or more than 1e6 m from the map"); return TOPAY_ERR_INVALID_ARG; }
+    SenseSlide& D = dec[(size_t)k];
+    if (!sense_slide_decide(b.desc, sp, prm.threshold, prm.slide_z != 0, b.batch_counter != 0, D)) {
+      set_err("topay_sense_slide: the sensor's voxel index does not fit an int at this resolution");
+      return TOPAY_ERR_INVALID_ARG;
+    }
+    if (D.status <= 0 || (D.shift[0] == 0 && D.shift[1] == 0 && D.shift[2] == 0)) continue;   // nothing to move
+    SenseSlideSlot R;
+    memset(&R, 0, sizeof(R));
+    R.src = b.logodds;
+    for (int a = 0; a < 3; a++) {   // (a shift of dims or more clears everything, and so does one of exactly dims)
+      R.dims[a] = b.desc.dims[a];
+      R.shift[a] = std::max(-b.desc.dims[a], std::min(b.desc.dims[a], D.shift[a]));
+    }
+    rows.push_back(R);
+    row_slot.push_back(k);
+    floats += ((size_t)R.dims[0] * R.dims[1] * R.dims[2] + 3) & ~(size_t)3;   // (each image starts on a 16-byte boundary)
+    max_cols = std::max(max_cols, R.dims[0] * R.dims[1]);
+  }
+  const size_t nr = rows.size();
+  const int bps = (max_cols + TOPAY_SENSE_BLOCK - 1) / TOPAY_SENSE_BLOCK;
+  if ((long long)nr * bps >= (1ll << 31)) { set_err("topay_sense_slide: launch too large"); return TOPAY_ERR_UNSUPPORTED; }
+  HIPCHK(hipSetDevice(c->device));
+  DevTimer& tm = c->sense.slide_timer;
+  if (nr > 0) {
+    if ((s = c->sense.slide.ensure(floats * sizeof(float))) != TOPAY_OK) return s;
+    if ((s = c->sense.io.ensure(sizeof(SenseSlideSlot) * nr)) != TOPAY_OK) return s;
+    float* at = c->sense.slide.as<float>();
+    for (SenseSlideSlot& R : rows) { R.dst = at; at += ((size_t)R.dims[0] * R.dims[1] * R.dims[2] + 3) & ~(size_t)3; }
+    HIPCHK(h2d(c, c->sense.io.as<SenseSlideSlot>(), (const SenseSlideSlot*)rows.data(), nr));
+  }
+  HIPCHK(tm.start(c->stream));
+  if (nr > 0) {
+    hipLaunchKernelGGL(k_sense_slide, dim3((unsigned)(nr * bps)), dim3(TOPAY_SENSE_BLOCK), 0, c->stream, (const SenseSlideSlot*)c->sense.io.as<SenseSlideSlot>(), bps);
+    HIPCHK(hipGetLastError());
+    for (const SenseSlideSlot& R : rows)   // the image back into the belief, on the same stream
+      HIPCHK(hipMemcpyAsync((void*)R.src, R.dst, sizeof(float) * (size_t)R.dims[0] * R.dims[1] * R.dims[2], hipMemcpyDeviceToDevice, c->stream));
+  }
+  HIPCHK(tm.stop(c->stream));
+  for (int k = 0; k < n; k++) {   // the descriptor is the one statement of the grid: it moves with the launches
+    const SenseSlide& D = dec[(size_t)k];
+    if (D.status <= 0) continue;
+    topay_map_desc_t& d = c->sense.slot[map_ids[k]].desc;
+    for (int a = 0; a < 3; a++) {
+      const double by = (double)D.shift[a] * d.resolution;
+      d.origin[a] = d.origin[a] + by;
+      d.min_boundary[a] = d.min_boundary[a] + by;
+      d.max_boundary[a] = d.max_boundary[a] + by;
+    }
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));   // (rows is on this stack)
+  HIPCHK(tm.read(&c->sense.slide_ms));
+  for (int k = 0; k < n; k++) {
+    if (status) status[k] = dec[(size_t)k].status;
+    if (shift)
+      for (int a = 0; a < 3; a++) shift[3 * (size_t)k + a] = dec[(size_t)k].status > 0 ? dec[(size_t)k].shift[a] : 0;
+  }
+  return TOPAY_OK;
+}
+
+topay_status topay_sense_slide_ms(topay_ctx* c, double* ms) {
+  if (!c || !ms) return TOPAY_ERR_INVALID_ARG;
+  *ms = c->sense.slide_ms;
+  return TOPAY_OK;
+}
+
+topay_status topay_sense_get_desc(topay_ctx* c, int map_id, topay_map_desc_t* desc) {
+  if (!c || !desc) return TOPAY_ERR_INVALID_ARG;
+  if (topay_status s = check_map_slots(c, 1, &map_id, 0, "topay_sense_get_desc")) return s;
+  if (topay_status s = sense_check_beliefs(c, 1, &map_id, "topay_sense_get_desc")) return s;
+  *desc = c->sense.slot[map_id].desc;
   return TOPAY_OK;
 }
 

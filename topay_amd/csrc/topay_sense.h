@@ -10,6 +10,8 @@
 //   k_sense_box_reset  the cache box of a slot that has been flushed becomes empty
 //   k_sense_occupancy  the belief as occ3d / occ2d / occ2d_critical (isOccupied, prob_map.h:129; the 2-D rule of
 //                      GridMap::cloudCallback, grid_map.cpp:554-568, with the voxel centre as the point)
+//   k_sense_slide      SlidingMap::mapSliding (sliding_map.cpp:113-166): the belief moved by whole voxels into a scratch image, what
+//                      enters the window unknown
 //   k_sense_scan       the range sensor: one lane per ray through occ3d (not a restatement: pointcloud_render_node needs PCL)
 // Frame.  The reference indexes its world frame, floor(p / resolution) with centres at + 0.5 (ORIGIN_AT_CORNER, CMakeLists.txt:14;
 // raycaster.cpp:46-63, sliding_map.cpp:175-203).  Here every position is first moved into the map's frame, u = p - origin (the
@@ -59,6 +61,11 @@ struct SenseScanSlot {
   double origin[3], res;
   int dims[3], pad;
   double pose[4];   // x, y, z, yaw
+};
+struct SenseSlideSlot {
+  const float* src;   // the belief's log-odds, [nx][ny][nz]
+  float* dst;         // the shifted image, same layout, in the context's scratch
+  int dims[3], shift[3];
 };
 struct alignas(16) SensePoint { float x, y, z, i; };
 
@@ -322,6 +329,32 @@ __global__ void __launch_bounds__(TOPAY_SENSE_BLOCK) k_sense_occupancy(const Sen
   }
   S.occ2c[col] = any ? 1 : 0;
   S.occ2[col] = low ? 1 : 0;
+}
+
+// SlidingMap::mapSliding (sliding_map.cpp:113-166) as a move: dst[l] = src[l + shift] where l + shift is a voxel of the grid, else 0
+// (resetCell).  One lane per (x, y) column of the destination; adjacent lanes are adjacent y, so a wave reads and writes contiguous
+// runs of columns, the read run displaced by a constant.  src and dst never overlap (dst is the context's scratch).  A column whose
+// nz is a multiple of 4 and that does not move in z goes in 16-byte pieces (every column then starts on a 16-byte boundary: both
+// bases do); otherwise float by float, a z shift moving within the column.  The host gives |shift[a]| <= dims[a].
+__global__ void __launch_bounds__(TOPAY_SENSE_BLOCK) k_sense_slide(const SenseSlideSlot* slots, int blocks_per_slot) {
+  const int slot = blockIdx.x / blocks_per_slot;
+  const SenseSlideSlot S = slots[slot];
+  const int col = (blockIdx.x - slot * blocks_per_slot) * blockDim.x + threadIdx.x, ny = S.dims[1], nz = S.dims[2];
+  if (col >= S.dims[0] * ny) return;
+  const int x = col / ny, y = col - x * ny;
+  const int sx = x + S.shift[0], sy = y + S.shift[1], s2 = S.shift[2];
+  const bool inside = sx >= 0 && sx < S.dims[0] && sy >= 0 && sy < ny;
+  float* d = S.dst + (size_t)col * nz;
+  const float* s = S.src + ((size_t)(inside ? sx : 0) * ny + (inside ? sy : 0)) * nz;
+  struct alignas(16) F4 { float x, y, z, w; };
+  if ((nz & 3) == 0 && s2 == 0) {
+    for (int z = 0; z < nz; z += 4) *(F4*)(d + z) = inside ? *(const F4*)(s + z) : F4{0.0f, 0.0f, 0.0f, 0.0f};
+  } else {
+    for (int z = 0; z < nz; z++) {
+      const int sz = z + s2;
+      d[z] = inside && sz >= 0 && sz < nz ? s[sz] : 0.0f;
+    }
+  }
 }
 
 // Ray k = i * n_el + j of a pose: azimuth 2 pi i / n_az + yaw, elevation fov ((j + 0.5) / n_el - 0.5); traversed from the pose
