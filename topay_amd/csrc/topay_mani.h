@@ -16,6 +16,13 @@
 #define TOPAY_ESDF_LOOKAHEAD 2
 #define TOPAY_ESDF_LOOKAHEAD_OCC2 1
 #define TOPAY_OCC2_FENCE 1
+// 1: work of the block whose result is exactly zero is skipped under scalar branches when no active lane of the wave needs
+// it -- a sphere's base and arm-local force transforms when no lane has a force on it, the two torque walks when no lane
+// has a force on any sphere (the comments at the skips say why every value keeps its bits).  0: the code paths of before,
+// for the bit comparison of the two builds (tests/test_mani_skip.py) and the A/B.  A compile-time switch only.
+#ifndef TOPAY_MANI_SKIP_IDLE
+#define TOPAY_MANI_SKIP_IDLE 1
+#endif
 
 namespace topay {
 
@@ -111,6 +118,19 @@ __device__ __noinline__ ManiOut manipulator_block(const TOPAY_GLB DevMap* mp, ld
     }
   }
   const double omg = (pj == 0 || pj == 2 * TOPAY_K) ? 0.5 : 1.0;
+#if TOPAY_MANI_SKIP_IDLE
+  // Lanes whose pose is not finite (or absurd: det_sincos_n turns |angle| >= 1e15 into NaN) never allow a skip: the skipped
+  // arithmetic multiplies pose-derived factors by zero forces, which is zero only for finite factors.  A sum of magnitudes
+  // is at least its largest term and NaN if a term is, so it is below 1e15 only if every angle and both coordinates are.
+  unsigned long long forced_all;   // (wave-uniform: a lane mask in a scalar register pair)
+  {
+    double mag = fabs(pos[0]) + fabs(pos[1]);
+#pragma unroll
+    for (int d = 2; d < 10; d++) mag += fabs(pos[d]);
+    forced_all = __ballot(in_act && !(mag < 1.0e15));
+  }
+  unsigned long long forced_any = forced_all;
+#endif
   ManiOut out;
   double cost, gdTk;
   const double mu = P.relu_mu;
@@ -284,6 +304,19 @@ __device__ __noinline__ ManiOut manipulator_block(const TOPAY_GLB DevMap* mp, ld
       gdTk += omg * wMC * (pe * invK);
       cost += w * wMC * pe;
     }
+#if TOPAY_MANI_SKIP_IDLE
+    // Sphere k has a force in a lane only from the pair stash, the chassis top or an ESDF violation, and almost every sample
+    // of a converging candidate has none.  The vote is over ACTIVE lanes: a padding lane computes on clamped inputs and its
+    // results are dropped.  G is never -0.0 (it starts at +0.0, and a sum is -0.0 in round-to-nearest only if both terms
+    // are), so a lane without a vote holds G = (+0, +0, +0) and, its pose being finite, the transforms below would give
+    // bFx + 0, bFy + 0, bMz + (+-0) and L = (+-0, +-0, +-0).  bFx, bFy and bMz start at +0.0 and likewise never hold -0.0:
+    // adding +-0 returns them bit for bit.  L = +0.0 in place of +-0 is read by the walks alone: added to or subtracted
+    // from Fx, Fy, Fz and, times a finite factor, added to Mx, My, Mz -- accumulators that start at +0.0 as well.  So when
+    // no active lane votes, the branch (scalar: the ballot is wave-uniform) changes no bit of any active lane's result.
+    const unsigned long long forced_k = __ballot(in_act && !(Gx == 0.0 && Gy == 0.0 && Gz == 0.0)) | forced_all;
+    forced_any |= forced_k;
+    if (forced_k != 0) {
+#endif
     bFx += Gx;
     bFy += Gy;
     bMz = fma(Px[k] - pos[0], Gy, fma(-(Py[k] - pos[1]), Gx, bMz));
@@ -291,12 +324,29 @@ __device__ __noinline__ ManiOut manipulator_block(const TOPAY_GLB DevMap* mp, ld
     Lx[k] = fma(A[6], Gz, fma(A[3], Gy, A[0] * Gx));
     Ly[k] = fma(A[7], Gz, fma(A[4], Gy, A[1] * Gx));
     Lz[k] = fma(A[8], Gz, fma(A[5], Gy, A[2] * Gx));
+#if TOPAY_MANI_SKIP_IDLE
+    } else {
+      Lx[k] = 0.0; Ly[k] = 0.0; Lz[k] = 0.0;
+    }
+#endif
     if (OCC >= 2 && TOPAY_OCC2_FENCE) __builtin_amdgcn_sched_barrier(0);
   }
   MSTAMP(3);  // ESDF loop
   MMARK(3);
   // joints: tau_i = u_i . (Mo_beyond - o_{i+1} x F_beyond) with F, Mo = sums of g' and rho x g'.
   // walk 2a accumulates the totals, walk 2b peels off the links at or below each joint.
+#if TOPAY_MANI_SKIP_IDLE
+  // No active lane has a force on any sphere: every L is +-0, the walks' sums F and Mo stay +0.0 (they start there, see
+  // above) and each torque is a sum of three products of a finite axis component with +0.0, that is +0.0 or -0.0.  The
+  // seven words take +0.0 without the two chains of rotations.  Where a walk would have left -0.0 the difference does not
+  // travel: the joint limits below add a nonzero term to the word or leave it, and sample_rest() and the row accumulation
+  // of the gradient phase read the word only as a term of sums that start at +0.0 (qacc, aq[][]), where +0.0 and -0.0 add
+  // the same.  (The cosines parked in the words are not needed on this path.)
+  if (forced_any == 0) {
+#pragma unroll
+    for (int i = 0; i < 7; i++) mg_lds[i * 64] = 0.0;
+  } else {
+#endif
   double Fx = 0, Fy = 0, Fz = 0, Mx = 0, My = 0, Mz = 0;
   {
     double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
@@ -351,6 +401,9 @@ __device__ __noinline__ ManiOut manipulator_block(const TOPAY_GLB DevMap* mp, ld
       joint_rotate(R, i, cqi_, sq[i]);
     }
   }
+#if TOPAY_MANI_SKIP_IDLE
+  }
+#endif
   MSTAMP(4);  // walks 2a/2b
   MMARK(4);
   // joint position limits — moma_traj_opt.cpp:1616-1666 (symmetric joint_pos_limit_max, reference quirk); the rare
