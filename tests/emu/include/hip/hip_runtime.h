@@ -110,11 +110,11 @@ inline void barrier() {
   s.lanes[me].wait_gen = s.blk_gen;
   swapcontext(&s.lanes[me].ctx, &s.sched);
 }
-inline void run_block(unsigned bx, size_t shmem_bytes, const std::function<void()>& body) {
+inline void run_block(unsigned bx, unsigned by, size_t shmem_bytes, const std::function<void()>& body) {
   State& s = S();
   const int nl = (int)(s.bdim.x * s.bdim.y * s.bdim.z);
   s.nl = nl;
-  s.bid = {bx, 0, 0};
+  s.bid = {bx, by, 0};
   s.body = body;
   static const size_t STK = 1 << 20;
   if ((int)s.lanes.size() < nl) s.lanes.resize(nl);
@@ -350,5 +350,7 @@ inline void hipLaunchKernelGGL(K kernel, dim3 grid, dim3 block, size_t shmem, hi
   hip_emu::State& s = hip_emu::S();
   s.bdim = block;
   s.gdim = grid;
-  for (unsigned b = 0; b < grid.x; b++) hip_emu::run_block(b, shmem, [&]() { kernel(args...); });
+  // blocks along x and y (the field construction's launches number the maps of a batch along y); no kernel uses grid.z
+  for (unsigned by = 0; by < grid.y; by++)
+    for (unsigned b = 0; b < grid.x; b++) hip_emu::run_block(b, by, shmem, [&]() { kernel(args...); });
 }

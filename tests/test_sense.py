@@ -390,9 +390,10 @@ def test_commit_of_consecutive_slots(backend):
     """23 x 23 x 12: neither grid of a run of 3 ends on a 16-byte boundary.
 
     What this compares is one backend with itself: one commit of three slots against three commits of one.  On the device the first
-    goes through the field construction as ONE batch of three maps, which nothing independent checks here: the emulator commits a run
-    slot by slot (its launches have no map dimension), so under it both sides take the same path, and test_commit's comparison with
-    topay_build_esdf_fields covers single slots only."""
+    goes through the field construction as ONE batch of three maps; under the emulator topay_sense_commit hands a run over slot by
+    slot, so there both sides take the same path.  The independent check of that batched construction is in tests/test_edt_exact.py
+    (test_sense_commit_of_consecutive_slots_against_the_definition): the same three slots, every field against the brute-force
+    definition computed from the slot's own occupancy grids, on the device as well."""
     opt, slots = _opt(backend), [10, 11, 12]
     opt.sense_reset(slots, **GRID_ODD)
     clouds = [_cloud(300, 40 + k, spread=1.1) for k in range(3)]

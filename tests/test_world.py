@@ -3,9 +3,10 @@ rasteriser's occupancy grids, the fields built from them, the scenario samplers 
 harness (harness/workload.hpp) with equal seeds.  Everything is compared bit for bit; a sampler instance may differ only at a
 tie of a collision threshold (the rule of tests/test_collision.py), at most one per test.
 
-Every case runs twice: through the CPU lane emulator of the kernel sources and, marked gpu, on the device.  The emulator runs
-the blocks of a launch along x only, so the field construction (blockIdx.y = map) serves one map per call there: cases that
-need the fields of several maps build them one call per map on the emulator and in one call on the device.
+Every case runs twice: through the CPU lane emulator of the kernel sources and, marked gpu, on the device.  Cases that need
+the fields of several maps build them one call per map on the emulator and in one call on the device (they were written when
+the emulator ran the blocks of a launch along x only; the batched construction, blockIdx.y = map, is checked on both in
+tests/test_edt_exact.py).
 
 Shapes: the default 20 x 20 x 1.6 m map where the issue names it, otherwise 10 x 10 m (100 x 100 cells, the obstacle counts
 scaled as World::build scales them) -- the smallest map on which a start and a goal 3 m apart fit.

@@ -268,8 +268,9 @@ topay_status topay_sense_commit(topay_ctx* c, int n, const int* map_ids) {
   HIPCHK(hipSetDevice(c->device));
   if (topay_status ws = wait_pending(c)) return ws;   // inputs of a solve in flight stay untouched
   DevTimer& tm = c->sense.timer[SenseState::kCommit];
-  // Runs of consecutive slots on one grid go through the field construction together (its launches take a batch of maps).  The lane
-  // emulator runs the blocks of a launch along x only (blockIdx.y = map stays 0), so there a run is one slot.
+  // Runs of consecutive slots on one grid go through the field construction together (its launches take a batch of maps).  Under
+  // the lane emulator a run stays one slot: an emulator that walks the blocks of a launch along x only (blockIdx.y = map stays 0)
+  // would build the first map of a run alone.  The batched construction is checked in tests/test_edt_exact.py.
 #ifdef TOPAY_CPU_EMU
   const int max_run = 1;
 #else
