@@ -596,6 +596,47 @@ topay_status topay_track_clear(topay_ctx* ctx, int robot);
  * topay_track_safe_ms: device time (HIP events around the launch) of the last sweep. */
 topay_status topay_track_safe(topay_ctx* ctx, int n, const int* robots, const int* map_ids, int* safe, int* first_hit, double* hit);
 topay_status topay_track_safe_ms(topay_ctx* ctx, double* ms);
+/* Tracked trajectories sampled on the device: where n robots are at many times each, how they move there and how much room
+ * they have.  Slot robots[k]'s trajectory `which` (1 end_traj, 2 global_traj) at M samples in all; row s of an output belongs
+ * to sample s, and `what` (a sum of TOPAY_SAMPLE_*) says which outputs are computed.  At a sample's time t:
+ *   state      [M][10]     MomaTraj::getState(t) (moma_traj_opt.h:113-137): x, y, theta, q1..q7; t clamped to [0, T]
+ *   dstate     [M][10]     getDState(t) (moma_traj_opt.h:149-158): ds/dt, dtheta/dt, 0, the seven joint rates; t clamped
+ *   ee_pose    [M][9]      MomaParam::getFKPose of that state (moma_param.h:339-373), the 9-vector of topay_ee_pose
+ *   centres    [M][12][3]  the collision spheres' centres in the world frame (MomaParam::getColliPts, moma_param.h:203-247), as
+ *                          the safety sweep forms them (planner.cpp:619)
+ *   distance   [M][13]     what the sweep compares (planner.cpp:613-624): column 0 GridMap::getDistance2d of the chassis xy,
+ *                          columns 1..12 getDistance3d of sphere i (grid_map.h:256-362), on map slot map_ids[k] AS IT IS NOW; a
+ *                          point outside the map is 1e10 away
+ *   clearance  [M][13]     distance minus the body's full radius: chassis_colli_radius, colli_point_radius of sphere i (not the
+ *                          sweep's 0.99 of it); outside the map 1e10 - r
+ *   duration   [n]         getTotalDuration (minco.hpp:304-313) of robot k's trajectory; needs no bit of `what`
+ * clearance + r is the distance again only while r / 2 <= distance <= 2 r, where the subtraction is exact; closer or further it
+ * rounds.  So `distance` is there beside `clearance`: hit[k][1] of topay_track_safe IS distance[first_hit[k][0]][first_hit[k][1]] of
+ * the grid t0 = 0, step = 0.01, and the sweep's test is distance < 0.99 r.
+ * topay_track_sample takes ragged times: robot k's are times[time_off[k] .. time_off[k + 1] - 1], time_off[0] = 0, M =
+ * time_off[n]; a robot may have none.  topay_track_sample_grid takes a grid per robot: sample j of robot k (row k m + j) is the
+ * running sum t0[k], += step (j additions, the `for (t = t0; ..; t += step)` of the reference's loops, planner.cpp:608, 719); m
+ * samples always, no cut at T.
+ * Every output pointer may be NULL, and an output whose bit is clear or whose pointer is NULL is neither computed nor written.
+ * An output may be host memory or memory of the context's device (a torch tensor's data_ptr(), 8-byte aligned): the pointer
+ * is asked (hipPointerGetAttributes); device memory is written by the kernel where it lies, and the entry returns once that is
+ * done.  A robot may be named more than once.  The entries only read: trajectories, the resident batch, the plan store and the
+ * maps stay as they are.
+ * TOPAY_ERR_NO_TRAJ: a slot without the trajectory `which` names.  TOPAY_ERR_NO_MAP: TOPAY_SAMPLE_CLEARANCE or _DISTANCE and a map
+ * slot that is not set (TOPAY_SAMPLE_CENTRES needs no map, and map_ids may be NULL without those two bits).
+ * TOPAY_ERR_INVALID_ARG: n <= 0, which outside 1..2, what without a bit or with an unknown one, a robot slot out of range,
+ * TOPAY_SAMPLE_CLEARANCE or _DISTANCE with map_ids NULL, time_off that decreases or does not start at 0, a time, t0 or step
+ * that is not finite and below 1e9 in magnitude (checked before any launch), m < 0, n m of 2^31 or more, an output on another
+ * device.  topay_track_sample_ms: device time (HIP events around the launch) of the last sampling kernel. */
+enum { TOPAY_SAMPLE_STATE = 1, TOPAY_SAMPLE_DSTATE = 2, TOPAY_SAMPLE_EE_POSE = 4, TOPAY_SAMPLE_CLEARANCE = 8, TOPAY_SAMPLE_CENTRES = 16,
+       TOPAY_SAMPLE_DISTANCE = 32 };
+topay_status topay_track_sample(topay_ctx* ctx, int n, const int* robots, int which, const int* map_ids /* n */,
+                                const int* time_off /* n + 1 */, const double* times, int what, double* state, double* dstate,
+                                double* ee_pose, double* clearance, double* centres, double* duration, double* distance);
+topay_status topay_track_sample_grid(topay_ctx* ctx, int n, const int* robots, int which, const int* map_ids /* n */,
+                                     const double* t0 /* n */, double step, int m, int what, double* state, double* dstate,
+                                     double* ee_pose, double* clearance, double* centres, double* duration, double* distance);
+topay_status topay_track_sample_ms(topay_ctx* ctx, double* ms);
 /* The endpoints of a replan, Planner::replanCallback (planner.cpp:708-731), for n robots:
  *   start[k]    end_traj.getState(t_s), t_s = t_since_replan[k] + planning_budget
  *   start_v[k]  end_traj.getDState(t_s) (moma_traj_opt.h:149-158): ds/dt, dtheta/dt, 0, the seven joint rates; t clamped to [0, T]

@@ -216,6 +216,12 @@ def load(path=None):
         L.topay_replan_inputs.argtypes = [C.c_void_p, C.c_int, c_ip, c_dp, c_dp, c_dp, C.c_double, C.c_double, c_dp, c_dp, c_dp, c_ip]
         L.topay_replan_calls.argtypes = [C.c_void_p, C.c_int, c_ip, c_ip, c_dp, c_dp, c_dp, c_dp, C.c_double, C.c_double, C.c_double,
                                          C.POINTER(PlanParams), C.c_ulonglong, c_ip, c_dp, c_ip, c_ip]
+    if hasattr(L, "topay_track_sample"):   # (older builds of the library under tools/libs, A/B runs)
+        # the outputs as addresses: a numpy array's or a device tensor's
+        outs = [C.c_void_p] * 7
+        L.topay_track_sample.argtypes = [C.c_void_p, C.c_int, c_ip, C.c_int, c_ip, c_ip, c_dp, C.c_int] + outs
+        L.topay_track_sample_grid.argtypes = [C.c_void_p, C.c_int, c_ip, C.c_int, c_ip, c_dp, C.c_double, C.c_int, C.c_int] + outs
+        L.topay_track_sample_ms.argtypes = [C.c_void_p, c_dp]
     if hasattr(L, "topay_ee_goals"):   # (older builds of the library under tools/libs, A/B runs)
         L.topay_ee_default_params.argtypes = [C.POINTER(EeParams)]
         L.topay_ee_default_params.restype = None
@@ -498,6 +504,11 @@ def _dp(a):
 def _ip(a):
     return a.ctypes.data_as(c_ip) if a is not None else None
 
+
+# TOPAY_SAMPLE_* of include/topay.h; the outputs of track_sample as (name, bit, shape of a row)
+SAMPLE_STATE, SAMPLE_DSTATE, SAMPLE_EE_POSE, SAMPLE_CLEARANCE, SAMPLE_CENTRES, SAMPLE_DISTANCE = 1, 2, 4, 8, 16, 32
+SAMPLE_OUTPUTS = (("state", SAMPLE_STATE, (10,)), ("dstate", SAMPLE_DSTATE, (10,)), ("ee_pose", SAMPLE_EE_POSE, (9,)),
+                  ("clearance", SAMPLE_CLEARANCE, (13,)), ("centres", SAMPLE_CENTRES, (12, 3)), ("distance", SAMPLE_DISTANCE, (13,)))
 
 STAT_KEYS = ["stage1_ret", "stage1_iters", "stage1_evals", "stage2_last_ret", "stage2_iters", "stage2_evals",
              "alm_outer", "sum_bound"]
@@ -1173,6 +1184,67 @@ class MomaTrajOptBatch:
         """Device time of the last track_safe (or of the sweep of the last replan_calls), milliseconds."""
         ms = np.zeros(1)
         _chk(self.L, self.L.topay_track_safe_ms(self.h, _dp(ms)))
+        return float(ms[0])
+
+    def _sample_outs(self, what, n, rows, out):
+        """The seven output addresses of topay_track_sample / _grid in the order of the C entry, and the dict the call returns:
+        a new numpy array per selected output, or the caller's tensor of `out` (float64, contiguous, of the output's shape)."""
+        if what <= 0 or what >= 64:
+            raise ValueError("what must be a sum of SAMPLE_* bits")
+        out = dict(out or {})
+        res, ptr = {}, {}
+        for name, bit, tail in SAMPLE_OUTPUTS + (("duration", 0, ()),):
+            if bit and not what & bit:
+                ptr[name] = None
+                continue
+            shape = ((n,) if name == "duration" else (rows,)) + tail
+            t = out.pop(name, None)
+            if t is None:
+                res[name] = np.zeros(shape)
+                ptr[name] = res[name].ctypes.data
+            else:   # a torch tensor, by its methods: torch is not imported here
+                if str(t.dtype) != "torch.float64" or not t.is_contiguous() or tuple(t.shape) != shape:
+                    raise ValueError(f"out[{name!r}] must be a contiguous float64 tensor of shape {shape}")
+                res[name] = t
+                ptr[name] = t.data_ptr()
+        if out:
+            raise ValueError(f"out has entries that `what` does not select: {sorted(out)}")
+        return [ptr[k] for k in ("state", "dstate", "ee_pose", "clearance", "centres", "duration", "distance")], res
+
+    def track_sample(self, robots, times, which=1, map_ids=None, what=SAMPLE_STATE | SAMPLE_DSTATE, out=None):
+        """The robots' tracked trajectories (which: 1 end_traj, 2 global_traj) at ragged times: times[k] is the sequence of
+        robot k's times (it may be empty), row sum(len(times[:k])) + j of an output is its sample j.  what: a sum of SAMPLE_*;
+        CLEARANCE and DISTANCE need map_ids.  Returns a dict of the selected outputs (SAMPLE_OUTPUTS: state [M, 10], dstate
+        [M, 10], ee_pose [M, 9], clearance [M, 13], centres [M, 12, 3], distance [M, 13]) and "duration" [n], numpy arrays.
+        out: a dict of torch tensors on the context's device under the same names (float64, contiguous, of those shapes): the
+        kernel writes into them, they are returned in place of arrays, and the work on them is done when the call returns."""
+        rb = np.ascontiguousarray(robots, dtype=np.int32)
+        n = len(rb)
+        if len(times) != n:
+            raise ValueError("times must hold one sequence per robot")
+        ts = [np.asarray(t, dtype=np.float64).reshape(-1) for t in times]
+        off = np.concatenate([[0], np.cumsum([len(t) for t in ts])]).astype(np.int32)
+        flat = np.ascontiguousarray(np.concatenate(ts)) if n else np.zeros(0)
+        mid = None if map_ids is None else np.ascontiguousarray(np.broadcast_to(np.asarray(map_ids, dtype=np.int32), (n,)))
+        ptrs, res = self._sample_outs(int(what), n, int(off[-1]), out)
+        _chk(self.L, self.L.topay_track_sample(self.h, n, _ip(rb), int(which), _ip(mid), _ip(off), _dp(flat), int(what), *ptrs))
+        return res
+
+    def track_sample_grid(self, robots, t0, step, m, which=1, map_ids=None, what=SAMPLE_STATE | SAMPLE_DSTATE, out=None):
+        """As track_sample on a grid per robot: sample j of robot k (row k m + j) at the running sum t0[k], += step; m samples
+        always, beyond the trajectory's end the clamped state."""
+        rb = np.ascontiguousarray(robots, dtype=np.int32)
+        n = len(rb)
+        t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, dtype=np.float64), (n,)))
+        mid = None if map_ids is None else np.ascontiguousarray(np.broadcast_to(np.asarray(map_ids, dtype=np.int32), (n,)))
+        ptrs, res = self._sample_outs(int(what), n, n * int(m), out)
+        _chk(self.L, self.L.topay_track_sample_grid(self.h, n, _ip(rb), int(which), _ip(mid), _dp(t0), float(step), int(m), int(what), *ptrs))
+        return res
+
+    def track_sample_ms(self):
+        """Device time of the last track_sample / track_sample_grid kernel, milliseconds."""
+        ms = np.zeros(1)
+        _chk(self.L, self.L.topay_track_sample_ms(self.h, _dp(ms)))
         return float(ms[0])
 
     # ---- the tracking controller and the fake robot (topay_host_mpc.h)

@@ -277,15 +277,15 @@ struct FrontState {
 };
 
 // Tracked trajectories (topay_host_track.h): the arena, the slots' descriptors (host: what the kernels are handed per call),
-// the upload block of topay_track_set, the inputs / outputs of the sweep and endpoint kernels, the device time of the last
-// k_track_safe launch.
+// the upload block of topay_track_set, the inputs / outputs of the sweep, endpoint and sampling kernels, the device time of the
+// last k_track_safe and of the last k_track_sample launch.
 struct TrackSlot { topay::TrackDesc d[2] = {{0, 0, 0}, {0, 0, 0}}; long long cap[2] = {0, 0}; double T[2] = {0, 0}; };   // [0] end_traj, [1] global_traj
 struct TrackState {
   DevBuf arena, stage, io;
   size_t used = 0;   // doubles of the arena handed out
   std::vector<TrackSlot> slots;
-  DevTimer safe_timer;
-  double safe_ms = 0.0;
+  DevTimer safe_timer, sample_timer;
+  double safe_ms = 0.0, sample_ms = 0.0;
   const topay::TrackDesc* find(int robot, int w) const { return slots.empty() || slots[robot].d[w].N <= 0 ? nullptr : &slots[robot].d[w]; }
 };
 

@@ -1,6 +1,6 @@
 // Host side of the C-ABI, part 9: tracked trajectories (end_traj / global_traj of every robot slot), the one check of the robot
-// slots an entry names, the safety sweep, the endpoints of a replan and the replanning cycle (topay_track.h;
-// Planner::safeCallback and replanCallback).
+// slots an entry names, the safety sweep, the endpoints of a replan, the sampling of tracked trajectories and the replanning
+// cycle (topay_track.h; Planner::safeCallback and replanCallback).
 
 #pragma once
 
@@ -166,6 +166,121 @@ static topay_status track_endpoints_impl(topay_ctx* c, int n, const int* robots,
   return TOPAY_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Sampling (k_track_sample).  An output of topay_track_sample / _grid may lie on the host or on the device.  The host code had no
+// convention for device outputs before these entries (every other entry copies back), so the pointer itself is asked:
+// hipPointerGetAttributes.  Device memory of the context's device is written by the kernel where it lies; anything else (plain,
+// pinned or managed host memory) gets a block of the io buffer and a copy back.
+// ---------------------------------------------------------------------------------------------------------------------
+struct SampleOut {
+  double* user = nullptr;   // the caller's pointer; null: not asked for
+  double* dev = nullptr;    // where the kernel writes
+  size_t count = 0;         // doubles
+  bool direct = false;      // dev == user
+};
+static topay_status sample_out(topay_ctx* c, double* user, bool asked, size_t count, SampleOut& o) {
+  o = SampleOut();
+  if (!user || !asked) return TOPAY_OK;
+  o.user = user; o.count = count;
+#ifndef TOPAY_CPU_EMU
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, user) != hipSuccess) (void)hipGetLastError();   // memory the runtime has never seen: the host's
+  else if (at.type == hipMemoryTypeDevice) {
+    if (at.device != c->device) { set_err("topay_track_sample: an output lies on another device than the context"); return TOPAY_ERR_INVALID_ARG; }
+    o.direct = true; o.dev = user;
+  }
+#endif
+  return TOPAY_OK;
+}
+
+struct TrackSampleOuts { double *state, *dstate, *ee_pose, *clearance, *centres, *duration, *distance; };
+
+// Robot k's samples are rows off[k] .. off[k + 1] - 1.  times: the rows' times, or null for a grid call (t0[k], += step).
+static topay_status track_sample_impl(topay_ctx* c, int n, const int* robots, int w, const int* map_ids, const std::vector<int>& off, const double* times,
+                                      const double* t0, double step, int what, const TrackSampleOuts& U) {
+  const size_t N = (size_t)n, M = (size_t)off[N];
+  // the work table (TrackSampleItem)
+  std::vector<topay::TrackDesc> desc(N);
+  std::vector<topay::TrackSampleItem> items;
+  for (int k = 0; k < n; k++) {
+    desc[k] = *c->track.find(robots[k], w);
+    const int cnt = off[k + 1] - off[k];
+    double t = times ? 0.0 : t0[k];
+    int b = 0;
+    do {
+      topay::TrackSampleItem I;
+      I.robot = k; I.row0 = off[k] + 64 * b; I.count = std::min(64, cnt - 64 * b); I.head = b == 0; I.t_first = t;
+      items.push_back(I);
+      if (!times)
+        for (int j = 0; j < 64; j++) t += step;   // (the sums of track_times, in its order)
+      b++;
+    } while (64 * b < cnt);
+  }
+  const size_t NI = items.size();
+  // the outputs: what is asked for and has somewhere to go
+  const int K = topay::kSampleBodies;
+  SampleOut o_st, o_dv, o_ee, o_cl, o_ce, o_du, o_di;
+  topay_status s;
+  if ((s = sample_out(c, U.state, what & topay::kSampleState, 10 * M, o_st)) != TOPAY_OK || (s = sample_out(c, U.dstate, what & topay::kSampleDState, 10 * M, o_dv)) != TOPAY_OK ||
+      (s = sample_out(c, U.ee_pose, what & topay::kSampleEePose, 9 * M, o_ee)) != TOPAY_OK || (s = sample_out(c, U.clearance, what & topay::kSampleClearance, K * M, o_cl)) != TOPAY_OK ||
+      (s = sample_out(c, U.centres, what & topay::kSampleCentres, 3 * TOPAY_NSPH * M, o_ce)) != TOPAY_OK || (s = sample_out(c, U.duration, true, N, o_du)) != TOPAY_OK ||
+      (s = sample_out(c, U.distance, what & topay::kSampleDistance, K * M, o_di)) != TOPAY_OK)
+    return s;
+  SampleOut* outs[7] = {&o_st, &o_dv, &o_ee, &o_cl, &o_ce, &o_du, &o_di};
+  int eff = 0;
+  const int bit[7] = {topay::kSampleState, topay::kSampleDState, topay::kSampleEePose, topay::kSampleClearance, topay::kSampleCentres, 0, topay::kSampleDistance};
+  for (int a = 0; a < 7; a++)
+    if (outs[a]->user) eff |= bit[a];
+  if (eff == 0 && !o_du.user) return TOPAY_OK;
+  const bool need_map = eff & (topay::kSampleClearance | topay::kSampleDistance);
+  topay::TrackSampleItem* d_items; topay::TrackDesc* d_desc; int* d_mid; double* d_times;
+  auto lay = [&](Carver& k) {
+    for (SampleOut* o : outs)
+      if (o->user && !o->direct) o->dev = k.take<double>(o->count);
+    d_times = k.take<double>(times ? M : 0); d_items = k.take<topay::TrackSampleItem>(NI); d_desc = k.take<topay::TrackDesc>(N); d_mid = k.take<int>(N);
+  };
+  if ((s = c->track.io.carve(lay)) != TOPAY_OK) return s;
+  HIPCHK(h2d(c, d_items, items.data(), NI));
+  HIPCHK(h2d(c, d_desc, desc.data(), N));
+  if (need_map) HIPCHK(h2d(c, d_mid, map_ids, N));
+  if (times && M > 0) HIPCHK(h2d(c, d_times, times, M));
+  if ((s = push_params(c)) != TOPAY_OK) return s;
+  topay::TrackSampleArgs A;
+  A.n_items = (int)NI; A.what = eff; A.items = d_items; A.desc = d_desc; A.arena = c->track.arena.as<double>(); A.map_id = d_mid;
+  A.times = times ? d_times : nullptr; A.step = step;
+  A.state = o_st.dev; A.dstate = o_dv.dev; A.ee_pose = o_ee.dev; A.clearance = o_cl.dev; A.centres = o_ce.dev; A.duration = o_du.dev; A.distance = o_di.dev;
+  const int level = eff & (topay::kSampleClearance | topay::kSampleCentres | topay::kSampleDistance) ? 2 : eff & topay::kSampleEePose ? 1 : 0;
+  void (*kern)(topay::TrackSampleArgs, const DevMap*) = level == 2 ? topay::k_track_sample<2> : level == 1 ? topay::k_track_sample<1> : topay::k_track_sample<0>;
+  HIPCHK(c->track.sample_timer.start(c->stream));
+  hipLaunchKernelGGL(kern, dim3((unsigned)NI), dim3(64), 0, c->stream, A, (const DevMap*)c->dmaps.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(c->track.sample_timer.stop(c->stream));
+  for (SampleOut* o : outs)
+    if (o->user && !o->direct && o->count > 0) HIPCHK(d2h(c, o->user, o->dev, o->count));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  (void)c->track.sample_timer.read(&c->track.sample_ms);
+  return TOPAY_OK;
+}
+
+// What both sampling entries check ahead of their times: the slots, `which`, `what`, the maps when distances are asked for.
+static topay_status track_sample_check(topay_ctx* c, int n, const int* robots, int which, const int* map_ids, int what, const char* who) {
+  if (!c || n <= 0 || !robots) return TOPAY_ERR_INVALID_ARG;
+  const std::string me(who);
+  if (which < 1 || which > 2) { set_err(me + ": which must be 1 (end_traj) or 2 (global_traj)"); return TOPAY_ERR_INVALID_ARG; }
+  if (what <= 0 || what >= 2 * topay::kSampleDistance) { set_err(me + ": what must be a sum of TOPAY_SAMPLE_* bits, at least one"); return TOPAY_ERR_INVALID_ARG; }
+  if (topay_status s = check_robot_slots(c, n, robots, 0, who)) return s;   // (in range, then the maps, then the trajectories)
+  if (what & (topay::kSampleClearance | topay::kSampleDistance)) {   // (the centres need no map)
+    if (!map_ids) { set_err(me + ": TOPAY_SAMPLE_CLEARANCE and TOPAY_SAMPLE_DISTANCE need map_ids"); return TOPAY_ERR_INVALID_ARG; }
+    if (topay_status s = check_map_slots(c, n, map_ids, kMapResident | kMap2d | kMap3d, who)) return s;
+  }
+  for (int k = 0; k < n; k++)
+    if (!c->track.find(robots[k], which - 1)) {
+      set_err(me + ": robot slot " + std::to_string(robots[k]) + (which == 1 ? " has no end_traj" : " has no global_traj"));
+      return TOPAY_ERR_NO_TRAJ;
+    }
+  return TOPAY_OK;
+}
+
 // Winners of the last planning call into the slots: device to device from the plan store.
 static topay_status track_commit_plan_impl(topay_ctx* c, int n, const int* robots, const int* call_idx, int which, int* committed) {
   PlanStore& S = c->plan_store;
@@ -267,6 +382,46 @@ topay_status topay_track_safe(topay_ctx* c, int n, const int* robots, const int*
 topay_status topay_track_safe_ms(topay_ctx* c, double* ms) {
   if (!c || !ms) return TOPAY_ERR_INVALID_ARG;
   *ms = c->track.safe_ms;
+  return TOPAY_OK;
+}
+
+topay_status topay_track_sample(topay_ctx* c, int n, const int* robots, int which, const int* map_ids, const int* time_off, const double* times, int what,
+                                double* state, double* dstate, double* ee_pose, double* clearance, double* centres, double* duration, double* distance) {
+  if (topay_status s = track_sample_check(c, n, robots, which, map_ids, what, "topay_track_sample")) return s;
+  if (!time_off || time_off[0] != 0) { set_err("topay_track_sample: time_off must be given and start at 0"); return TOPAY_ERR_INVALID_ARG; }
+  for (int k = 0; k < n; k++)
+    if (time_off[k + 1] < time_off[k]) { set_err("topay_track_sample: time_off decreases"); return TOPAY_ERR_INVALID_ARG; }
+  const std::vector<int> off(time_off, time_off + n + 1);
+  if (off[(size_t)n] > 0 && (!times || !all_finite(times, (size_t)off[(size_t)n]))) {
+    set_err("topay_track_sample: the times must be finite (below 1e9 in magnitude)");
+    return TOPAY_ERR_INVALID_ARG;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  if (topay_status ws = wait_pending(c)) return ws;
+  static const double none = 0.0;   // (a call without samples is still a ragged call)
+  const TrackSampleOuts U{state, dstate, ee_pose, clearance, centres, duration, distance};
+  return track_sample_impl(c, n, robots, which - 1, map_ids, off, times ? times : &none, nullptr, 0.0, what, U);
+}
+
+topay_status topay_track_sample_grid(topay_ctx* c, int n, const int* robots, int which, const int* map_ids, const double* t0, double step, int m, int what,
+                                     double* state, double* dstate, double* ee_pose, double* clearance, double* centres, double* duration, double* distance) {
+  if (topay_status s = track_sample_check(c, n, robots, which, map_ids, what, "topay_track_sample_grid")) return s;
+  if (!t0 || !all_finite(t0, (size_t)n) || !all_finite(&step, 1)) {
+    set_err("topay_track_sample_grid: t0 and step must be finite (below 1e9 in magnitude)");
+    return TOPAY_ERR_INVALID_ARG;
+  }
+  if (m < 0 || (long long)n * m > 0x7fffffffll) { set_err("topay_track_sample_grid: m must not be negative, n * m below 2^31"); return TOPAY_ERR_INVALID_ARG; }
+  HIPCHK(hipSetDevice(c->device));
+  if (topay_status ws = wait_pending(c)) return ws;
+  std::vector<int> off((size_t)n + 1);
+  for (int k = 0; k <= n; k++) off[(size_t)k] = k * m;
+  const TrackSampleOuts U{state, dstate, ee_pose, clearance, centres, duration, distance};
+  return track_sample_impl(c, n, robots, which - 1, map_ids, off, nullptr, t0, step, what, U);
+}
+
+topay_status topay_track_sample_ms(topay_ctx* c, double* ms) {
+  if (!c || !ms) return TOPAY_ERR_INVALID_ARG;
+  *ms = c->track.sample_ms;
   return TOPAY_OK;
 }
 

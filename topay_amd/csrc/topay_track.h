@@ -5,10 +5,13 @@
 //   k_track_safe       safeCallback: samples every 0.01 s against the map slot given in the call, first violation
 //   k_track_endpoints  replanCallback:708-731: start = getState(t_s), start_v = getDState(t_s) (moma_traj_opt.h:149-158),
 //                      local goal = first state of global_traj beyond the horizon
+//   k_track_sample     getState (moma_traj_opt.h:113-137), getDState (149-158), getFKPose (moma_param.h:339-373), the sphere
+//                      centres (getColliPts, 203-247) and their distances at many times per robot: one wave per 64 samples
 // One wave per trajectory / robot.  A tracked trajectory lies in the arena as
 //   start[4] (x, y, theta, -) | T[N] | coef[9][6N] (element d * 6N + 6i + k = coefficient of t^k: what feas_* read) |
 //   cseq[num + 1][2] (chassis xy after every 0.025 s Simpson panel)
 #pragma once
+#include "topay_ee.h"
 #include "topay_feas.h"
 
 namespace topay {
@@ -232,6 +235,121 @@ __global__ void __launch_bounds__(64, 2) k_track_endpoints(TrackEndArgs A) {
   if (!found && lane == 0) {
     for (int a = 0; a < 10; a++) A.goal[10 * (size_t)r + a] = A.global_goal[10 * (size_t)r + a];
     A.goal_source[r] = -1;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// topay_track_sample: the tracked trajectories of n robots at many times each.  The bits of `what` (TOPAY_SAMPLE_* of
+// include/topay.h) select the outputs; a row of an output belongs to one sample.
+// ---------------------------------------------------------------------------------------------------------------------
+enum : int { kSampleState = 1, kSampleDState = 2, kSampleEePose = 4, kSampleClearance = 8, kSampleCentres = 16, kSampleDistance = 32 };
+constexpr int kSampleBodies = 1 + TOPAY_NSPH;   // chassis, spheres
+
+// One work item = one wave: `count` <= 64 consecutive samples of one robot of the call, rows row0 .. row0 + count - 1 of the
+// outputs.  The host flattens the ragged ranges into these, so a robot with 1000 samples and one with 1 share no trip count.
+// Every robot has an item, also one without samples (count 0): its first item writes the robot's duration.
+struct TrackSampleItem {
+  int robot;       // position among the n robots of the call
+  int row0;
+  int count;
+  int head;        // the robot's first item
+  double t_first;  // grid calls: the running sum t0, += step up to sample row0 of the robot, formed by the host
+};
+struct TrackSampleArgs {
+  int n_items, what;
+  const TrackSampleItem* items;
+  const TrackDesc* desc;    // [n]
+  const double* arena;
+  const int* map_id;        // [n]; read only for kSampleClearance / kSampleDistance
+  const double* times;      // [rows]; null: a grid call, sample j of an item at t_first, += step (track_times)
+  double step;
+  double *state, *dstate, *ee_pose, *clearance, *centres, *duration, *distance;   // null or of the call's rows (duration: [n])
+};
+
+// A row of R doubles, contiguous per lane, as 16-byte stores (R odd: and one of 8).  Rows are 8-byte aligned only (9 and 13
+// doubles per row; a caller's device tensor), which global stores of this width take.
+typedef double track_pair __attribute__((vector_size(16), aligned(8)));
+template <int R> __device__ __forceinline__ void track_store_row(double* dst, const double (&v)[R]) {
+#ifndef TOPAY_CPU_EMU
+#pragma unroll
+  for (int a = 0; a + 1 < R; a += 2) {
+    track_pair p;
+    p[0] = v[a]; p[1] = v[a + 1];
+    *(TOPAY_GLB track_pair*)(dst + a) = p;
+  }
+  if (R & 1) dst[R - 1] = v[R - 1];
+#else
+  for (int a = 0; a < R; a++) dst[a] = v[a];
+#endif
+}
+
+// Lanes <-> samples.  LEVEL is what the launch needs at most: 0 getState / getDState, 1 and getFKPose, 2 and the twelve
+// spheres with their lookups -- three kernels, so that a call for states alone does not hold the registers of the walk along
+// the arm.  Inside a kernel `what` (wave-uniform) selects; an output whose bit is clear is neither computed nor written.
+// Every figure is the device function of its other user: track_state / track_dstate (k_track_endpoints), ee_pose_of (k_ee_pose),
+// sphere_centres, feas_dist2d / feas_dist3d (k_track_safe).  No LDS: a lane's row is contiguous (80 bytes of a state), so the
+// 16-byte stores of a wave fill whole lines of its 5 KB between them; a transposed write through LDS would add a round trip
+// to save nothing but the order in which those lines fill.
+template <int LEVEL>
+__global__ void __launch_bounds__(64, 2) k_track_sample(TrackSampleArgs A, const DevMap* maps) {
+  const int it = blockIdx.x;
+  if (it >= A.n_items) return;
+  const int lane = threadIdx.x & 63;
+  const TrackSampleItem I = A.items[it];
+  const int k = __builtin_amdgcn_readfirstlane(I.robot), count = __builtin_amdgcn_readfirstlane(I.count);
+  const int what = A.what;
+  const FeasIO F = track_io(A.arena, A.desc[k]);
+  const double Ttot = track_duration(F);
+  if (I.head && lane == 0 && A.duration) A.duration[k] = Ttot;
+  double tg;
+  if (A.times) tg = lane < count ? A.times[(size_t)I.row0 + lane] : 0.0;
+  else {
+    double t = I.t_first;
+    tg = track_times(t, A.step, lane);
+  }
+  if (lane >= count) return;
+  const size_t row = (size_t)I.row0 + lane;
+  if (what & kSampleDState) {
+    double sv[10];
+    track_dstate(F, Ttot, tg, sv);
+    track_store_row<10>(A.dstate + 10 * row, sv);
+  }
+  if (!(what & ~kSampleDState)) return;
+  double st[10];
+  track_state(F, Ttot, tg, st);
+  if (what & kSampleState) track_store_row<10>(A.state + 10 * row, st);
+  if (LEVEL >= 1 && (what & kSampleEePose)) {
+    double po[9];
+    ee_pose_of(dev_params(), st, po);
+    track_store_row<9>(A.ee_pose + 9 * row, po);
+  }
+  if (LEVEL >= 2 && (what & (kSampleClearance | kSampleCentres | kSampleDistance))) {
+    dev_params_ref P = dev_params();
+    double Px[TOPAY_NSPH], Py[TOPAY_NSPH], Pz[TOPAY_NSPH];
+    sphere_centres(st, Px, Py, Pz);
+    if (what & kSampleCentres) {
+      double cc[3 * TOPAY_NSPH];
+#pragma unroll
+      for (int s = 0; s < TOPAY_NSPH; s++) { cc[3 * s] = Px[s]; cc[3 * s + 1] = Py[s]; cc[3 * s + 2] = Pz[s]; }
+      track_store_row<3 * TOPAY_NSPH>(A.centres + 3 * TOPAY_NSPH * row, cc);
+    }
+    if (what & (kSampleClearance | kSampleDistance)) {
+      const TOPAY_GLB DevMap* mp = (const TOPAY_GLB DevMap*)(maps + __builtin_amdgcn_readfirstlane(A.map_id[k]));
+      const DevMap M = load_map(mp);
+      // the twelve lookups are independent and branch-free (esdf3d_query): unrolled, their gathers go out ahead of the arithmetic
+      double d[kSampleBodies];
+#pragma unroll
+      for (int s = 0; s < TOPAY_NSPH; s++) d[1 + s] = feas_dist3d(M, Px[s], Py[s], Pz[s]);
+      d[0] = feas_dist2d(M, st[0], st[1]);
+      if (what & kSampleDistance) track_store_row<kSampleBodies>(A.distance + kSampleBodies * row, d);
+      if (what & kSampleClearance) {
+        double cl[kSampleBodies];
+        cl[0] = d[0] - P.chassis_colli_radius;
+#pragma unroll
+        for (int s = 0; s < TOPAY_NSPH; s++) cl[1 + s] = d[1 + s] - P.sph_r[s];
+        track_store_row<kSampleBodies>(A.clearance + kSampleBodies * row, cl);
+      }
+    }
   }
 }
 
