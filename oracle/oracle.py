@@ -174,6 +174,19 @@ class Oracle:
                 "alm_outer", "sum_bound"]
         return dict(zip(keys, s.tolist()))
 
+    def round_stats(self, cap=64):
+        """The ALM rounds of the last solve one by one: list of dicts ret / iters / evals / sum_bound (stage 2's L-BFGS runs)."""
+        a = np.zeros(4 * cap, dtype=np.int32)
+        n = min(self.L.orc_get_round_stats(self.h, cap, _ip(a)), cap)
+        return [dict(zip(("ret", "iters", "evals", "sum_bound"), a[4 * r:4 * r + 4].tolist())) for r in range(n)]
+
+    def get_param(self, name):
+        self.L.orc_get_param.restype = C.c_double
+        v = self.L.orc_get_param(self.h, name.encode())
+        if v != v:
+            raise KeyError(name)
+        return v
+
     def traj_cost(self):
         return self.L.orc_traj_cost(self.h)
 

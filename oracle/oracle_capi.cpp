@@ -38,14 +38,36 @@ int orc_set_param(void* hh, const char* name, double v) {
   SETD(s2_mani_acc_weight) SETD(s2_mean_time_weight) SETD(alm_tolerance) SETI(alm_max_outer) SETI(alm_work_budget) SETI(exact_chain)
 #undef SETD
 #undef SETI
-  if (n == "s1_max_iterations") { p.s1_lbfgs.max_iterations = (int)v; return 0; }
-  if (n == "s2_max_iterations") { p.s2_lbfgs.max_iterations = (int)v; return 0; }
-  if (n == "s1_mem_size") { p.s1_lbfgs.mem_size = (int)v; return 0; }
-  if (n == "s2_mem_size") { p.s2_lbfgs.mem_size = (int)v; return 0; }
-  if (n == "s1_delta") { p.s1_lbfgs.delta = v; return 0; }
-  if (n == "s2_delta") { p.s2_lbfgs.delta = v; return 0; }
-  if (n == "s2_past") { p.s2_lbfgs.past = (int)v; return 0; }
+  // every field of both stages' L-BFGS blocks: "s1_<field>" / "s2_<field>".  (s1_past is accepted for completeness: optimize()
+  // replaces the stage-1 window by the candidate's own, s1_normal_past or s1_shot_path_past -- MTO_CPP:359-366.)
+  if (n.size() > 3 && (n.compare(0, 3, "s1_") == 0 || n.compare(0, 3, "s2_") == 0)) {
+    LbfgsParam& lp = n[1] == '1' ? p.s1_lbfgs : p.s2_lbfgs;
+    const std::string f = n.substr(3);
+#define LPD(field) if (f == #field) { lp.field = v; return 0; }
+#define LPI(field) if (f == #field) { lp.field = (int)v; return 0; }
+    LPI(mem_size) LPI(past) LPI(max_linesearch) LPI(max_iterations)
+    LPD(g_epsilon) LPD(delta) LPD(min_step) LPD(max_step) LPD(f_dec_coeff) LPD(s_curv_coeff) LPD(cautious_factor) LPD(machine_prec)
+#undef LPD
+#undef LPI
+  }
   return -1;
+}
+// read-back of the same names (the known-answer tests check that a set value arrived in the field it names)
+double orc_get_param(void* hh, const char* name) {
+  const Params& p = ((OracleHandle*)hh)->opt.prm;
+  std::string n(name);
+  if (n == "s1_normal_past") return p.s1_normal_past;
+  if (n == "s1_shot_path_past") return p.s1_shot_path_past;
+  if (n == "alm_max_outer") return p.alm_max_outer;
+  if (n.size() > 3 && (n.compare(0, 3, "s1_") == 0 || n.compare(0, 3, "s2_") == 0)) {
+    const LbfgsParam& lp = n[1] == '1' ? p.s1_lbfgs : p.s2_lbfgs;
+    const std::string f = n.substr(3);
+#define LPG(field) if (f == #field) return (double)lp.field;
+    LPG(mem_size) LPG(past) LPG(max_linesearch) LPG(max_iterations)
+    LPG(g_epsilon) LPG(delta) LPG(min_step) LPG(max_step) LPG(f_dec_coeff) LPG(s_curv_coeff) LPG(cautious_factor) LPG(machine_prec)
+#undef LPG
+  }
+  return std::numeric_limits<double>::quiet_NaN();
 }
 
 // map buffers are NOT copied: caller keeps them alive
@@ -158,6 +180,15 @@ void orc_get_stats(void* hh, int s[8]) {
   const SolveStats& st = ((OracleHandle*)hh)->opt.stats;
   s[0] = st.stage1_ret; s[1] = st.stage1_iters; s[2] = st.stage1_evals; s[3] = st.stage2_last_ret;
   s[4] = st.stage2_iters; s[5] = st.stage2_evals; s[6] = st.alm_outer; s[7] = st.sum_bound;
+}
+// the ALM rounds of the last solve one by one: rows of (return code, iterations, evaluations, sum of bound); returns the rounds
+int orc_get_round_stats(void* hh, int cap, int* out4) {
+  const SolveStats& st = ((OracleHandle*)hh)->opt.stats;
+  const int n = (int)st.round_ret.size();
+  for (int r = 0; r < n && r < cap; r++) {
+    out4[4 * r] = st.round_ret[r]; out4[4 * r + 1] = st.round_iters[r]; out4[4 * r + 2] = st.round_evals[r]; out4[4 * r + 3] = st.round_sum_bound[r];
+  }
+  return n;
 }
 void orc_debug_counters(long long* out2) { out2[0] = g_dbg_ls_evals; out2[1] = g_dbg_ftest_fail; }
 double orc_traj_cost(void* hh) { return ((OracleHandle*)hh)->opt.traj_cost; }
@@ -430,14 +461,9 @@ void orc_esdf_query(void* hh, int dim, const double* pos, double* dist, double* 
   else h->map.getDisWithGradI3d(pos, *dist, grad);
 }
 // L-BFGS on the n-d Rosenbrock function / a diagonal quadratic (kind 0/1) with the stage-`stage` parameter set
-int orc_lbfgs_test(int kind, int n, int stage, double* x, double* f, int* iters, int* evals) {
-  Params p;
-  LbfgsParam lp = stage == 1 ? p.s1_lbfgs : p.s2_lbfgs;
-  std::vector<double> xx(x, x + n);
-  LbfgsStats st;
-  EvalFn fn;
+static EvalFn textbook_fn(int kind, int n) {
   if (kind == 0)
-    fn = [n](const std::vector<double>& v, std::vector<double>& g) {
+    return [n](const std::vector<double>& v, std::vector<double>& g) {
       double fx = 0.0;
       g.assign(n, 0.0);
       for (int i = 0; i < n; i += 2) {
@@ -448,17 +474,64 @@ int orc_lbfgs_test(int kind, int n, int stage, double* x, double* f, int* iters,
       }
       return fx;
     };
-  else
-    fn = [n](const std::vector<double>& v, std::vector<double>& g) {
-      double fx = 0.0;
-      g.assign(n, 0.0);
-      for (int i = 0; i < n; i++) { double w = 1.0 + i; fx += 0.5 * w * (v[i] - 1.0) * (v[i] - 1.0); g[i] = w * (v[i] - 1.0); }
-      return fx;
-    };
-  int ret = lbfgs_optimize(xx, *f, fn, nullptr, lp, &st);
+  return [n](const std::vector<double>& v, std::vector<double>& g) {
+    double fx = 0.0;
+    g.assign(n, 0.0);
+    for (int i = 0; i < n; i++) { double w = 1.0 + i; fx += 0.5 * w * (v[i] - 1.0) * (v[i] - 1.0); g[i] = w * (v[i] - 1.0); }
+    return fx;
+  };
+}
+int orc_lbfgs_test(int kind, int n, int stage, double* x, double* f, int* iters, int* evals) {
+  Params p;
+  LbfgsParam lp = stage == 1 ? p.s1_lbfgs : p.s2_lbfgs;
+  std::vector<double> xx(x, x + n);
+  LbfgsStats st;
+  int ret = lbfgs_optimize(xx, *f, textbook_fn(kind, n), nullptr, lp, &st);
   std::memcpy(x, xx.data(), n * sizeof(double));
   *iters = st.iterations;
   *evals = st.evaluations;
+  return ret;
+}
+// The same two functions with the L-BFGS block of handle `hh`'s stage `stage` (orc_set_param), recording the run: row 0 of
+// xs / gs = the initial point and its gradient, row k = the iterate and gradient accepted by iteration k with its cost
+// fs[k] and line-search step steps[k] (what lbfgs.hpp hands to its progress callback); device_epl > 0 runs the vector
+// arithmetic in the device's order (one wave).  Returns the solver's code; *iters = final k, *rows = rows written (<= cap).
+int orc_lbfgs_trace(void* hh, int kind, int n, int stage, int device_epl, const double* x0, int cap, double* xs, double* gs,
+                    double* fs, double* steps, int* iters, int* evals, int* sum_bound, int* rows) {
+  const Params& p = ((OracleHandle*)hh)->opt.prm;
+  const LbfgsParam lp = stage == 1 ? p.s1_lbfgs : p.s2_lbfgs;
+  std::vector<double> xx(x0, x0 + n);
+  LbfgsStats st;
+  int nrow = 0;
+  const EvalFn base = textbook_fn(kind, n);
+  EvalFn fn = [&](const std::vector<double>& v, std::vector<double>& g) {
+    const double f = base(v, g);
+    if (nrow == 0 && cap > 0) {
+      std::memcpy(xs, v.data(), n * sizeof(double));
+      std::memcpy(gs, g.data(), n * sizeof(double));
+      fs[0] = f; steps[0] = 0.0;
+      nrow = 1;
+    }
+    return f;
+  };
+  ProgressFn pr = [&](const std::vector<double>& v, const std::vector<double>& g, double fx, double step, int k, int) {
+    if (k < cap) {
+      std::memcpy(xs + (size_t)k * n, v.data(), n * sizeof(double));
+      std::memcpy(gs + (size_t)k * n, g.data(), n * sizeof(double));
+      fs[k] = fx; steps[k] = step;
+      nrow = k + 1;
+    }
+    return 0;
+  };
+  double f = 0.0;
+  g_device_epl = device_epl;
+  g_device_nw = 1;
+  const int ret = lbfgs_optimize(xx, f, fn, pr, lp, &st);
+  g_device_epl = 0;
+  *iters = st.iterations;
+  *evals = st.evaluations;
+  *sum_bound = st.sum_bound;
+  *rows = nrow;
   return ret;
 }
 

@@ -326,3 +326,88 @@ def test_lbfgs_on_textbook_functions(L):
         else:  # stage-1 parameters stop early by design (delta 1e-2, past 2)
             assert it.value < 40
         assert ev.value >= it.value
+
+
+LBFGS_FIELDS = ("mem_size", "past", "max_linesearch", "g_epsilon", "delta", "min_step", "max_step", "f_dec_coeff", "s_curv_coeff",
+                "cautious_factor", "machine_prec", "max_iterations")
+
+
+def test_every_lbfgs_field_is_settable_by_name():
+    """orc_set_param: s1_<field> / s2_<field> reach the field they name and no other (tests/test_solver_paths.py relies on it)."""
+    o = orc.Oracle()
+    before = {(s, f): o.get_param(f"{s}_{f}") for s in ("s1", "s2") for f in LBFGS_FIELDS}
+    for i, (s, f) in enumerate(before):
+        v = 3 + i if f in ("mem_size", "past", "max_linesearch", "max_iterations") else 0.125 + i / 64.0
+        o.set_param(f"{s}_{f}", v)
+        after = {k: o.get_param(f"{k[0]}_{k[1]}") for k in before}
+        assert after[(s, f)] == v and all(after[k] == before[k] for k in before if k != (s, f)), (s, f)
+        before = after
+    with pytest.raises(KeyError):
+        o.set_param("s2_no_such_field", 1.0)
+
+
+def _lbfgs_trace(L, o, kind, n, x0, device_epl=0, cap=400):
+    L.orc_lbfgs_trace.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_dp, C.c_int, c_dp, c_dp, c_dp, c_dp,
+                                  C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    xs, gs, fs, steps = np.zeros((cap, n)), np.zeros((cap, n)), np.zeros(cap), np.zeros(cap)
+    it, ev, sb, rows = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+    ret = L.orc_lbfgs_trace(o.h, kind, n, 2, device_epl, _dp(np.ascontiguousarray(x0, dtype=np.float64)), cap, _dp(xs), _dp(gs), _dp(fs),
+                            _dp(steps), C.byref(it), C.byref(ev), C.byref(sb), C.byref(rows))
+    r = rows.value
+    return dict(ret=ret, iters=it.value, evals=ev.value, sum_bound=sb.value, x=xs[:r], g=gs[:r], f=fs[:r], step=steps[:r])
+
+
+def _two_loop(pairs, g):
+    """Plain L-BFGS two-loop recursion (Nocedal & Wright, algorithm 7.4) in longdouble over `pairs` = [(s, y), ...] NEWEST FIRST,
+    initial scaling y.s / y.y of the newest pair; returns the search direction -H g.  No ring, no indices."""
+    ld = np.longdouble
+    q = -g.astype(ld)
+    al = []
+    for s, y in pairs:
+        a = (s @ q) / (y @ s)
+        al.append(a)
+        q = q - a * y
+    s0, y0 = pairs[0]
+    q = q * ((y0 @ s0) / (y0 @ y0))
+    for (s, y), a in zip(reversed(pairs), reversed(al)):
+        b = (y @ q) / (y @ s)
+        q = q + (a - b) * s
+    return q
+
+
+@pytest.mark.parametrize("device_epl", [0, 2])
+@pytest.mark.parametrize("mem", [1, 2, 3])
+def test_lbfgs_direction_after_the_ring_has_wrapped(L, mem, device_epl):
+    """The oracle's L-BFGS (reference order and device order) with a history of 1, 2 and 3 pairs on the 10-d Rosenbrock function and on
+    the 20-d diagonal quadratic, which need far more iterations than that: at EVERY iteration, those after the ring has wrapped
+    included, the next iterate is x_k + step_{k+1} d_k with d_k the direction of a plain two-loop recursion over the last min(k, mem)
+    pairs (s_j, y_j) = (x_{j+1} - x_j, g_{j+1} - g_j) of the recorded iterates (the C API hands out iterates, not directions).
+    Tolerance: this file's for linear solves (1e-11, test_banded_solve_and_adjoint).  The runs are capped at 3 mem + 10 iterations,
+    where every step is still longer than 1e-4: a direction that used a wrong, a missing or a stale pair moves the iterate by a
+    sizeable fraction of that, seven orders of magnitude above the tolerance."""
+    ld = np.longdouble
+    for kind, n in ((0, 10), (1, 20)):
+        o = orc.Oracle()
+        for k, v in dict(s2_mem_size=mem, s2_past=0, s2_g_epsilon=1e-9, s2_max_iterations=3 * mem + 10).items():
+            o.set_param(k, v)
+        x0 = np.zeros(n)
+        if kind == 0:
+            x0[:] = -1.2
+            x0[1::2] = 1.0
+        tr = _lbfgs_trace(L, o, kind, n, x0, device_epl=device_epl)
+        K = len(tr["x"]) - 1                       # rows 0..K: K accepted iterations on record
+        assert tr["ret"] in (0, -1008) and K >= 3 * mem + 4, (tr["ret"], K)
+        s = [(tr["x"][j + 1] - tr["x"][j]).astype(ld) for j in range(K)]
+        y = [(tr["g"][j + 1] - tr["g"][j]).astype(ld) for j in range(K)]
+        # no pair was refused by the cautious update (y.s > 1e-6 |s|^2 |g_j|), so the retained pairs are simply the last `mem`
+        assert all(y[j] @ s[j] > 1e-6 * (s[j] @ s[j]) * np.sqrt(tr["g"][j].astype(ld) @ tr["g"][j].astype(ld)) for j in range(K))
+        assert tr["sum_bound"] == sum(min(j, mem) for j in range(1, tr["iters"]))
+        checked = 0
+        for k in range(1, K):                      # direction used by iteration k + 1, built from pairs k-1, k-2, ...
+            pairs = [(s[j], y[j]) for j in range(k - 1, max(-1, k - 1 - mem), -1)]
+            d = _two_loop(pairs, tr["g"][k])
+            nxt = tr["x"][k].astype(ld) + ld(tr["step"][k + 1]) * d
+            assert np.abs(s[k]).max() > 1e-4
+            assert np.allclose(tr["x"][k + 1], np.asarray(nxt, dtype=np.float64), rtol=1e-11, atol=1e-11), (kind, mem, k)
+            checked += k > 2 * mem
+        assert checked >= mem + 3
