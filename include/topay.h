@@ -1093,6 +1093,18 @@ topay_status topay_unpack_records(const topay_record_t* gathered, int world, int
  * the solver on the first of them -- so *waves is 1 for every n_pieces.  Any output pointer may be NULL. */
 topay_status topay_class_of(int n_pieces, int* waves, int* elements_per_thread, int* class_index);
 
+/* topay_edt_test_plan (test hook): what the distance-field build (topay_build_esdf*) decides from the shape of n_maps maps of
+ * dims = (nx, ny, nz) alone, as the 19 numbers out[0 .. 19).  No context and no device, like topay_class_of.
+ *   out[0]       1: every dimension <= 512 cells, the exhaustive-search kernels; 0: the envelope kernel
+ *   out[1]       first pass of the 3-D field: 16 / 32 / 64 = the ballot kernel of that line length, 0 = the direct kernel
+ *   out[2..5)    lines per tile wy, wx, w2 of the y pass, the x pass and the 2-D x pass
+ *   out[5..8)    dynamic LDS bytes of those tiles
+ *   out[8..13)   per envelope pass (3-D z, y, x; 2-D y, x): 1 = stacks in LDS, 0 = in the HBM workspace
+ *   out[13..18)  per envelope pass: LDS bytes of a block's stacks
+ *   out[18]      workspace elements per map
+ * out[1..8) describe the launches when out[0] is 1, out[8..19) when it is 0. */
+topay_status topay_edt_test_plan(const int dims[3], int n_maps, long long* out);
+
 /* Device memory (bytes) of the batch resident in the context: every block topay_set_init_traj sized.  The variable-length
  * blocks (L-BFGS history first of all) are packed by each candidate's own size, not strided by the longest member. */
 topay_status topay_workspace_bytes(topay_ctx* ctx, unsigned long long* bytes);

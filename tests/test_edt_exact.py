@@ -6,12 +6,14 @@ each compared with the reference directly, never with each other.  Four of the f
 esdf2d, inflate, critical-inflate); the plain critical field is scratch on the device (its buffer is released at the end
 of the build) and enters through its threshold grid, the seeds of critical-inflate.
 
-Case -> path, from the dispatch in topay_host_maps.h (restated in `plan` below and asserted per case; the constants
-that the restatement rests on are pinned to the source text in test_dispatch_constants_are_the_sources):
+Case -> path.  The dispatch is stated once in the library (edt_plan of topay_edt.h, which the launchers of
+topay_host_maps.h read) and restated independently in `plan` below; every case asserts its selections against both --
+the library under test is asked through api.edt_plan -- and test_plan_is_the_restatement compares the two statements
+field by field on both sides of every decision:
 
  lines <= 512 cells in every dimension ("small"): z pass k_edt_first_ballot<nz> for nz in 16/32/64, else
- k_edt_direct<0,0>; y pass k_edt_tile<1,0> with wy = largest divisor of nz up to 64; x pass k_edt_tile_signed with
- wx = largest divisor of ny nz up to 32; each 2-D field k_edt_direct<0,0> twice and k_edt_tile_signed with w2 = largest
+ k_edt_direct; y pass k_edt_tile with wy = largest divisor of nz up to 64; x pass k_edt_tile_signed with
+ wx = largest divisor of ny nz up to 32; each 2-D field k_edt_direct twice and k_edt_tile_signed with w2 = largest
  divisor of ny up to 32.  k_edt_threshold twice per build, k_edt_project when no critical grid is handed over.
 
    ballot16      9 x 7 x 16     k_edt_first_ballot<16>, 1008 cells: the last wave is partly dead; wy 16, wx 28, w2 7
@@ -21,7 +23,7 @@ that the restatement rests on are pinned to the source text in test_dispatch_con
    wy1           6 x 5 x 67     nz prime above 64: wy 1; wx 5
    w2_1          8 x 37 x 3     ny prime above 32: w2 1 (k_edt_tile_signed with one line per tile); wy 3, wx 3
    tiny          4 x 3 x 5      tiles smaller than the block (cells < 256)
-   ytile128k     2 x 512 x 64   k_edt_tile<1,0> tile of 512 x 64 x 4 B = 128 KB, the LDS maximum
+   ytile128k     2 x 512 x 64   k_edt_tile tile of 512 x 64 x 4 B = 128 KB, the LDS maximum
    xtile128k     512 x 4 x 8    k_edt_tile_signed tiles of 2 x 512 x 32 x 4 B = 128 KB
    x1 / y1       1 x 7 x 5, 6 x 1 x 5   a dimension of one cell in x or y (accepted); z = 1 is refused (pinned below)
 
@@ -65,7 +67,7 @@ def _radius():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the dispatch of topay_host_maps.h, restated
+# the dispatch (edt_plan of topay_edt.h), restated
 # ---------------------------------------------------------------------------------------------------------------------
 def pick_w(lines, cap):
     return max(d for d in range(1, cap + 1) if lines % d == 0)
@@ -93,25 +95,48 @@ def plan(dims, n_maps=1):
                 x2=f"<1,1,{ws[env_stacks(nx, ny, n_maps)]}>", lds_y=env_lds_bytes(ny))
 
 
-def test_dispatch_constants_are_the_sources():
-    """`plan` restates the dispatch; the constants it uses are the ones in the source, so a change of the dispatch fails
-    here instead of silently moving a case to another path."""
-    src = open(os.path.join(ROOT, "topay_amd", "csrc", "topay_host_maps.h")).read()
-    for pat in (r"small_lines = std::max\(nx, std::max\(ny, nz\)\) <= 512;",
-                r"pick_w = \[\]\(long long lines\) \{ int w = 1; for \(int d = 1; d <= 64; d\+\+\) if \(lines % d == 0\) w = d;",
-                r"pick_w32 = \[\]\(long long lines\) \{ int w = 1; for \(int d = 1; d <= 32; d\+\+\) if \(lines % d == 0\) w = d;",
-                r"wy = pick_w\(nz\), wx = pick_w32\(\(long long\)ny \* nz\);", r"w2 = pick_w32\(ny\);",
-                r"lds_bytes = \[\]\(int n\) \{ return \(size_t\)\(n \+ 2\) \* 64 \* 10; \};",
-                r"if \(lb <= 56 \* 1024 \|\| \(lb <= 150 \* 1024 && \(long long\)n_maps \* P\.nlines <= 65536\)\)",
-                r"if \(nz == 16\) hipLaunchKernelGGL\(k_edt_first_ballot<16>", r"else if \(nz == 32\) hipLaunchKernelGGL\(k_edt_first_ballot<32>",
-                r"else if \(nz == 64\) hipLaunchKernelGGL\(k_edt_first_ballot<64>"):
-        assert re.search(pat, src), pat
+def _lib(backend):
+    """The library under test: the emulator build in the CPU cases, the product library in the gpu cases."""
+    return api.load(EMU_LIB if backend == "emu" else None)
+
+
+# Shapes on both sides of every decision of the dispatch (n_maps 1 unless a pair says otherwise).
+SWEEP = ([(512, 7, 5), (513, 7, 5), (7, 512, 5), (7, 513, 5), (7, 5, 512), (7, 5, 513)]            # small / envelope, per axis
+         + [(5, 7, nz) for nz in (15, 16, 17, 31, 32, 33, 63, 64, 65, 67)]                          # ballot widths, wy up to its cap
+         + [(5, ny, 3) for ny in (31, 32, 33, 37)]                                                  # w2 up to its cap, prime above it
+         + [(513, n, 3) for n in (87, 88, 100, 101, 238, 239)]                                      # y stacks: 56 KB, 64 KB, 150 KB
+         + [(3, 513, n) for n in (87, 88, 238, 239)] + [(n, 513, 3) for n in (87, 88, 238, 239)]    # ... the same for z and for x, x2
+         + [(513, 1, 2), (1, 513, 3), (1, 7, 5), (6, 1, 5)])                                        # one cell in x and in y
+# 65536 lines in all and one map more: 513 x 100 x 3 has 1539 y lines of 65280 B of stacks (42 maps: 64638, 43: 66177);
+# 1024 x 97 x 2 has 2048 y lines of 97 cells, 63360 B (32 maps: 65536 exactly, 33: 67584) and 1024 lines in its 2-D y pass
+# (64 maps: 65536 exactly); 513 x 1 x 97 has 513 z lines of 97 cells (127 maps: 65151, 128: 65664)
+SWEEP_MAPS = [((513, 100, 3), 42), ((513, 100, 3), 43), ((1024, 97, 2), 32), ((1024, 97, 2), 33), ((1024, 97, 2), 64), ((1024, 97, 2), 65),
+              ((513, 1, 97), 127), ((513, 1, 97), 128), ((513, 1, 97), 129)]
+
+
+def test_plan_is_the_restatement():
+    """The library's own statement of the dispatch (edt_plan of topay_edt.h, which the construction reads) equals the restatement
+    `plan`, field by field, on both sides of every decision: a change of the dispatch fails here instead of silently moving a
+    case to another path."""
+    lib = _lib("emu")
+    shapes = [(d, 1) for d in SWEEP] + [(d, 1) for d, _, _ in list(SMALL.values()) + list(LARGE.values())] + SWEEP_MAPS
+    for dims, n_maps in shapes:
+        assert api.edt_plan(dims, n_maps, lib=lib) == plan(dims, n_maps), (dims, n_maps)
+    # the sweep does sit on both sides of each threshold
+    assert env_lds_bytes(87) <= 56 * 1024 < env_lds_bytes(88) and env_lds_bytes(238) == 150 * 1024 < env_lds_bytes(239)
+    assert [plan((1024, 97, 2), m)["y"] for m in (32, 33)] == ["<1,0,1>", "<1,0,0>"] and 32 * 1024 * 2 == 65536
+    assert [plan((1024, 97, 2), m)["y2"] for m in (64, 65)] == ["<0,0,1>", "<0,0,0>"] and 64 * 1024 == 65536
+    assert [plan((513, 1, 97), m)["z"] for m in (127, 128)] == ["<0,0,1>", "<0,0,0>"]
+    assert {plan(d)["family"] for d in SWEEP[:6]} == {"small", "envelope"}
+    assert {plan(d)["first"] for d in SWEEP[6:16]} == {"ballot16", "ballot32", "ballot64", "direct"}
     # every kernel the construction launches is one that a case below is named after
+    src = open(os.path.join(ROOT, "topay_amd", "csrc", "topay_host_maps.h")).read()
     launched = set(re.findall(r"k_edt_[a-z_]+(?:<[0-9, ]+>)?", src))
-    assert launched == {"k_edt_first_ballot<16>", "k_edt_first_ballot<32>", "k_edt_first_ballot<64>", "k_edt_direct<0, 0>", "k_edt_tile<1, 0>",
-                        "k_edt_tile<1, 1>", "k_edt_tile_signed", "k_edt_pass<0, 0, 0>", "k_edt_pass<0, 0, 1>", "k_edt_pass<1, 0, 0>",
-                        "k_edt_pass<1, 0, 1>", "k_edt_pass<1, 1, 0>", "k_edt_pass<1, 1, 1>", "k_edt_threshold", "k_edt_project",
-                        "k_edt_direct", "k_edt_tile"}, launched   # (<1, 1>: only its LDS attribute is set; the bare names: comments)
+    # Gone from this set because they were never launched: k_edt_tile<1, 1> (only its LDS attribute was set), and the template
+    # arguments of k_edt_direct<0, 0> / k_edt_tile<1, 0> (the only instances ever launched: the kernels are plain functions now).
+    assert launched == {"k_edt_first_ballot<16>", "k_edt_first_ballot<32>", "k_edt_first_ballot<64>", "k_edt_direct", "k_edt_tile",
+                        "k_edt_tile_signed", "k_edt_pass<0, 0, 0>", "k_edt_pass<0, 0, 1>", "k_edt_pass<1, 0, 0>",
+                        "k_edt_pass<1, 0, 1>", "k_edt_pass<1, 1, 0>", "k_edt_pass<1, 1, 1>", "k_edt_threshold", "k_edt_project"}, launched
 
 
 # name -> (dims, res, expected selections)
@@ -139,21 +164,22 @@ LARGE = {
 }
 
 
-def _assert_plan(dims, expect, n_maps=1):
-    got = plan(dims, n_maps)
-    for k, v in expect.items():
-        assert got[k] == v, (dims, k, got[k], v)
+def _assert_plan(backend, dims, expect, n_maps=1):
+    """The expected selections of a case, against the restatement and against what the library under test decides."""
+    for who, got in (("restatement", plan(dims, n_maps)), ("library", api.edt_plan(dims, n_maps, lib=_lib(backend)))):
+        for k, v in expect.items():
+            assert got[k] == v, (who, dims, k, got[k], v)
 
 
 def test_plan_of_every_case():
     for dims, _, expect in list(SMALL.values()) + list(LARGE.values()):
-        _assert_plan(dims, expect)
+        _assert_plan("emu", dims, expect)
     assert env_lds_bytes(101) > 64 * 1024 >= env_lds_bytes(100) > 56 * 1024       # 101: above the default; both conditional
     assert env_stacks(238, 513 * 2, 1) == "lds" and env_stacks(239, 513 * 2, 1) == "hbm"
-    _assert_plan((513, 100, 3), dict(y="<1,0,1>"), n_maps=42)                     # 42 x 1539 = 64638 lines
-    _assert_plan((513, 100, 3), dict(z="<0,0,1>", y="<1,0,0>", x="<1,1,0>", y2="<0,0,1>", x2="<1,1,0>"), n_maps=43)   # 66177
-    _assert_plan((23, 19, 13), dict(first="direct", wy=13, wx=19, w2=19))
-    _assert_plan((23, 23, 12), dict(first="direct", wy=12, wx=23, w2=23))
+    _assert_plan("emu", (513, 100, 3), dict(y="<1,0,1>"), n_maps=42)              # 42 x 1539 = 64638 lines
+    _assert_plan("emu", (513, 100, 3), dict(z="<0,0,1>", y="<1,0,0>", x="<1,1,0>", y2="<0,0,1>", x2="<1,1,0>"), n_maps=43)   # 66177
+    _assert_plan("emu", (23, 19, 13), dict(first="direct", wy=13, wx=19, w2=19))
+    _assert_plan("emu", (23, 23, 12), dict(first="direct", wy=12, wx=23, w2=23))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -273,7 +299,7 @@ def _case(name):
 
 def _run_case(backend, name):
     dims, res, pats = _case(name)
-    _assert_plan(dims, (SMALL.get(name) or LARGE[name])[2])
+    _assert_plan(backend, dims, (SMALL.get(name) or LARGE[name])[2])
     opt = _opt(backend)
     explicit = 0
     for p, o3, o2, oc, want in pats:
@@ -382,7 +408,7 @@ def test_batch_of_three_maps_into_later_slots(backend):
 @pytest.mark.parametrize("backend", BACKENDS)
 def test_envelope_batch_of_two(backend):
     """2 maps of 513 x 5 x 3 into slots 8, 9: blockIdx.y = map in k_edt_pass, LDS stacks (z, y) and HBM stacks per map (x)."""
-    _assert_plan((513, 5, 3), SMALL["env_x"][2], n_maps=2)
+    _assert_plan(backend, (513, 5, 3), SMALL["env_x"][2], n_maps=2)
     _run_batch(backend, (513, 5, 3), 0.1, 2, "voxels", 98, first=8)
 
 
@@ -394,7 +420,7 @@ def test_envelope_batch_of_43_takes_hbm_stacks(backend):
 
     Device only: the emulator needs 12 s for the 6.6 million cells.  It runs k_edt_pass<1,0,0> in env_y and the map dimension of
     a k_edt_pass launch in test_envelope_batch_of_two."""
-    _assert_plan((513, 100, 3), dict(z="<0,0,1>", y="<1,0,0>", x="<1,1,0>", y2="<0,0,1>", x2="<1,1,0>"), n_maps=43)
+    _assert_plan(backend, (513, 100, 3), dict(z="<0,0,1>", y="<1,0,0>", x="<1,1,0>", y2="<0,0,1>", x2="<1,1,0>"), n_maps=43)
     _run_batch(backend, (513, 100, 3), 0.5, 43, "voxels", 99, first=2)
 
 

@@ -245,6 +245,8 @@ def load(path=None):
     L.topay_build_esdf_fields.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(MapDesc), C.POINTER(C.c_int8), C.POINTER(C.c_int8),
                                           C.POINTER(C.c_int8)]
     L.topay_get_map_fields.argtypes = [C.c_void_p, C.c_int, c_dp, c_dp]
+    if hasattr(L, "topay_edt_test_plan"):   # (older builds of the library under tools/libs, A/B runs)
+        L.topay_edt_test_plan.argtypes = [c_ip, C.c_int, C.POINTER(C.c_longlong)]
     if hasattr(L, "topay_generate_worlds"):   # (older builds of the library under tools/libs, A/B runs)
         L.topay_world_default_params.argtypes = [C.c_int, C.POINTER(WorldParams)]
         L.topay_generate_worlds.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(WorldParams), c_u64p, c_dp, c_ip]
@@ -361,6 +363,23 @@ def sample_start_goal_xy(seeds, size_xy=20.0, lib=None):
     s3, g3 = np.zeros((len(sd), 3)), np.zeros((len(sd), 3))
     _chk(L, L.topay_sample_start_goal_xy(len(sd), sd.ctypes.data_as(c_u64p), float(size_xy), _dp(s3), _dp(g3)))
     return s3, g3
+
+
+def edt_plan(dims, n_maps=1, lib=None):
+    """What the distance-field build decides from the shape of n_maps maps of dims = (nx, ny, nz) alone (edt_plan of topay_edt.h through
+    the test hook topay_edt_test_plan; host arithmetic, no device).  family "small": the first pass ("ballot16" / "ballot32" /
+    "ballot64" / "direct"), the tile widths wy, wx, w2 and the LDS bytes lds_y, lds_x, lds_2 of their tiles.  family "envelope": the
+    k_edt_pass instance <SRC,FIN,WS> of the passes z, y, x (3-D) and y2, x2 (2-D) -- WS 1: stacks in LDS -- and lds_y, the stack bytes
+    of the 3-D y pass."""
+    L = lib or load()
+    out = (C.c_longlong * 19)()
+    _chk(L, L.topay_edt_test_plan((C.c_int * 3)(*[int(d) for d in dims]), int(n_maps), out))
+    if out[0]:
+        return dict(family="small", first=f"ballot{out[1]}" if out[1] else "direct", wy=out[2], wx=out[3], w2=out[4],
+                    lds_y=out[5], lds_x=out[6], lds_2=out[7])
+    ws = out[8:13]
+    return dict(family="envelope", z=f"<0,0,{ws[0]}>", y=f"<1,0,{ws[1]}>", x=f"<1,1,{ws[2]}>", y2=f"<0,0,{ws[3]}>", x2=f"<1,1,{ws[4]}>",
+                lds_y=out[14])
 
 
 def test_mt64(seed, skip, n, lib=None):

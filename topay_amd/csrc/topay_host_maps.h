@@ -123,200 +123,237 @@ topay_status topay_share_maps(topay_ctx* c, topay_ctx* owner, int first_map_id, 
   return TOPAY_OK;
 }
 
-// ESDF construction on the device (GridMap::updateESDF, grid_map.cpp:125-521) from occupancy grids that already lie in device
-// memory: d_occ3 [n_maps][nx*ny*nz], d_occ2 [n_maps][nx*ny] (points below the chassis height), d_occ2c [n_maps][nx*ny] (the
-// critical grid; written here as the projection of d_occ3 when project_critical).  The body of topay_build_esdf_fields, which
-// uploads the grids first, and of topay_generate_worlds (topay_host_world.h), whose rasteriser wrote them.  The grids are read
-// only (d_occ2c apart) and stay the caller's.
+// ESDF construction on the device (GridMap::updateESDF, grid_map.cpp:125-521): one batch of n_maps maps of equal dimensions.  What
+// the shape decides -- kernel family, first pass, tile widths, LDS sizes, where the envelope stacks live -- is edt_plan's
+// (topay_edt.h); the launchers here read it.  Three jobs: setup (arena and workspace), construct (the launches), publish (the slots).
+struct EdtBuild {
+  topay_ctx* c;
+  const int n_maps, nx, ny, nz;
+  const size_t n2, n3, M;
+  const double res;
+  const EdtPlan plan;
+  double *e3, *e2, *e2i, *e2c;   // results; e2i: inflate; e2c: critical (holds the critical-inflate field at the end, as the reference's buffer does)
+  double *t1, *t2, *e2s;         // workspace: two intermediate volumes; the plain critical field
+  signed char* occ_thr;          // 2-D scratch: the thresholded fields
+  int* vws;                      // envelope stacks in HBM
+  double* zws;
+
+  EdtBuild(topay_ctx* ctx, int maps, const topay_map_desc_t* desc)
+      : c(ctx), n_maps(maps), nx(desc->dims[0]), ny(desc->dims[1]), nz(desc->dims[2]), n2((size_t)nx * ny), n3(n2 * nz), M((size_t)maps),
+        res(desc->resolution), plan(edt_plan(nx, ny, nz, maps)) {}
+
+  topay_status setup(int first_map_id) {
+    topay_status s;
+    EdtState& w = c->edt;
+    if ((s = w.thr.ensure(M * n2)) != TOPAY_OK) return s;
+    if ((s = w.tmp1.ensure(M * n3 * 8)) != TOPAY_OK) return s;
+    if ((s = w.tmp2.ensure(M * n3 * 8)) != TOPAY_OK) return s;
+    // results: e3 | e2 | e2 inflate | e2 critical in a new arena (they stay there); the plain critical field is scratch
+    // (a rebuild of the same range of slots -- a new episode's maps -- takes the arena of the previous build over)
+    // arenas of earlier builds whose slots this build overwrites completely are released (a caller that varies the slot
+    // ranges would otherwise accumulate full-size arenas until topay_destroy)
+    for (size_t i = 0; i < c->map_arenas.size();) {
+      topay_ctx::MapArena& a = c->map_arenas[i];
+      const bool same = a.first == first_map_id && a.n == n_maps;
+      if (!same && a.first >= first_map_id && a.first + a.n <= first_map_id + n_maps) {
+        a.buf.release();
+        c->map_arenas.erase(c->map_arenas.begin() + (long)i);
+      } else {
+        i++;
+      }
+    }
+    topay_ctx::MapArena* ar = nullptr;
+    for (auto& a : c->map_arenas)
+      if (a.first == first_map_id && a.n == n_maps) ar = &a;
+    if (!ar) {
+      c->map_arenas.emplace_back();
+      ar = &c->map_arenas.back();
+      ar->first = first_map_id;
+      ar->n = n_maps;
+    }
+    auto lay_arena = [&](Carver& k) {
+      e3 = k.take<double>(M * n3); e2 = k.take<double>(M * n2); e2i = k.take<double>(M * n2); e2c = k.take<double>(M * n2);
+    };
+    if ((s = ar->buf.carve(lay_arena)) != TOPAY_OK) return s;
+    if ((s = w.out2.ensure(M * n2 * 8)) != TOPAY_OK) return s;
+    if ((s = w.v.ensure(M * plan.ws_elems * 4)) != TOPAY_OK) return s;
+    if ((s = w.z.ensure(M * plan.ws_elems * 8)) != TOPAY_OK) return s;
+    occ_thr = w.thr.as<signed char>();
+    t1 = w.tmp1.as<double>();
+    t2 = w.tmp2.as<double>();
+    e2s = w.out2.as<double>();
+    vws = w.v.as<int>();
+    zws = w.z.as<double>();
+    return TOPAY_OK;
+  }
+
+  // One launcher per kernel family.  Only the envelope launcher can fail (its per-launch LDS attribute).
+  dim3 cells(long long n_elems) const { return dim3((unsigned)((n_elems + 255) / 256), (unsigned)n_maps); }
+  // first pass, along the contiguous axis: lines of n cells, n_elems cells per map; ballot 16 / 32 / 64 = n, or 0
+  void first_pass(long long n_elems, int n, int ballot, const signed char* occ, int* dst_i, int pass) const {
+    const long long map_stride = n_elems;   // the maps of a batch lie back to back
+    if (ballot == 16) hipLaunchKernelGGL(k_edt_first_ballot<16>, cells(n_elems), dim3(256), 0, c->stream, n_elems, map_stride, occ, dst_i, pass);
+    else if (ballot == 32) hipLaunchKernelGGL(k_edt_first_ballot<32>, cells(n_elems), dim3(256), 0, c->stream, n_elems, map_stride, occ, dst_i, pass);
+    else if (ballot == 64) hipLaunchKernelGGL(k_edt_first_ballot<64>, cells(n_elems), dim3(256), 0, c->stream, n_elems, map_stride, occ, dst_i, pass);
+    else hipLaunchKernelGGL(k_edt_direct, cells(n_elems), dim3(256), 0, c->stream, n_elems, n, map_stride, occ, dst_i, pass);
+  }
+  // strided pass over tiles of W lines x n cells (geometry: topay_edt.h), int32 to int32
+  void tile(long long map_stride, int n, int W, size_t lds, long long step, long long inner_tiles, long long outer_stride, long long tiles,
+            const int* src, int* dst_i) const {
+    hipLaunchKernelGGL(k_edt_tile, dim3((unsigned)tiles, (unsigned)n_maps), dim3(256), lds, c->stream, n, W, step, inner_tiles, outer_stride,
+                       map_stride, src, dst_i);
+  }
+  // final pass of a signed field, both signs at once (two tiles of W <= 32 lines in LDS)
+  void tile_signed(long long map_stride, int n, int W, size_t lds, long long step, long long inner_tiles, long long outer_stride, long long tiles,
+                   const int* src_pos, const int* src_neg, double* dst_d) const {
+    hipLaunchKernelGGL(k_edt_tile_signed, dim3((unsigned)tiles, (unsigned)n_maps), dim3(256), lds, c->stream, n, W, step, inner_tiles,
+                       outer_stride, map_stride, src_pos, src_neg, dst_d, res);
+  }
+  // envelope pass k of the plan: kern_l with the stacks in LDS, kern_g with the stacks in the HBM workspace
+  using EnvelopeKernel = void (*)(EdtPass, const signed char*, const double*, double*, int*, double*, int, double);
+  topay_status envelope(EnvelopeKernel kern_g, EnvelopeKernel kern_l, int k, const signed char* occ, const double* src, double* dst, int pass) const {
+    const EdtPass& P = plan.pass[k];
+    const dim3 grid((unsigned)((P.nlines + 63) / 64), (unsigned)n_maps);
+    if (plan.stack_lds[k]) {
+      HIPCHK(hipFuncSetAttribute((const void*)kern_l, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.stack_bytes[k]));
+      hipLaunchKernelGGL(kern_l, grid, dim3(64), plan.stack_bytes[k], c->stream, P, occ, src, dst, vws, zws, pass, res);
+    } else {
+      hipLaunchKernelGGL(kern_g, grid, dim3(64), 0, c->stream, P, occ, src, dst, vws, zws, pass, res);
+    }
+    return TOPAY_OK;
+  }
+  void threshold(const double* field, signed char* occ) const {
+    const long long n = (long long)(M * n2);
+    hipLaunchKernelGGL(k_edt_threshold, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, field, c->dp.chassis_colli_radius, occ, n);
+  }
+  void project(const signed char* occ3, signed char* occ2) const {
+    const long long n = (long long)(M * n2);
+    hipLaunchKernelGGL(k_edt_project, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, occ3, occ2, (long long)n2, nz, (long long)M);
+  }
+
+  // The 3-D field: along z and y per sign, then along x (small family: both signs in one launch) -- grid_map.cpp:425-521
+  topay_status field3d(const signed char* occ, double* out) const {
+    const long long yz = (long long)ny * nz;
+    if (plan.small) {
+      // (tiles of up to 512 x 64 cells x 4 B = 128 KB of LDS: above the 64 KB default; set once, not per launch)
+      static std::once_flag edt_attr_once[16];
+      std::call_once(edt_attr_once[c->device % 16], [] {
+        (void)hipFuncSetAttribute((const void*)k_edt_tile, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEdtTileLdsMax);
+        (void)hipFuncSetAttribute((const void*)k_edt_tile_signed, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEdtSignedLdsMax);
+      });
+      const int wy = plan.wy, wx = plan.wx;
+      int *i1 = (int*)t1, *i2 = (int*)t2;
+      int* i2n = i2 + M * n3;   // second half of the workspace volume: the negative part's squared distances after the y pass
+      for (int pass = 0; pass < 2; pass++) {
+        first_pass((long long)n3, nz, plan.first, occ, i1, pass);
+        tile((long long)n3, ny, wy, plan.lds_y, nz, nz / wy, yz, (long long)nx * (nz / wy), i1, pass == 0 ? i2 : i2n);
+      }
+      tile_signed((long long)n3, nx, wx, plan.lds_x, yz, yz / wx, 0, yz / wx, i2, i2n, out);
+      return TOPAY_OK;
+    }
+    for (int pass = 0; pass < 2; pass++) {
+      topay_status s;
+      if ((s = envelope(k_edt_pass<0, 0, 0>, k_edt_pass<0, 0, 1>, kEdtZ, occ, nullptr, t1, pass)) != TOPAY_OK) return s;
+      if ((s = envelope(k_edt_pass<1, 0, 0>, k_edt_pass<1, 0, 1>, kEdtY, nullptr, t1, t2, pass)) != TOPAY_OK) return s;
+      if ((s = envelope(k_edt_pass<1, 1, 0>, k_edt_pass<1, 1, 1>, kEdtX, nullptr, t2, out, pass)) != TOPAY_OK) return s;
+    }
+    return TOPAY_OK;
+  }
+  // One signed 2-D field from an occupancy grid: along y (lines x), along x (lines y), positive then negative part --
+  // grid_map.cpp:125-207 and, with other seeds, 211-279, 283-351, 355-423
+  topay_status field2d(const signed char* occ, double* out) const {
+    if (plan.small) {
+      const int w2 = plan.w2;
+      int* i1 = (int*)t1;
+      int* i1n = i1 + M * n2;
+      first_pass((long long)n2, ny, 0, occ, i1, 0);
+      first_pass((long long)n2, ny, 0, occ, i1n, 1);
+      tile_signed((long long)n2, nx, w2, plan.lds_2, ny, ny / w2, 0, ny / w2, i1, i1n, out);
+      return TOPAY_OK;
+    }
+    for (int pass = 0; pass < 2; pass++) {
+      topay_status s;
+      if ((s = envelope(k_edt_pass<0, 0, 0>, k_edt_pass<0, 0, 1>, kEdtY2, occ, nullptr, t1, pass)) != TOPAY_OK) return s;
+      if ((s = envelope(k_edt_pass<1, 1, 0>, k_edt_pass<1, 1, 1>, kEdtX2, nullptr, t1, out, pass)) != TOPAY_OK) return s;
+    }
+    return TOPAY_OK;
+  }
+
+  // The five fields in the order of updateESDF.  occ2c is written here, as the projection of occ3, when project_critical.
+  topay_status construct(const signed char* occ3, const signed char* occ2, signed char* occ2c, bool project_critical) const {
+    topay_status s;
+    if ((s = field3d(occ3, e3)) != TOPAY_OK) return s;               // esdf_buffer_3d (425-521)
+    if ((s = field2d(occ2, e2)) != TOPAY_OK) return s;               // esdf_buffer_2d
+    threshold(e2, occ_thr);
+    if ((s = field2d(occ_thr, e2i)) != TOPAY_OK) return s;           // esdf_buffer_2d_inflate (355-423)
+    if (project_critical) project(occ3, occ2c);
+    if ((s = field2d(occ2c, e2s)) != TOPAY_OK) return s;             // 2-D critical (211-279)
+    threshold(e2s, occ_thr);
+    return field2d(occ_thr, e2c);                                    // critical inflate, stored in esdf_buffer_2d_critical (283-351)
+  }
+
+  // the map slots point into the arena; descriptors as topay_set_map
+  topay_status publish(int first_map_id, const topay_map_desc_t* desc) const {
+    for (int k = 0; k < n_maps; k++) {
+      const int map_id = first_map_id + k;
+      c->map2d[map_id].release(); c->map3d[map_id].release(); c->map2d_inf[map_id].release(); c->map2d_crit[map_id].release();
+      DevMap& m = c->hmaps[map_id];
+      for (int i = 0; i < 3; i++) {
+        m.origin[i] = desc->origin[i]; m.dims[i] = desc->dims[i];
+        m.min_b[i] = desc->min_boundary[i]; m.max_b[i] = desc->max_boundary[i];
+      }
+      m.res = desc->resolution;
+      m.res_inv = 1.0 / desc->resolution;
+      m.esdf2d = (glb_cdp)(e2 + (size_t)k * n2);
+      m.esdf3d = (glb_cdp)(e3 + (size_t)k * n3);
+      m.esdf2d_inflate = (glb_cdp)(e2i + (size_t)k * n2);
+      m.esdf2d_critical = (glb_cdp)(e2c + (size_t)k * n2);
+      c->have_map[map_id] = 1;
+    }
+    HIPCHK(hipMemcpyAsync((char*)c->dmaps.p + sizeof(DevMap) * first_map_id, &c->hmaps[first_map_id], sizeof(DevMap) * n_maps,
+                          hipMemcpyHostToDevice, c->stream));
+    return TOPAY_OK;
+  }
+};
+
+// The construction from occupancy grids that already lie in device memory: d_occ3 [n_maps][nx*ny*nz], d_occ2 [n_maps][nx*ny] (points
+// below the chassis height), d_occ2c [n_maps][nx*ny] (the critical grid; written here as the projection of d_occ3 when
+// project_critical).  The body of topay_build_esdf_fields, which uploads the grids first, and of topay_generate_worlds
+// (topay_host_world.h), whose rasteriser wrote them.  The grids are read only (d_occ2c apart) and stay the caller's.
 static topay_status build_fields_from_device(topay_ctx* c, int n_maps, int first_map_id, const topay_map_desc_t* desc, signed char* d_occ3,
                                              signed char* d_occ2, signed char* d_occ2c, bool project_critical) {
-  const int nx = desc->dims[0], ny = desc->dims[1], nz = desc->dims[2];
-  const size_t n2 = (size_t)nx * ny, n3 = n2 * nz, M = (size_t)n_maps;
   if (topay_status ds = map_dims_check(desc)) return ds;
   invalidate_sharers(c, first_map_id, n_maps);
   drop_shared_slots(c, first_map_id, n_maps);
+  EdtBuild b(c, n_maps, desc);
   topay_status s;
-  if ((s = c->edt.thr.ensure(M * n2)) != TOPAY_OK) return s;
-  signed char* d_occ2t = c->edt.thr.as<signed char>();   // 2-D scratch: the thresholded fields
-  if ((s = c->edt.tmp1.ensure(M * n3 * 8)) != TOPAY_OK) return s;
-  if ((s = c->edt.tmp2.ensure(M * n3 * 8)) != TOPAY_OK) return s;
-  // results: e3 | e2 | e2 inflate | e2 critical in a new arena (they stay there); the plain critical field is scratch
-  // (a rebuild of the same range of slots -- a new episode's maps -- takes the arena of the previous build over)
-  // arenas of earlier builds whose slots this build overwrites completely are released (a caller that varies the slot
-  // ranges would otherwise accumulate full-size arenas until topay_destroy)
-  for (size_t i = 0; i < c->map_arenas.size();) {
-    topay_ctx::MapArena& a = c->map_arenas[i];
-    const bool same = a.first == first_map_id && a.n == n_maps;
-    if (!same && a.first >= first_map_id && a.first + a.n <= first_map_id + n_maps) {
-      a.buf.release();
-      c->map_arenas.erase(c->map_arenas.begin() + (long)i);
-    } else {
-      i++;
-    }
-  }
-  topay_ctx::MapArena* ar = nullptr;
-  for (auto& a : c->map_arenas)
-    if (a.first == first_map_id && a.n == n_maps) ar = &a;
-  if (!ar) {
-    c->map_arenas.emplace_back();
-    ar = &c->map_arenas.back();
-    ar->first = first_map_id;
-    ar->n = n_maps;
-  }
-  DevBuf& arena = ar->buf;
-  double *e3, *e2, *e2i, *e2c;   // e2i: inflate; e2c: critical (holds the critical-inflate field at the end, as the reference's buffer does)
-  auto lay_arena = [&](Carver& k) {
-    e3 = k.take<double>(M * n3); e2 = k.take<double>(M * n2); e2i = k.take<double>(M * n2); e2c = k.take<double>(M * n2);
-  };
-  if ((s = arena.carve(lay_arena)) != TOPAY_OK) return s;
-  if ((s = c->edt.out2.ensure(M * n2 * 8)) != TOPAY_OK) return s;
-  // workspace for the envelope stacks of the pass with the most (lines x cells), per map
-  const size_t ws_elems = std::max(std::max((size_t)nx * ny * (nz + 2), (size_t)nx * nz * (ny + 2)), (size_t)ny * nz * (nx + 2));
-  if ((s = c->edt.v.ensure(M * ws_elems * 4)) != TOPAY_OK) return s;
-  if ((s = c->edt.z.ensure(M * ws_elems * 8)) != TOPAY_OK) return s;
+  if ((s = b.setup(first_map_id)) != TOPAY_OK) return s;
   HIPCHK(c->edt.timer.start(c->stream));
-  double* t1 = c->edt.tmp1.as<double>();
-  double* t2 = c->edt.tmp2.as<double>();
-  double* e2s = c->edt.out2.as<double>();   // scratch: the plain critical field
-  int* vws = c->edt.v.as<int>();
-  double* zws = c->edt.z.as<double>();
-  const double res = desc->resolution;
-  // envelope stacks in LDS when a 64-line block fits ((n + 2) x 64 x (8 + 2) B <= 150 KB, i.e. lines up to ~238 cells)
-  // and the launch is small, else in the HBM workspace
-  auto lds_bytes = [](int n) { return (size_t)(n + 2) * 64 * 10; };
-  auto launch = [&](auto kern_g, auto kern_l, EdtPass P, long long map_stride, const signed char* occ, const double* src,
-                    double* dst, int pass) -> topay_status {
-    const int bs = 64;
-    P.map_stride = map_stride;
-    P.ws_stride = (long long)ws_elems;
-    const dim3 grid((unsigned)((P.nlines + bs - 1) / bs), (unsigned)n_maps);
-    const size_t lb = lds_bytes(P.n);
-    // LDS stacks cut the latency of every envelope step but leave one wave per CU resident (129 KB per 64-line block
-    // at n = 200): they win while the launch cannot fill the device anyway (a single benchmark-size map: 2.7 vs 3.8 ms)
-    // and lose when there are lines enough to hide the HBM latency instead (1024 maps: 191 vs 142 ms).
-    if (lb <= 56 * 1024 || (lb <= 150 * 1024 && (long long)n_maps * P.nlines <= 65536)) {  // short lines: several blocks per CU still fit
-      HIPCHK(hipFuncSetAttribute((const void*)kern_l, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
-      hipLaunchKernelGGL(kern_l, grid, dim3(bs), lb, c->stream, P, occ, src, dst, vws, zws, pass, res);
-    } else {
-      hipLaunchKernelGGL(kern_g, grid, dim3(bs), 0, c->stream, P, occ, src, dst, vws, zws, pass, res);
-    }
-    return TOPAY_OK;
-  };
-  // Lines of up to 512 cells (every benchmark map: 200 x 200 x 16) take the exhaustive-search passes (topay_edt.h:
-  // k_edt_direct / k_edt_tile, 32-bit squared distances between the passes); longer lines the serial envelope passes.
-  const bool small_lines = std::max(nx, std::max(ny, nz)) <= 512;
-  auto pick_w = [](long long lines) { int w = 1; for (int d = 1; d <= 64; d++) if (lines % d == 0) w = d; return w; };
-  int* i1 = (int*)t1;
-  int* i2 = (int*)t2;
-  auto direct = [&](auto kern, long long n_elems, int n, const signed char* occ, const int* src, int* dst_i, double* dst_d, int pass) {
-    hipLaunchKernelGGL(kern, dim3((unsigned)((n_elems + 255) / 256), (unsigned)n_maps), dim3(256), 0, c->stream, n_elems, n, n_elems, occ, src,
-                       dst_i, dst_d, pass, res);
-  };
-  auto tile = [&](auto kern, long long n_elems, int n, int W, long long step, long long inner_tiles, long long outer_stride, long long tiles,
-                  const int* src, int* dst_i, double* dst_d, int pass) -> topay_status {
-    const size_t lb = (size_t)n * W * sizeof(int);
-    hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)n_maps), dim3(256), lb, c->stream, n, W, step, inner_tiles, outer_stride, n_elems,
-                       (const signed char*)nullptr, src, dst_i, dst_d, pass, res);
-    return TOPAY_OK;
-  };
-  // final pass of a signed field, both signs at once (k_edt_tile_signed: two tiles of W <= 32 lines in LDS)
-  auto pick_w32 = [](long long lines) { int w = 1; for (int d = 1; d <= 32; d++) if (lines % d == 0) w = d; return w; };
-  auto signed_x = [&](long long n_elems, int n, int W, long long step, long long inner_tiles, long long outer_stride, long long tiles,
-                      const int* sp, const int* sn, double* dst_d) {
-    const size_t lb = (size_t)n * W * sizeof(int) * 2;
-    hipLaunchKernelGGL(k_edt_tile_signed, dim3((unsigned)tiles, (unsigned)n_maps), dim3(256), lb, c->stream, n, W, step, inner_tiles, outer_stride,
-                       n_elems, sp, sn, dst_d, res);
-  };
-  if (small_lines) {
-    // (tiles of up to 512 x 64 cells x 4 B = 128 KB of LDS: above the 64 KB default; set once, not per launch)
-    static std::once_flag edt_attr_once[16];
-    std::call_once(edt_attr_once[c->device % 16], [] {
-      (void)hipFuncSetAttribute((const void*)k_edt_tile<1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 512 * 64 * 4);
-      (void)hipFuncSetAttribute((const void*)k_edt_tile<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 512 * 64 * 4);
-      (void)hipFuncSetAttribute((const void*)k_edt_tile_signed, hipFuncAttributeMaxDynamicSharedMemorySize, 512 * 32 * 4 * 2);
-    });
-    const int wy = pick_w(nz), wx = pick_w32((long long)ny * nz);
-    int* i2n = i2 + M * n3;   // second half of the workspace volume: the negative part's squared distances after the y pass
-    for (int pass = 0; pass < 2; pass++) {   // 3-D: along z and y per sign, then along x for both — grid_map.cpp:425-521
-      const dim3 g1((unsigned)((n3 + 255) / 256), (unsigned)n_maps);
-      if (nz == 16) hipLaunchKernelGGL(k_edt_first_ballot<16>, g1, dim3(256), 0, c->stream, (long long)n3, (long long)n3, (const signed char*)d_occ3, i1, pass);
-      else if (nz == 32) hipLaunchKernelGGL(k_edt_first_ballot<32>, g1, dim3(256), 0, c->stream, (long long)n3, (long long)n3, (const signed char*)d_occ3, i1, pass);
-      else if (nz == 64) hipLaunchKernelGGL(k_edt_first_ballot<64>, g1, dim3(256), 0, c->stream, (long long)n3, (long long)n3, (const signed char*)d_occ3, i1, pass);
-      else direct(k_edt_direct<0, 0>, (long long)n3, nz, d_occ3, nullptr, i1, nullptr, pass);
-      if ((s = tile(k_edt_tile<1, 0>, (long long)n3, ny, wy, nz, nz / wy, (long long)ny * nz, (long long)nx * (nz / wy), i1, pass == 0 ? i2 : i2n, nullptr, pass)) != TOPAY_OK) return s;
-    }
-    signed_x((long long)n3, nx, wx, (long long)ny * nz, ((long long)ny * nz) / wx, 0, ((long long)ny * nz) / wx, i2, i2n, e3);
-  }
-  for (int pass = 0; pass < 2 && !small_lines; pass++) {
-    // 3-D: along z (lines (x, y)), along y (lines (x, z)), along x (lines (y, z)) — grid_map.cpp:425-521
-    EdtPass pz{(long long)nx * ny, nz, (long long)nx * ny, 0, (long long)nz, 1, 0, 0};
-    EdtPass py{(long long)nx * nz, ny, (long long)nz, (long long)ny * nz, 1, (long long)nz, 0, 0};
-    EdtPass px{(long long)ny * nz, nx, (long long)ny * nz, 0, 1, (long long)ny * nz, 0, 0};
-    if ((s = launch(k_edt_pass<0, 0, 0>, k_edt_pass<0, 0, 1>, pz, (long long)n3, d_occ3, nullptr, t1, pass)) != TOPAY_OK) return s;
-    if ((s = launch(k_edt_pass<1, 0, 0>, k_edt_pass<1, 0, 1>, py, (long long)n3, nullptr, t1, t2, pass)) != TOPAY_OK) return s;
-    if ((s = launch(k_edt_pass<1, 1, 0>, k_edt_pass<1, 1, 1>, px, (long long)n3, nullptr, t2, e3, pass)) != TOPAY_OK) return s;
-  }
-  // One signed 2-D field from an occupancy grid: along y (lines x), along x (lines y), positive then negative part —
-  // grid_map.cpp:125-207 and, with other seeds, 211-279, 283-351, 355-423
-  auto field2d = [&](const signed char* occ, double* out) -> topay_status {
-    if (small_lines) {
-      const int w2 = pick_w32(ny);
-      int* i1n = i1 + M * n2;
-      direct(k_edt_direct<0, 0>, (long long)n2, ny, occ, nullptr, i1, nullptr, 0);
-      direct(k_edt_direct<0, 0>, (long long)n2, ny, occ, nullptr, i1n, nullptr, 1);
-      signed_x((long long)n2, nx, w2, ny, ny / w2, 0, ny / w2, i1, i1n, out);
-      return TOPAY_OK;
-    }
-    EdtPass qy{(long long)nx, ny, (long long)nx, 0, (long long)ny, 1, 0, 0};
-    EdtPass qx{(long long)ny, nx, (long long)ny, 0, 1, (long long)ny, 0, 0};
-    for (int pass = 0; pass < 2; pass++) {
-      topay_status s2;
-      if ((s2 = launch(k_edt_pass<0, 0, 0>, k_edt_pass<0, 0, 1>, qy, (long long)n2, occ, nullptr, t1, pass)) != TOPAY_OK) return s2;
-      if ((s2 = launch(k_edt_pass<1, 1, 0>, k_edt_pass<1, 1, 1>, qx, (long long)n2, nullptr, t1, out, pass)) != TOPAY_OK) return s2;
-    }
-    return TOPAY_OK;
-  };
-  auto threshold = [&](const double* field, signed char* occ) {
-    const long long n = (long long)(M * n2);
-    hipLaunchKernelGGL(k_edt_threshold, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, field, c->dp.chassis_colli_radius, occ, n);
-  };
-  if ((s = field2d(d_occ2, e2)) != TOPAY_OK) return s;              // esdf_buffer_2d
-  threshold(e2, d_occ2t);
-  if ((s = field2d(d_occ2t, e2i)) != TOPAY_OK) return s;            // esdf_buffer_2d_inflate (355-423)
-  if (project_critical) {
-    const long long n = (long long)(M * n2);
-    hipLaunchKernelGGL(k_edt_project, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const signed char*)d_occ3, d_occ2c,
-                       (long long)n2, nz, (long long)M);
-  }
-  if ((s = field2d(d_occ2c, e2s)) != TOPAY_OK) return s;            // 2-D critical (211-279)
-  threshold(e2s, d_occ2t);
-  if ((s = field2d(d_occ2t, e2c)) != TOPAY_OK) return s;            // critical inflate, stored in esdf_buffer_2d_critical (283-351)
+  if ((s = b.construct(d_occ3, d_occ2, d_occ2c, project_critical)) != TOPAY_OK) return s;
   HIPCHK(hipGetLastError());
   HIPCHK(c->edt.timer.stop(c->stream));
-  // the map slots point into the arena; descriptors as topay_set_map
-  for (int k = 0; k < n_maps; k++) {
-    const int map_id = first_map_id + k;
-    c->map2d[map_id].release(); c->map3d[map_id].release(); c->map2d_inf[map_id].release(); c->map2d_crit[map_id].release();
-    DevMap& m = c->hmaps[map_id];
-    for (int i = 0; i < 3; i++) {
-      m.origin[i] = desc->origin[i]; m.dims[i] = desc->dims[i];
-      m.min_b[i] = desc->min_boundary[i]; m.max_b[i] = desc->max_boundary[i];
-    }
-    m.res = desc->resolution;
-    m.res_inv = 1.0 / desc->resolution;
-    m.esdf2d = (glb_cdp)(e2 + (size_t)k * n2);
-    m.esdf3d = (glb_cdp)(e3 + (size_t)k * n3);
-    m.esdf2d_inflate = (glb_cdp)(e2i + (size_t)k * n2);
-    m.esdf2d_critical = (glb_cdp)(e2c + (size_t)k * n2);
-    c->have_map[map_id] = 1;
-  }
-  HIPCHK(hipMemcpyAsync((char*)c->dmaps.p + sizeof(DevMap) * first_map_id, &c->hmaps[first_map_id], sizeof(DevMap) * n_maps,
-                        hipMemcpyHostToDevice, c->stream));
+  if ((s = b.publish(first_map_id, desc)) != TOPAY_OK) return s;
   HIPCHK(hipStreamSynchronize(c->stream));
   HIPCHK(c->edt.timer.read(&c->edt.ms));
   // the construction's workspace (occupancy, two intermediate volumes, the envelope stacks, the staged results: about
   // five times the maps themselves) is not needed once the fields sit in their map slots
   c->edt.thr.release(); c->edt.tmp1.release(); c->edt.tmp2.release(); c->edt.v.release(); c->edt.z.release(); c->edt.out2.release();
+  return TOPAY_OK;
+}
+
+// Test hook: the plan of n_maps maps of dims, as 19 numbers: small (0 / 1); first (16 / 32 / 64 = ballot width, 0 = direct); wy, wx,
+// w2; lds_y, lds_x, lds_2; then per envelope pass in the order 3-D z, y, x, 2-D y, x: five times stacks in LDS (0 / 1), five times
+// the stacks' LDS bytes; the workspace elements per map.  No context, no device.
+topay_status topay_edt_test_plan(const int dims[3], int n_maps, long long* out) {
+  if (!dims || !out || dims[0] <= 0 || dims[1] <= 0 || dims[2] <= 0 || n_maps <= 0) return TOPAY_ERR_INVALID_ARG;
+  const EdtPlan p = edt_plan(dims[0], dims[1], dims[2], n_maps);
+  const long long head[8] = {p.small, p.first, p.wy, p.wx, p.w2, (long long)p.lds_y, (long long)p.lds_x, (long long)p.lds_2};
+  std::copy(head, head + 8, out);
+  for (int k = 0; k < kEdtPasses; k++) {
+    out[8 + k] = p.stack_lds[k];
+    out[13 + k] = (long long)p.stack_bytes[k];
+  }
+  out[18] = (long long)p.ws_elems;
   return TOPAY_OK;
 }
 
